@@ -44,6 +44,11 @@ class Victims(C.Structure):
     _fields_ = [("pos", vp), ("idx", vp), ("off", vp), ("rows", vp), ("cap", c_i64)]
 
 
+class GemmRoute(C.Structure):
+    _fields_ = [("family", c_i32), ("tm", c_i32), ("tn", c_i32), ("mode", c_i32), ("aligned", c_i32), ("splits", c_i32),
+                ("vec_a", c_i32), ("vec_b", c_i32), ("fast", c_i32)]
+
+
 # name -> (restype, argtypes); every symbol include/cdlrm_hip.h declares
 PROTOTYPES = {
     "cdlrm_abi_version": (C.c_int, []),
@@ -105,6 +110,10 @@ PROTOTYPES = {
     "cdlrm_linear_bwd_work_bytes": (c_u64, [c_i64, c_i32, c_i32]),
     "cdlrm_linear_bwd": (C.c_int, [vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i32, c_i32,
                                    c_i32, c_i32, vp, vp]),
+    "cdlrm_linear_fwd_route": (C.c_int, [vp, c_i64, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_i32, vp, c_i32,
+                                         C.POINTER(GemmRoute)]),
+    "cdlrm_linear_bwd_route": (C.c_int, [vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i32, c_i32,
+                                         c_i32, c_i32, vp, vp, c_i32, C.POINTER(GemmRoute)]),
     "cdlrm_mlp_wgrad_work_bytes": (c_u64, [c_i32, c_i64, vp, vp]),
     "cdlrm_mlp_wgrad": (C.c_int, [c_i32, vp, vp, vp, vp, vp, vp, c_i64, vp, vp, vp, vp]),
     "cdlrm_mlp_wgrad_sgd": (C.c_int, [c_i32, vp, vp, vp, vp, vp, vp, vp, vp, c_f32, c_i64, vp, vp, vp, vp]),

@@ -121,14 +121,15 @@ __global__ void __launch_bounds__(256) k_linear_smallk_rows(const float* __restr
     }
 }
 
-extern "C" int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y,
-                                int64_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+// rec != nullptr: the route query (cdlrm_linear_fwd_route) -- every decision below is taken, its outcome recorded, nothing launched
+static int linear_fwd(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y, int64_t M, int32_t N,
+                      int32_t K, int32_t act, void* stream, const GemmRec* rec) {
     CDLRM_REQUIRE(X && W && Y && M >= 0 && N >= 1 && K >= 1 && ld_x >= K && ld_y >= N, "bad argument");
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint riding on the activation code
     act &= ~CDLRM_GEMM_ALONE;
     CDLRM_REQUIRE(act >= 0 && act <= 2, "bad activation code");
     if (M == 0) return 0;
-    CDLRM_CLEAR_STALE();
+    if (!rec) CDLRM_CLEAR_STALE();
     // (Round 6, measured and removed: this layer on the matrix cores -- a wave owning 16 rows x 256 columns, the weights as
     //  16x16x4 fragments in registers, ascending k, bit-identical -- 10.9 us alone against 8.6 for the register kernel below at
     //  M = 8192 (64 scattered 4-byte weight loads per lane for 64 MFMAs), 0.5542 against 0.5519 ms per c3 step.)
@@ -140,6 +141,10 @@ extern "C" int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, co
         const int rpw = M >= 32768 ? 128 : M >= 4096 ? 32 : 8;
         const int64_t blocks = cdiv(M, rpw) * (N >> 8);
         if (blocks <= 0x7fffffff) {
+            if (rec) {
+                gemm_record(rec, CDLRM_ROUTE_SMALLK_ROWS, 0, 0, 0, 0, 1, 0, 0, 0);
+                return 0;
+            }
             hipLaunchKernelGGL((k_linear_smallk_rows<13>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, X, ld_x, W,
                                bias, Y, ld_y, M, (int)N, rpw, (int)act);
             CDLRM_LAUNCH_CHECK();
@@ -147,6 +152,10 @@ extern "C" int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, co
         }
     }
     if (K <= SK_KMAX && N % 4 == 0 && ld_y % 4 == 0 && aligned16(Y) && cdiv(M, 32) <= 65535) {
+        if (rec) {
+            gemm_record(rec, CDLRM_ROUTE_SMALLK, 0, 0, 0, 0, 1, 0, 0, 0);
+            return 0;
+        }
         dim3 grid((unsigned)cdiv(N, 128), (unsigned)cdiv(M, 32));
         hipLaunchKernelGGL(k_linear_smallk, grid, dim3(256), 0, (hipStream_t)stream, X, ld_x, W, bias, Y, ld_y, M, (int)N,
                            (int)K, (int)act);
@@ -159,7 +168,21 @@ extern "C" int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, co
     g.vecA = aligned16(X) && ld_x % 4 == 0 && K % 4 == 0;
     g.vecB = aligned16(W) && K % 4 == 0;
     g.alone = alone;
-    return launch_gemm<true, true>(g, 1, (hipStream_t)stream);
+    return launch_gemm<true, true>(g, 1, (hipStream_t)stream, rec);
+}
+
+extern "C" int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y,
+                                int64_t M, int32_t N, int32_t K, int32_t act, void* stream) {
+    return linear_fwd(X, ld_x, W, bias, Y, ld_y, M, N, K, act, stream, nullptr);
+}
+
+extern "C" int cdlrm_linear_fwd_route(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y,
+                                      int64_t M, int32_t N, int32_t K, int32_t act, void* stream, int32_t n_cu,
+                                      cdlrm_gemm_route* out) {
+    CDLRM_REQUIRE(out && n_cu >= 1, "bad argument");
+    memset(out, 0, sizeof(*out));
+    const GemmRec rec = {out, n_cu};
+    return linear_fwd(X, ld_x, W, bias, Y, ld_y, M, N, K, act, stream, &rec);
 }
 
 // ---- backward helpers -----------------------------------------------------------------------------
@@ -326,10 +349,10 @@ extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes(int32_t n_layers, int64_t M, cons
     return total;
 }
 
-extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, const float* Y, int64_t ld_y, float* dY,
-                                int64_t ld_dy, float* dX, int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N,
-                                int32_t K, int32_t act, int32_t x_act, void* work, void* stream) {
-    CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
+// rec != nullptr: the route query (cdlrm_linear_bwd_route): rec[0] the dgrad, rec[1] the weight gradient; nothing launched
+static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float* Y, int64_t ld_y, float* dY, int64_t ld_dy,
+                      float* dX, int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N, int32_t K, int32_t act,
+                      int32_t x_act, void* work, void* stream, const GemmRec* rec) {
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint for the dgrad GEMM, riding on the activation code
     act &= ~CDLRM_GEMM_ALONE;
     CDLRM_REQUIRE(X && W && dY && work && M >= 1 && N >= 1 && K >= 1, "bad argument");
@@ -338,13 +361,10 @@ extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, co
     CDLRM_REQUIRE(act >= 0 && act <= 2 && x_act >= 0 && x_act <= 2, "bad activation code");
     CDLRM_REQUIRE(((uintptr_t)work & 255) == 0, "work must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    // a completion event waiting for this call (cdlrm_event_attach_next) rides on the dgrad GEMM when that is the call's only
-    // launch (the training step's use); with several launches it is recorded behind the last one
-    if (act != 0 || dW || !dX) stop_scope.hold(s);
     const int splits = wgrad_splits(M, N, K);
     float* slabs = (float*)work;
     float* cs = (float*)((char*)work + ((((uint64_t)splits * N * K * 4) + 255) & ~(uint64_t)255));
-    if (act != 0) {     // dZ = dY * act'(Y) in place
+    if (act != 0 && !rec) {     // dZ = dY * act'(Y) in place
         const int64_t nb = cdiv(M * N, 256), blocks = nb < 2048 ? nb : 2048;
         hipLaunchKernelGGL(k_act_grad, dim3((unsigned)blocks), dim3(256), 0, s, Y, ld_y, dY, ld_dy, M, N, act);
     }
@@ -356,7 +376,7 @@ extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, co
         g.vecB = aligned16(W) && K % 4 == 0;
         g.mask = X; g.ldmask = ld_x; g.mask_act = x_act;
         g.alone = alone;
-        int rc = launch_gemm<true, false>(g, 1, s);
+        int rc = launch_gemm<true, false>(g, 1, s, rec);
         if (rc) return rc;
     }
     // dW[N,K] = dZ[M,N]^T X[M,K], split over M into slabs summed in slab order; the first column panel of the
@@ -371,9 +391,9 @@ extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, co
         const int zs = (int)cdiv(M, g.kchunk);      // <= splits
         g.C = zs > 1 ? slabs : dW;
         g.colsum = db ? (zs > 1 ? cs : db) : nullptr;
-        int rc = launch_gemm<false, false>(g, zs, s);
+        int rc = launch_gemm<false, false>(g, zs, s, rec ? rec + 1 : nullptr);
         if (rc) return rc;
-        if (zs > 1) {   // one launch sums the dW slabs and the bias-gradient partials
+        if (zs > 1 && !rec) {   // one launch sums the dW slabs and the bias-gradient partials
             int64_t gxa = cdiv((int64_t)N * K, 256);
             if (gxa > 2048) gxa = 2048;
             const int64_t gxb = db ? cdiv(N, 64) : 0;
@@ -381,8 +401,29 @@ extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, co
                                (int)gxa, cs, (int64_t)N, zs, db);
         }
     }
-    CDLRM_LAUNCH_CHECK();
-    return 0;                           // (stop_scope records an event no launch carried)
+    if (!rec) CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, const float* Y, int64_t ld_y, float* dY,
+                                int64_t ld_dy, float* dX, int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N,
+                                int32_t K, int32_t act, int32_t x_act, void* work, void* stream) {
+    CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
+    // a completion event waiting for this call (cdlrm_event_attach_next) rides on the dgrad GEMM when that is the call's only
+    // launch (the training step's use); with several launches it is recorded behind the last one
+    if ((act & ~CDLRM_GEMM_ALONE) != 0 || dW || !dX) stop_scope.hold((hipStream_t)stream);
+    return linear_bwd(X, ld_x, W, Y, ld_y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, stream, nullptr);
+    // (stop_scope records an event no launch carried)
+}
+
+extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float* W, const float* Y, int64_t ld_y, float* dY,
+                                      int64_t ld_dy, float* dX, int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N,
+                                      int32_t K, int32_t act, int32_t x_act, void* work, void* stream, int32_t n_cu,
+                                      cdlrm_gemm_route* out) {
+    CDLRM_REQUIRE(out && n_cu >= 1, "bad argument");
+    memset(out, 0, 2 * sizeof(*out));
+    const GemmRec rec[2] = {{out, n_cu}, {out + 1, n_cu}};
+    return linear_bwd(X, ld_x, W, Y, ld_y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, stream, rec);
 }
 
 // (Round 4 built the two layers with a thin side -- the 13-wide first layer and the 1-wide output layer -- as vector-ALU

@@ -40,6 +40,20 @@ struct GemmArgs {
                                               // kernel of gemm_wide.h wants a whole CU: 96 KB of LDS, one wave per SIMD)
 };
 
+// "Record, don't launch" (cdlrm_linear_fwd_route / _bwd_route): the launch functions below take an optional GemmRec and then
+// write what they chose into *out instead of launching -- the route and the launch come out of the same decisions.  n_cu: the
+// compute-unit count the wide kernel's rule is evaluated for (the launching path asks the device).
+struct GemmRec {
+    cdlrm_gemm_route* out;
+    int n_cu;
+};
+static inline void gemm_record(const GemmRec* rec, int family, int tm, int tn, int mode, int aligned, int splits, int va,
+                               int vb, int fast) {
+    cdlrm_gemm_route& r = *rec->out;
+    r.family = family; r.tm = tm; r.tn = tn; r.mode = mode; r.aligned = aligned; r.splits = splits;
+    r.vec_a = va; r.vec_b = vb; r.fast = fast;
+}
+
 static inline GemmArgs gemm_args() {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
@@ -807,14 +821,25 @@ static void launch_gemm_staged(const GemmArgs& g, dim3 grid, int mode, hipStream
 }
 
 template <bool A_KC, bool B_KC>
-static void launch_gemm_direct(GemmArgs g, int splits, hipStream_t s) {
+static void launch_gemm_direct(GemmArgs g, int splits, hipStream_t s, const GemmRec* rec = nullptr) {
     g.vecC = aligned16(g.C) && g.ldc % 4 == 0 && g.slab % 4 == 0;
     const bool va = A_KC && g.vecA, vb = B_KC && g.vecB;     // only contraction-contiguous operands use 16-B loads
     dim3 grid((unsigned)cdiv(g.N, 32), (unsigned)cdiv(g.M, 32), (unsigned)splits);
     const int64_t klen = g.kchunk < g.K ? g.kchunk : g.K;
     const bool al = direct_aligned<A_KC, B_KC>(g, klen);
     const int mode = direct_mode(klen, al);
-    if (direct_staged<A_KC, B_KC>(g, klen)) {
+    const bool st = direct_staged<A_KC, B_KC>(g, klen);
+    if (rec) {
+        // direct_prefetch's launch-wide conditions (a thread also needs its float4 inside the matrix)
+        const int pre = g.fastep && g.vecC && (g.bias == nullptr || aligned16(g.bias)) &&
+                        (g.mask_act == 0 || (aligned16(g.mask) && g.ldmask % 4 == 0));
+        // the kernel launched below: staged (16-byte loads throughout), the aligned loader (16-byte loads on the
+        // contraction-contiguous operands), the generic one (va / vb)
+        gemm_record(rec, st ? CDLRM_ROUTE_STAGED : CDLRM_ROUTE_DIRECT, 0, 0, mode, st || al, splits, st ? 1 : al ? A_KC : va,
+                    st ? 1 : al ? B_KC : vb, pre);
+        return;
+    }
+    if (st) {
         launch_gemm_staged<A_KC, B_KC>(g, grid, mode, s);
         return;
     }

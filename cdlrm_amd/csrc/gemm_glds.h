@@ -228,7 +228,7 @@ __device__ __forceinline__ void g2_epilogue_full(const GemmArgs& g, f32x16 (&acc
 // what g2_epilogue_full can take: forward = bias (absent or 16-byte loadable) + activation, no mask; dgrad = an activation mask
 // with 16-byte loadable rows (or none), no bias / activation.  `fastep` is set by the host (launch_gemm) from the debug switch.
 template <bool B_KC>
-__device__ __forceinline__ bool g2_full_ok(const GemmArgs& g) {
+__host__ __device__ __forceinline__ bool g2_full_ok(const GemmArgs& g) {
     if (!g.fastep) return false;
     if (B_KC) return g.mask_act == 0 && (g.bias == nullptr || (((uintptr_t)g.bias) & 15) == 0);
     return g.bias == nullptr && g.act == 0 && (g.mask_act == 0 || ((((uintptr_t)g.mask) & 15) == 0 && (g.ldmask & 3) == 0));
@@ -492,14 +492,15 @@ static void launch_gemm2(const GemmArgs& g, int tm, int tn, int splits, hipStrea
 // the wide kernel (gemm_wide.h: k_gemm3, one workgroup per CU on 128x128 tiles) takes the un-split forward / dgrad GEMMs whose
 // tiles fill the chip; defined in gemm_wide.h, which a translation unit that calls launch_gemm includes instead of this file
 template <bool A_KC, bool B_KC>
-static bool gemm3_try(const GemmArgs& g, int splits, hipStream_t s);
+static bool gemm3_try(const GemmArgs& g, int splits, hipStream_t s, const GemmRec* rec);
 
+// rec != nullptr: record the route in *rec->out, launch nothing (gemm.h: GemmRec)
 template <bool A_KC, bool B_KC>
-static int launch_gemm(GemmArgs g, int splits, hipStream_t s) {
+static int launch_gemm(GemmArgs g, int splits, hipStream_t s, const GemmRec* rec = nullptr) {
     if (g.K < 4) g.vecA = g.vecB = 0;
     if constexpr (A_KC || !B_KC) {
-        if (gemm3_try<A_KC, B_KC>(g, splits, s)) {
-            CDLRM_LAUNCH_CHECK();
+        if (gemm3_try<A_KC, B_KC>(g, splits, s, rec)) {
+            if (!rec) CDLRM_LAUNCH_CHECK();
             return 0;
         }
     }
@@ -509,8 +510,8 @@ static int launch_gemm(GemmArgs g, int splits, hipStream_t s) {
     const bool long_narrow = (g.M >= 4096 || g.K >= 4096) && cdiv(g.M, 64) * cdiv(g.N, 64) * splits >= 256 &&
                              gemm2_applies<A_KC, B_KC>(g);
     if (gemm_use_direct(g.M, g.N, splits) && !long_narrow) {
-        launch_gemm_direct<A_KC, B_KC>(g, splits, s);
-        CDLRM_LAUNCH_CHECK();
+        launch_gemm_direct<A_KC, B_KC>(g, splits, s, rec);
+        if (!rec) CDLRM_LAUNCH_CHECK();
         return 0;
     }
     if (gemm2_applies<A_KC, B_KC>(g)) {
@@ -534,6 +535,10 @@ static int launch_gemm(GemmArgs g, int splits, hipStream_t s) {
         // depend on its shape).  At M = 8192 the same shape is one tile per CU and loses (round 2, and again in round 5).
         if (!(g_cdlrm_debug[6] & 16) && A_KC && splits == 1 && tm2 == 2 && cdiv(g.M, 128) * cdiv(g.N, 128) >= 1024) tn2 = 2;
         // (the same shape for the split-M weight gradients of a long batch: a tie, c5 3.7017 against 3.6995 ms, ten rounds -- not taken)
+        if (rec) {      // full tiles of an un-split forward / dgrad take g2_epilogue_full where g2_full_ok holds (gemm2_tile_body)
+            gemm_record(rec, CDLRM_ROUTE_GEMM2, tm2, tn2, 0, 0, splits, 1, 1, A_KC && splits == 1 && g2_full_ok<B_KC>(g));
+            return 0;
+        }
         launch_gemm2<A_KC, B_KC>(g, tm2, tn2, splits, s);
         CDLRM_LAUNCH_CHECK();
         return 0;
@@ -542,8 +547,8 @@ static int launch_gemm(GemmArgs g, int splits, hipStream_t s) {
         // a 13-wide (or 1-wide) side that the DMA kernel cannot load: the LDS-free kernel's 32x32 tiles waste less of the
         // MFMA than the 64x64 staged tile, whatever the number of slabs (the 512 x 13 weight gradient at M = 65536, 128
         // slabs: 1100 us on the tiled kernel, c5's longest launch)
-        launch_gemm_direct<A_KC, B_KC>(g, splits, s);
-        CDLRM_LAUNCH_CHECK();
+        launch_gemm_direct<A_KC, B_KC>(g, splits, s, rec);
+        if (!rec) CDLRM_LAUNCH_CHECK();
         return 0;
     }
     int tm, tn;
@@ -555,6 +560,10 @@ static int launch_gemm(GemmArgs g, int splits, hipStream_t s) {
     if (g.K < 4) g.vecA = g.vecB = 0;
     if (!A_KC && g.M < 4) g.vecA = 0;
     if (!B_KC && g.N < 4) g.vecB = 0;
+    if (rec) {
+        gemm_record(rec, CDLRM_ROUTE_GEMM, tm, tn, 0, 0, splits, g.vecA, g.vecB, 0);
+        return 0;
+    }
     dim3 grid((unsigned)cdiv(g.N, 64 * tn), (unsigned)cdiv(g.M, 64 * tm), (unsigned)splits);
     if (tm == 2 && tn == 2) launch_gemm_v<A_KC, B_KC, 2, 2>(g, grid, s);
     else if (tm == 1 && tn == 2) launch_gemm_v<A_KC, B_KC, 1, 2>(g, grid, s);

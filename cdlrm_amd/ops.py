@@ -562,6 +562,43 @@ def linear_bwd(X, W, Y, dY, dX, dW, db, act: int, work: torch.Tensor, stream=Non
                                       stream_ptr(stream)))
 
 
+ROUTE_FAMILIES = {0: None, 1: "smallk_rows", 2: "smallk", 3: "direct", 4: "staged", 5: "gemm2", 6: "gemm3", 7: "gemm"}
+
+
+def _route(r: _lib.GemmRoute) -> Optional[dict]:
+    fam = ROUTE_FAMILIES[r.family]
+    if fam is None:
+        return None
+    return dict(family=fam, tm=r.tm, tn=r.tn, mode=r.mode, aligned=r.aligned, splits=r.splits, vec_a=r.vec_a, vec_b=r.vec_b,
+                fast=r.fast)
+
+
+def linear_fwd_route(X, W, b, Y, act: int, alone: bool = False, n_cu: int = 256) -> dict:
+    """The kernel linear_fwd(X, W, b, Y, act, alone=alone) launches, from the same decision code, without launching it:
+    family (ROUTE_FAMILIES), tile (tm, tn), direct mode / aligned, splits, vec_a / vec_b, fast (the full-tile epilogue).
+    X, W, b, Y: tensors or anything with .shape, .stride(0) and .data_ptr() -- addresses are looked at for their alignment
+    only, no device is touched.  n_cu: the compute-unit count of the device the rule is evaluated for (MI355X: 256)."""
+    M, K = X.shape
+    N = W.shape[0]
+    out = _lib.GemmRoute()
+    check(_lib.raw().cdlrm_linear_fwd_route(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(b), Y.data_ptr(), Y.stride(0), M, N, K,
+                                            act | (GEMM_ALONE if alone else 0), None, int(n_cu), C.byref(out)))
+    return _route(out)
+
+
+def linear_bwd_route(X, W, Y, dY, dX, dW, db, act: int, x_act: int = 0, alone: bool = False, n_cu: int = 256):
+    """(dgrad, wgrad): the kernels linear_bwd with the same arguments launches for dX and for dW / db (None where it launches
+    none), as linear_fwd_route."""
+    M, K = X.shape
+    N = W.shape[0]
+    out = (_lib.GemmRoute * 2)()
+    check(_lib.raw().cdlrm_linear_bwd_route(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(Y), 0 if Y is None else Y.stride(0),
+                                            dY.data_ptr(), dY.stride(0), ptr(dX), 0 if dX is None else dX.stride(0), ptr(dW),
+                                            ptr(db), M, N, K, act | (GEMM_ALONE if alone else 0), int(x_act), 256, None,
+                                            int(n_cu), out))
+    return _route(out[0]), _route(out[1])
+
+
 def mlp_wgrad_work(M: int, Ns: Sequence[int], Ks: Sequence[int], device) -> torch.Tensor:
     """Scratch for mlp_wgrad over layers with output widths Ns and input widths Ks at batch M."""
     n = len(Ns)

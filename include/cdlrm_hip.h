@@ -440,6 +440,37 @@ int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, const float* 
                      int64_t M, int32_t N, int32_t K, int32_t act, int32_t x_act, void* work,
                      void* stream);
 
+/* Which kernel a GEMM launch of cdlrm_linear_fwd / cdlrm_linear_bwd goes to (the route queries below). */
+#define CDLRM_ROUTE_NONE 0          /* no such launch (no dX / no dW asked for) */
+#define CDLRM_ROUTE_SMALLK_ROWS 1   /* k_linear_smallk_rows: K = 13, weights in registers */
+#define CDLRM_ROUTE_SMALLK 2        /* k_linear_smallk: K <= 32 on the vector ALU */
+#define CDLRM_ROUTE_DIRECT 3        /* k_gemm_direct: LDS-free 32x32 tiles */
+#define CDLRM_ROUTE_STAGED 4        /* k_gemm_staged: 32x32 tiles, coalesced loads through wave-private LDS */
+#define CDLRM_ROUTE_GEMM2 5         /* k_gemm2: LDS-DMA, (64 tm) x (64 tn) tiles */
+#define CDLRM_ROUTE_GEMM3 6         /* k_gemm3: the wide kernel, (32 tm) x (32 tn) tiles, one workgroup per CU */
+#define CDLRM_ROUTE_GEMM 7          /* k_gemm: register-staged, (64 tm) x (64 tn) tiles */
+typedef struct cdlrm_gemm_route {
+    int32_t family;         /* CDLRM_ROUTE_* */
+    int32_t tm, tn;         /* tile: k_gemm / k_gemm2 in units of 64 rows / columns, k_gemm3 IM / JN in units of 32 */
+    int32_t mode;           /* direct / staged: 0 one batch of loads, 1 two, 2 a loop */
+    int32_t aligned;        /* direct: the aligned loader */
+    int32_t splits;         /* contraction slabs (split-M weight gradient: > 1 adds the slab reduction) */
+    int32_t vec_a, vec_b;   /* the kernel's 16-byte-load flags for A / B */
+    int32_t fast;           /* tiles inside the matrix may take the loads-first / in-loop epilogue (k_gemm2 g2_epilogue_full,
+                               k_gemm3 `fast`, the short-batch kernels' direct_prefetch) */
+} cdlrm_gemm_route;
+/* The plan of the same calls without the launches: same arguments (pointers are looked at for their alignment only, nothing is
+ * read or written, no device is touched), plus n_cu, the compute-unit count the wide kernel's rule is evaluated for (256 on
+ * MI355X).  The route comes out of the same decision code the launching call runs.  fwd: out[0]; bwd: out[0] the dgrad GEMM,
+ * out[1] the weight-gradient GEMM (family CDLRM_ROUTE_NONE where the call issues none). */
+int cdlrm_linear_fwd_route(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y,
+                           int64_t ld_y, int64_t M, int32_t N, int32_t K, int32_t act, void* stream, int32_t n_cu,
+                           cdlrm_gemm_route* out);
+int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float* W, const float* Y, int64_t ld_y,
+                           float* dY, int64_t ld_dy, float* dX, int64_t ld_dx, float* dW, float* db,
+                           int64_t M, int32_t N, int32_t K, int32_t act, int32_t x_act, void* work,
+                           void* stream, int32_t n_cu, cdlrm_gemm_route* out);
+
 /* Weight and bias gradients of n_layers Linear layers from the pre-activation gradients dZ[i] [M, N[i]] that
  * cdlrm_linear_bwd(dW = NULL) left behind: dW[i] [N[i], K[i]] = dZ[i]^T X[i], db[i] [N[i]] (entries may be NULL)
  * = column sums of dZ[i].  The arrays are HOST arrays of device pointers / sizes.  Replaces the per-parameter

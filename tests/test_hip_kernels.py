@@ -439,7 +439,9 @@ def test_dense_golden(ops, golden, itself):
                                        # the wide kernel (gemm_wide.h: one workgroup per CU on 128x128 tiles, taken where they fill
                                        # the chip): forward N = 512 with K = 480 (15 K tiles, sigmoid) and its dgrad onto 480
                                        # columns (edge tiles in N, the generic epilogue); K = 256 / 64 (ring run-out: 8 and 2 K
-                                       # tiles); a partial last row panel (16300 = 127 * 128 + 44: clamped source rows)
+                                       # tiles).  16300 = 127 * 128 + 44: its forward is NOT the wide kernel's (M % 64 = 44
+                                       # and 512 tiles of 128x128 > 256 CUs: k_gemm2 64x64 with a partial row panel); its
+                                       # dgrad onto 96 columns is (k_gemm3 2x4, partial last row panel: clamped source rows)
                                        (8192, 512, 480, 2), (8192, 512, 256, 0), (16384, 512, 64, 1), (16300, 512, 96, 1)])
 def test_linear_vs_torch_fp32(ops, M, N, K, act):
     """FP32-MFMA Linear fwd/bwd against a plain torch fp32 reference (CPU, float64 accumulate for the bound).  Long batches run
