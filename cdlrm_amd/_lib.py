@@ -49,6 +49,13 @@ class GemmRoute(C.Structure):
                 ("vec_a", c_i32), ("vec_b", c_i32), ("fast", c_i32)]
 
 
+class EmbBwdRoute(C.Structure):
+    _fields_ = [("sort_chunk", c_i32), ("sort_e", c_i32), ("sort_chunks", c_i32), ("merge_passes", c_i32), ("seg_meta", c_i32),
+                ("keys_in_b", c_i32), ("apply", c_i32), ("arange", c_i32), ("lpr", c_i32), ("reserved", c_i32),
+                ("apply_grid_x", c_i64), ("apply_grid_y", c_i64), ("long_grid", c_i64), ("keys_off", c_i64), ("meta_off", c_i64),
+                ("once_off", c_i64), ("apply_keys_off", c_i64)]
+
+
 # name -> (restype, argtypes); every symbol include/cdlrm_hip.h declares
 PROTOTYPES = {
     "cdlrm_abi_version": (C.c_int, []),
@@ -77,6 +84,7 @@ PROTOTYPES = {
     "cdlrm_embbag_bwd_prepare_window": (C.c_int, [vp, vp, c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, vp, vp]),
     "cdlrm_embbag_bwd_sorted_views": (C.c_int, [vp, vp, c_i32, c_i64, c_i32, vp, vp, vp]),
     "cdlrm_embbag_bwd_apply_sorted": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, c_f32, vp, vp, vp, c_i64, c_i32, c_i32, vp, vp]),
+    "cdlrm_embbag_bwd_route": (C.c_int, [c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(EmbBwdRoute)]),
     "cdlrm_qr_embbag_fwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
     "cdlrm_qr_embbag_bwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp]),
     "cdlrm_bag_fwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, c_i64, c_i32, vp, vp, vp]),

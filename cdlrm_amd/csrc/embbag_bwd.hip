@@ -693,35 +693,46 @@ static bool sorted_in_B(int64_t n) {
 // the sort of `lists` lists of n slot ids each (a batch: one list per table; a window chunk: one per table and batch)
 // (Measured for the look-ahead slices, which have a whole step of slack, and not taken: ONE workgroup per list of 8192 keys -- 83
 //  us on 52 CUs, no merge passes, one launch instead of four -- 0.5401 against 0.5363 ms per c3 step; a tie at a batch of 2048.)
+// rec != nullptr: the route query (cdlrm_embbag_bwd_route) -- every decision below is taken, its outcome recorded, nothing launched
 static int bwd_sort(int lists, int64_t n, const int32_t* slots, int nb, int64_t ld_in, int64_t batch_len, int nbt, int j0,
-                    uint64_t* keysA, uint64_t* keysB, int32_t* meta, uint8_t* once, int32_t* longcount, hipStream_t s) {
+                    uint64_t* keysA, uint64_t* keysB, int32_t* meta, uint8_t* once, int32_t* longcount, hipStream_t s,
+                    cdlrm_emb_bwd_route* rec = nullptr) {
     const int64_t chunk = sort_chunk(n);
     const int64_t nchunks = cdiv(n, chunk);
     const int npow2 = (int)chunk;
-    static bool attr_set = false;
-    if (!attr_set) {
-        CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)k_sort_chunks<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            SORT_CHUNK * 8));
-        attr_set = true;
-    }
     // keys per thread: the chunk spread over the 1024 threads
     const int E = (int)(chunk / SORT_THREADS);
     const dim3 sgrid((unsigned)nchunks, (unsigned)lists);
     const size_t slds = (size_t)SORT_THREADS * E * 8;
     const int wm = nchunks == 1 ? 1 : 0;
+    if (rec) {
+        rec->sort_chunk = (int32_t)chunk; rec->sort_e = E; rec->sort_chunks = (int32_t)nchunks; rec->seg_meta = !wm;
+    } else {
+        static bool attr_set = false;
+        if (!attr_set) {
+            CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)k_sort_chunks<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                SORT_CHUNK * 8));
+            attr_set = true;
+        }
 #define SORT_CALL(E_) hipLaunchKernelGGL(k_sort_chunks<E_>, sgrid, dim3(SORT_THREADS), slds, s, slots, n, keysA, meta, npow2, wm, longcount, once, nb, ld_in, batch_len, nbt, j0)
-    if (E == 1) SORT_CALL(1);
-    else if (E == 2) SORT_CALL(2);
-    else if (E == 4) SORT_CALL(4);
-    else SORT_CALL(8);
+        if (E == 1) SORT_CALL(1);
+        else if (E == 2) SORT_CALL(2);
+        else if (E == 4) SORT_CALL(4);
+        else SORT_CALL(8);
 #undef SORT_CALL
+    }
     uint64_t* cur = keysA;
     uint64_t* alt = keysB;
     for (int64_t run = chunk; run < n; run *= 2) {
         int64_t gx = cdiv(n, 256);
         if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(k_merge_pass, dim3((unsigned)gx, (unsigned)lists), dim3(256), 0, s, cur, alt, n, run, nb, nbt, j0);
+        if (rec) ++rec->merge_passes;
+        else hipLaunchKernelGGL(k_merge_pass, dim3((unsigned)gx, (unsigned)lists), dim3(256), 0, s, cur, alt, n, run, nb, nbt, j0);
         uint64_t* tmp = cur; cur = alt; alt = tmp;
+    }
+    if (rec) {
+        rec->keys_in_b = cur == keysB;
+        return 0;
     }
     if (nchunks > 1) {
         int64_t gx = cdiv(n, 256);
@@ -732,8 +743,8 @@ static int bwd_sort(int lists, int64_t n, const int32_t* slots, int nb, int64_t 
     return 0;
 }
 
-extern "C" int cdlrm_embbag_bwd_prepare(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, void* work, void* stream) {
-    CDLRM_REQUIRE(ctx && slots && work, "null argument");
+static int bwd_prepare(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, void* work, void* stream, cdlrm_emb_bwd_route* rec) {
+    CDLRM_REQUIRE(ctx && (rec || (slots && work)), "null argument");
     CDLRM_REQUIRE(((uintptr_t)work & 255) == 0, "work must be 256-byte aligned");
     CDLRM_REQUIRE(n < ((int64_t)1 << 31) && ctx->T < (1 << 20), "n < 2^31");
     if (n == 0) return 0;
@@ -741,7 +752,11 @@ extern "C" int cdlrm_embbag_bwd_prepare(cdlrm_ctx* ctx, const int32_t* slots, in
     if (g_cdlrm_debug[6] & 2) return 0;     // development build (tools/ab_step.py --attr debug:6): what the step costs WITHOUT the slot sort
 #endif
     BwdWork w = carve(work, ctx->T, n, ctx->D);
-    return bwd_sort(ctx->T, n, slots, 1, n, 0, 1, 0, w.keysA, w.keysB, w.meta, w.once, w.longcount, (hipStream_t)stream);
+    return bwd_sort(ctx->T, n, slots, 1, n, 0, 1, 0, w.keysA, w.keysB, w.meta, w.once, w.longcount, (hipStream_t)stream, rec);
+}
+
+extern "C" int cdlrm_embbag_bwd_prepare(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, void* work, void* stream) {
+    return bwd_prepare(ctx, slots, n, work, stream, nullptr);
 }
 
 // ---- a window chunk's batches sorted at once (the look-ahead resolver's slot ids: cdlrm_window_resolve) ----------------------
@@ -769,16 +784,21 @@ extern "C" uint64_t cdlrm_embbag_bwd_sorted_bytes(int32_t num_tables, int32_t nb
     return 2 * align256(e * 8) + align256(e * 4) + align256(e) + 256;
 }
 
-extern "C" int cdlrm_embbag_bwd_prepare_window(cdlrm_ctx* ctx, const int32_t* wslots, int64_t ld_w, int64_t batch_len,
-                                               int32_t nb, int64_t n, int32_t j0, int32_t count, void* sorted, void* stream) {
-    CDLRM_REQUIRE(ctx && wslots && sorted, "null argument");
+static int bwd_prepare_window(cdlrm_ctx* ctx, const int32_t* wslots, int64_t ld_w, int64_t batch_len, int32_t nb, int64_t n,
+                              int32_t j0, int32_t count, void* sorted, void* stream, cdlrm_emb_bwd_route* rec) {
+    CDLRM_REQUIRE(ctx && (rec || (wslots && sorted)), "null argument");
     CDLRM_REQUIRE(((uintptr_t)sorted & 255) == 0, "sorted must be 256-byte aligned");
     CDLRM_REQUIRE(nb >= 1 && n >= 1 && n < ((int64_t)1 << 31) && (int64_t)ctx->T * nb < 65536, "1 <= nb, T * nb < 65536, n < 2^31");
     CDLRM_REQUIRE(j0 >= 0 && count >= 1 && j0 + count <= nb, "0 <= j0, 1 <= count, j0 + count <= nb");
     CDLRM_REQUIRE(batch_len >= n && ld_w >= (int64_t)(nb - 1) * batch_len + n, "a batch's n slot ids lie inside its batch_len columns");
     SortedWin w = carve_sorted(sorted, ctx->T, nb, n);
     return bwd_sort(ctx->T * count, n, wslots + (int64_t)j0 * batch_len, count, ld_w, batch_len, nb, j0, w.keysA, w.keysB, w.meta,
-                    w.once, w.pad, (hipStream_t)stream);
+                    w.once, w.pad, (hipStream_t)stream, rec);
+}
+
+extern "C" int cdlrm_embbag_bwd_prepare_window(cdlrm_ctx* ctx, const int32_t* wslots, int64_t ld_w, int64_t batch_len,
+                                               int32_t nb, int64_t n, int32_t j0, int32_t count, void* sorted, void* stream) {
+    return bwd_prepare_window(ctx, wslots, ld_w, batch_len, nb, n, j0, count, sorted, stream, nullptr);
 }
 
 extern "C" int cdlrm_embbag_bwd_sorted_views(cdlrm_ctx* ctx, void* sorted, int32_t nb, int64_t n, int32_t j,
@@ -799,12 +819,14 @@ extern "C" int cdlrm_embbag_bwd_once_flags(cdlrm_ctx* ctx, void* work, int64_t n
 
 // sums + row updates over sorted lists: `cur` / `meta` are table 0's list, table t's lies kstride elements further (a batch's own
 // sort: n; a window chunk's: nb * n); aux_phase: the sorted slots are phase-0 aux slots (0 for a batch's own sort: k_take has
-// added the phase); scratch: partials, long-run list and run ends of `work`
+// added the phase); scratch: partials, long-run list and run ends of `work`.  rec != nullptr: the route query -- the kernels and
+// grids are chosen and recorded, nothing is launched
 static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off,
                      const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work, const uint64_t* cur,
-                     const int32_t* meta, int64_t kstride, int aux_phase, uint8_t* touched, void* stream, int skip_once) {
-    CDLRM_REQUIRE(ctx && grad && work, "null argument");
-    CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
+                     const int32_t* meta, int64_t kstride, int aux_phase, uint8_t* touched, void* stream, int skip_once,
+                     cdlrm_emb_bwd_route* rec = nullptr) {
+    CDLRM_REQUIRE(ctx && (rec || (grad && work)), "null argument");
+    CDLRM_REQUIRE(rec || ctx->weight, "cdlrm_ctx_bind_cache first");
     CDLRM_REQUIRE(((uintptr_t)grad & 15) == 0 && ld_bag % 4 == 0 && ld_table % 4 == 0 && ((uintptr_t)work & 255) == 0,
                   "aligned grad rows / work");
     CDLRM_REQUIRE(offsets != nullptr || n_bags == n, "Criteo layout needs n_bags == n");
@@ -825,6 +847,11 @@ static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, i
     const int ways = ctx->ways, aux_add = aux_phase * ctx->aux;
     float4* wt = reinterpret_cast<float4*>(ctx->weight);
     const int64_t aux_total = (int64_t)ctx->aux * ctx->aux_phases;
+    if (rec) {
+        rec->lpr = lpr;
+        rec->arange = offsets == nullptr;
+        rec->apply_keys_off = (int64_t)((const char*)cur - (const char*)work);
+    }
     if (skip_once || (g_cdlrm_debug[6] & 64)) {
         // a lane group per block of SEG_CH sorted positions (k_bwd_blocks): the form for the runs of >= 2 lookups that
         // cdlrm_embbag_bwd_apply_rest is left with (few heads per block).  With every run of one lookup in the list it is slower
@@ -835,6 +862,12 @@ static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, i
         const int64_t cap = cdiv((int64_t)256 * per_cu, T);
         if (g_cdlrm_debug[1] >= 0 && bx > cap) bx = cap;
         dim3 bgrid((unsigned)bx, (unsigned)T);
+        // (the lean form, below: the runs of >= 2 lookups, one lookup per bag)
+        const bool lean = !offsets && skip_once && !(g_cdlrm_debug[6] & 128);
+        if (rec) {
+            rec->apply = lean ? CDLRM_BWD_APPLY_BLOCKS_LEAN : CDLRM_BWD_APPLY_BLOCKS;
+            rec->apply_grid_x = bx; rec->apply_grid_y = T;
+        } else {
 #define BLK_LEAN(L, HU_, RA_)                                                                                      \
     hipLaunchKernelGGL((k_bwd_blocks<L, true, HU_, RA_>), bgrid, dim3(256), 0, s, ctx->d_tab, D4, wt, cur, meta, offsets, n, \
                        n_bags, ld_off, grad, ld_bag, ld_table, lr, w.partials, w.pstride, w.longlist, w.longcount,      \
@@ -845,7 +878,7 @@ static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, i
         // a SIMD, not its own latency chain, that the step pays for (alone it finishes in 30 us either way).  c3, tools/ab_step.py,
         // one box, 4 rounds: heads x rows / lone-head rows 4x4/16: 0.5393 ms, 2x4/8: 0.5357, 1x4/8: 0.5332, 2x4/4: 0.5362,
         // 1x4/4: 0.5350.  cdlrm_debug_set(6, 128): the 4x4/16 form.
-        if (!offsets && skip_once && !(g_cdlrm_debug[6] & 128)) {
+        if (lean) {
             DISPATCH_LPR_B(lpr, BLK_CALL_LEAN)
         } else {
 #define BLK_CALL(L)                                                                                                \
@@ -862,6 +895,7 @@ static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, i
         }
 #undef BLK_CALL_LEAN
 #undef BLK_LEAN
+        }
     } else {
         int64_t gx = cdiv(n, gpb);
         if (gx > 65535) gx = 65535;
@@ -875,6 +909,10 @@ static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, i
         const int64_t cap = cdiv((int64_t)256 * per_cu, T);
         if (g_cdlrm_debug[1] >= 0 && gx > cap) gx = cap;
         dim3 grid((unsigned)gx, (unsigned)T);
+        if (rec) {
+            rec->apply = CDLRM_BWD_APPLY_CHUNKS;
+            rec->apply_grid_x = gx; rec->apply_grid_y = T;
+        } else {
 #define BWD_CALL(L)                                                                                                \
     if (offsets)                                                                                                   \
         hipLaunchKernelGGL((k_bwd_chunks<L, false>), grid, dim3(256), 0, s, ctx->d_tab, D4, wt, cur, meta, offsets, n,    \
@@ -886,9 +924,14 @@ static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, i
                            touched, aux_total, w.runend, kstride, ways, aux_add)
         DISPATCH_LPR_B(lpr, BWD_CALL)
 #undef BWD_CALL
+        }
     }
     int64_t lx = cdiv((int64_t)T * (n / SEG_CH + 1), gpb);
     if (lx > 1024) lx = 1024;
+    if (rec) {
+        rec->long_grid = lx;
+        return 0;
+    }
 #define LONG_CALL(L) hipLaunchKernelGGL(k_bwd_long<L>, dim3((unsigned)lx), dim3(256), 0, s, ctx->d_tab, D4, wt, cur, n, lr, w.partials, w.pstride, w.longlist, w.longcount, touched, aux_total, w.runend, kstride, ways, aux_add)
     DISPATCH_LPR_B(lpr, LONG_CALL)
 #undef LONG_CALL
@@ -913,13 +956,19 @@ extern "C" int cdlrm_embbag_bwd_apply_rest(cdlrm_ctx* ctx, const int64_t* offset
 // The apply over a window chunk's sorted lists (cdlrm_embbag_bwd_prepare_window; keys / meta: batch j's views, tstride = nb * n):
 // no per-batch sort.  `work` only lends its scratch (partial sums, long-run list); its long-run counter must be zero -- every
 // apply leaves it zero, a fresh buffer is zero-filled by the caller.  One lookup per bag (the Criteo layout).
-extern "C" int cdlrm_embbag_bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table,
-                                             float lr, void* work, const uint64_t* keys, const int32_t* meta, int64_t tstride,
-                                             int32_t aux_phase, int32_t rest, uint8_t* touched, void* stream) {
+static int bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work,
+                            const uint64_t* keys, const int32_t* meta, int64_t tstride, int32_t aux_phase, int32_t rest,
+                            uint8_t* touched, void* stream, cdlrm_emb_bwd_route* rec) {
     CDLRM_REQUIRE(ctx && keys && meta && tstride >= n, "null argument / tstride");
     CDLRM_REQUIRE(aux_phase >= 0 && aux_phase < (ctx->aux_phases > 0 ? ctx->aux_phases : 1), "aux_phase outside the geometry's aux_phases");
     return cdlrm_embbag_bwd_apply_core(ctx, nullptr, n, n, 0, grad, ld_bag, ld_table, lr, work, keys, meta, tstride, aux_phase, touched, stream,
-                     rest ? 1 : 0);
+                     rest ? 1 : 0, rec);
+}
+
+extern "C" int cdlrm_embbag_bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table,
+                                             float lr, void* work, const uint64_t* keys, const int32_t* meta, int64_t tstride,
+                                             int32_t aux_phase, int32_t rest, uint8_t* touched, void* stream) {
+    return bwd_apply_sorted(ctx, n, grad, ld_bag, ld_table, lr, work, keys, meta, tstride, aux_phase, rest, touched, stream, nullptr);
 }
 
 extern "C" int cdlrm_embbag_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, const int64_t* offsets, int64_t n,
@@ -928,4 +977,43 @@ extern "C" int cdlrm_embbag_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, const 
     int rc = cdlrm_embbag_bwd_prepare(ctx, slots, n, work, stream);
     if (rc) return rc;
     return cdlrm_embbag_bwd_apply(ctx, offsets, n, n_bags, ld_off, grad, ld_bag, ld_table, lr, work, touched, stream);
+}
+
+// The route query: the calls above on a geometry of num_tables x dim, with `rec` set.  No context, device or buffer exists: `work` /
+// `sorted` are a made-up, aligned base address the buffers are carved from (the offsets below are relative to it), no pointer is read.
+extern "C" int cdlrm_embbag_bwd_route(int32_t num_tables, int32_t dim, int64_t n, int32_t has_offsets, int32_t entry, int32_t nb,
+                                      int32_t j0, int32_t count, cdlrm_emb_bwd_route* out) {
+    CDLRM_REQUIRE(out && num_tables >= 1 && dim >= 4 && dim % 4 == 0, "bad argument");
+    CDLRM_REQUIRE(entry >= CDLRM_BWD_ENTRY_APPLY && entry <= CDLRM_BWD_ENTRY_SORTED_REST, "entry: CDLRM_BWD_ENTRY_*");
+    CDLRM_REQUIRE(entry < CDLRM_BWD_ENTRY_SORTED || !has_offsets, "the window-sorted path has one lookup per bag");
+    memset(out, 0, sizeof(*out));
+    cdlrm_ctx c;
+    c.T = num_tables; c.D = dim;
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);
+    const int64_t* offsets = has_offsets ? reinterpret_cast<const int64_t*>(base) : nullptr;
+    if (entry < CDLRM_BWD_ENTRY_SORTED) {
+        int rc = bwd_prepare(&c, nullptr, n, base, nullptr, out);
+        if (rc || n == 0) return rc;
+        const BwdWork w = carve(base, c.T, n, c.D);
+        out->keys_off = (int64_t)((const char*)(out->keys_in_b ? w.keysB : w.keysA) - base);
+        out->meta_off = (int64_t)((const char*)w.meta - base);
+        out->once_off = (int64_t)((const char*)w.once - base);
+        return cdlrm_embbag_bwd_apply_core(&c, offsets, n, n, 0, nullptr, 4 * dim, dim, 0.f, base, nullptr, nullptr, 0, 0, nullptr,
+                                           nullptr, entry == CDLRM_BWD_ENTRY_REST, out);
+    }
+    int rc = bwd_prepare_window(&c, nullptr, (int64_t)nb * n, n, nb, n, j0, count, base, nullptr, out);
+    if (rc) return rc;
+    const uint64_t* keys;
+    const int32_t* meta;
+    const uint8_t* once;
+    rc = cdlrm_embbag_bwd_sorted_views(&c, base, nb, n, j0, &keys, &meta, &once);
+    if (rc) return rc;
+    const SortedWin w = carve_sorted(base, c.T, nb, n);
+    CDLRM_REQUIRE((out->keys_in_b ? w.keysB : w.keysA) + (int64_t)j0 * n == keys, "the sort and the views disagree on A / B");
+    out->keys_off = (int64_t)((const char*)keys - base);
+    out->meta_off = (int64_t)((const char*)meta - base);
+    out->once_off = (int64_t)((const char*)once - base);
+    // (apply_sorted's `work` is a buffer of its own: its scratch is carved from the same made-up base)
+    return bwd_apply_sorted(&c, n, nullptr, 4 * dim, dim, 0.f, base, keys, meta, (int64_t)nb * n, 0,
+                            entry == CDLRM_BWD_ENTRY_SORTED_REST, nullptr, nullptr, out);
 }

@@ -295,6 +295,27 @@ def embbag_bwd_apply_sorted(ctx: CacheCtx, n: int, grad: torch.Tensor, ld_bag: i
                                                    stream_ptr(stream)))
 
 
+BWD_ENTRIES = {"apply": 0, "rest": 1, "sorted": 2, "sorted_rest": 3}          # include/cdlrm_hip.h: CDLRM_BWD_ENTRY_*
+BWD_APPLY_KERNELS = {0: None, 1: "chunks", 2: "blocks", 3: "blocks_lean"}      # CDLRM_BWD_APPLY_*
+
+
+def embbag_bwd_route(T: int, D: int, n: int, offsets: bool, entry: str, nb: int = 1, j0: int = 0,
+                     count: Optional[int] = None) -> dict:
+    """The kernels one embedding backward launches, from the same decision code, without launching them: entry "apply"
+    (embbag_bwd_prepare + embbag_bwd_apply), "rest" (+ embbag_bwd_apply_rest), "sorted" / "sorted_rest"
+    (embbag_bwd_prepare_window(nb, j0, count) + embbag_bwd_apply_sorted(rest = 0 / 1)) on T tables of D columns with n lookups
+    each, offsets given or not.  Sort (sort_chunk, sort_e, sort_chunks, merge_passes, seg_meta, keys_in_b), apply kernel
+    (BWD_APPLY_KERNELS), arange, lpr, grids under the current cdlrm_debug_set values, and the byte offsets of table 0's sorted
+    keys / run distances / once-only flags in the work buffer (window entries: in the sorted buffer, batch j0).  No device is
+    touched."""
+    out = _lib.EmbBwdRoute()
+    check(_lib.raw().cdlrm_embbag_bwd_route(int(T), int(D), int(n), int(bool(offsets)), BWD_ENTRIES[entry], int(nb), int(j0),
+                                            int(nb - j0 if count is None else count), C.byref(out)))
+    r = {f: getattr(out, f) for f, _ in _lib.EmbBwdRoute._fields_ if f != "reserved"}
+    r["apply"] = BWD_APPLY_KERNELS[r["apply"]]
+    return r
+
+
 # ---- look-ahead window plan -------------------------------------------------------------------------
 
 class WindowPlan:

@@ -192,6 +192,40 @@ int cdlrm_embbag_bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const float* grad, 
                                   void* work, const uint64_t* keys, const int32_t* meta, int64_t tstride, int32_t aux_phase,
                                   int32_t rest, uint8_t* touched, void* stream);
 
+/* Which kernels one embedding backward launches (cdlrm_embbag_bwd_route below). */
+#define CDLRM_BWD_ENTRY_APPLY 0         /* cdlrm_embbag_bwd_prepare + cdlrm_embbag_bwd_apply (= cdlrm_embbag_bwd_sgd) */
+#define CDLRM_BWD_ENTRY_REST 1          /* cdlrm_embbag_bwd_prepare + cdlrm_embbag_bwd_apply_rest */
+#define CDLRM_BWD_ENTRY_SORTED 2        /* cdlrm_embbag_bwd_prepare_window + cdlrm_embbag_bwd_apply_sorted, rest = 0 */
+#define CDLRM_BWD_ENTRY_SORTED_REST 3   /* cdlrm_embbag_bwd_prepare_window + cdlrm_embbag_bwd_apply_sorted, rest = 1 */
+#define CDLRM_BWD_APPLY_CHUNKS 1        /* k_bwd_chunks: a lane group per sorted position */
+#define CDLRM_BWD_APPLY_BLOCKS 2        /* k_bwd_blocks, full form: a lane group per block of 32 positions, 4 heads x 4 rows
+                                           in flight (16 rows for a lone head) */
+#define CDLRM_BWD_APPLY_BLOCKS_LEAN 3   /* k_bwd_blocks, lean form: one head x 4 rows (8 for a lone head) */
+typedef struct cdlrm_emb_bwd_route {
+    int32_t sort_chunk;         /* keys per sorting workgroup (1024, 2048, 8192) */
+    int32_t sort_e;             /* keys per sorting thread (sort_chunk / 1024) */
+    int32_t sort_chunks;        /* sorting workgroups per list */
+    int32_t merge_passes;       /* k_merge_pass launches */
+    int32_t seg_meta;           /* 1: k_seg_meta writes the run distances and once-only flags; 0: the sort kernel does */
+    int32_t keys_in_b;          /* the sorted keys end in keys B (an odd number of merge passes) */
+    int32_t apply;              /* CDLRM_BWD_APPLY_* */
+    int32_t arange;             /* one lookup per bag (offsets NULL) */
+    int32_t lpr;                /* lanes per row: 4 .. 64 */
+    int32_t reserved;
+    int64_t apply_grid_x, apply_grid_y;     /* the apply kernel's grid under the current cdlrm_debug_set values */
+    int64_t long_grid;                      /* k_bwd_long's grid */
+    int64_t keys_off, meta_off, once_off;   /* byte offsets of table 0's sorted keys / run distances / once-only flags inside
+                                               `work` (table t's: t * n elements further), or inside `sorted` for batch j0 of a
+                                               window chunk (table t's: t * nb * n elements further), as _sorted_views gives */
+    int64_t apply_keys_off;                 /* byte offset of the keys the apply reads (== keys_off) */
+} cdlrm_emb_bwd_route;
+/* The plan of one backward without the launches: entry CDLRM_BWD_ENTRY_*, on num_tables tables of dim columns, n lookups per
+ * table, offsets given or not (has_offsets; the window entries take none), nb / j0 / count as _prepare_window takes them (the
+ * other entries ignore them).  The answer comes out of the same decision code the launching calls run; no device is touched and
+ * no pointer is read (the offsets are relative to the buffer's start). */
+int cdlrm_embbag_bwd_route(int32_t num_tables, int32_t dim, int64_t n, int32_t has_offsets, int32_t entry, int32_t nb,
+                           int32_t j0, int32_t count, cdlrm_emb_bwd_route* out);
+
 /* ---------------------------------------------------------------------------------------------
  * Look-ahead window path: Prefetcher.process_batch_slice (cache_manager.py:28-46) and
  * CacheEmbeddings (main_no_ddp.py:148-209), split into plan (side stream, overlaps training of the
