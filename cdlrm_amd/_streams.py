@@ -65,9 +65,9 @@ _LOW = {}               # device index -> the process's second least-urgent stre
 
 
 def low_priority_stream(device):
-    """Another stream of the least urgent priority, distinct from background_stream's (the engine's chunk sort: work whose
-    result is needed many steps later must not queue behind a plan's DMA copies, nor in front of anything a step waits for).
-    One per device and process, like background_stream's."""
+    """Another stream of the least urgent priority, distinct from background_stream's: tools/race_check.py puts the engine's
+    slice sorts there (TrainEngine.sort_st), out of order with every queue a step uses.  One per device and process, like
+    background_stream's."""
     if not is_hip(device):
         return _NullStream()
     from . import _lib

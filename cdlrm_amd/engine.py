@@ -7,12 +7,12 @@ libcdlrm_hip.so launches on preallocated buffers -- no autograd graph, no per-ta
           -> interaction bwd -> fused embedding bwd + sparse SGD || bottom dgrad chain || weight gradients
           -> grad all-reduce (RCCL) -> dense SGD -> every table_agg_freq steps: touched-row merge across ranks
 
-Five HIP streams: main (the chain above), side (embedding backward; the slot sort of batches without a look-ahead
-window), pref (the NEXT batch's take / tag probe and aux-row fill into the other aux region; at long batches also the top
-MLP's weight gradients), the window plan's, and a least-priority one on which `WindowResolver` sorts the slot ids of a
-look-ahead chunk slice by slice, batches ahead of their steps (the embedding backward's sort, off every queue a step waits
-for; its once-only flags let the interaction backward update the slots a batch reads once).  The launch sequence of a step is
-recorded once per control path and replayed (`_step_taped`).
+Four HIP streams: main (the chain above), side (embedding backward; the slot sort of batches without sorted lists; under
+the chained take the next batch's take), pref (with two aux regions the NEXT batch's take / tag probe and aux-row fill into
+the other aux region; the look-ahead chunks' resolve; the slot sorts `WindowResolver` issues slice by slice, batches ahead of
+their steps -- the embedding backward's sort, off every queue a step waits for, whose once-only flags let the interaction
+backward update the slots a batch reads once; at long batches also the top MLP's weight gradients) and the window plan's.
+The launch sequence of a step is recorded once per control path and replayed (`_step_taped`).
 
 `WindowPipeline` is the look-ahead side: it plans window w+1 (unique scan, tag probe, way choice, winners-
 only pinned-host -> HBM row fetch) on a side HIP stream while window w trains, and commits it at the
@@ -20,6 +20,7 @@ boundary (main_no_ddp.py:393-399, 148-209; cache_manager.py:66-115).
 """
 from __future__ import annotations
 
+import itertools
 import math
 import os
 from typing import List, Optional
@@ -32,6 +33,11 @@ from . import _streams as S
 from . import ops
 from ._lib import record as rec
 from .model_no_ddp import DLRM_Net, Embedding_Table_Cache_Group, Embedding_Table_Group, _linears
+
+
+# serial numbers of the slice sorts (WindowResolver.ensure_sorted), unique in the process: the slice events are a ring shared by
+# every resolver of an engine and re-recorded every RING chunks, so a step tells one slice's sort from the next by its serial
+_SORT_SERIAL = itertools.count(1)
 
 
 def square_bags(lS_o, lS_i, device=None, multiple: int = 256):
@@ -524,8 +530,8 @@ class WindowResolver:
         sl = int(getattr(engine, "sort_slice", 2))
         self.SL = max(1, min(max(sl, (sl * 8192) // max(self.width, 1)), self.CH))
         self.sorted_upto = 0        # batches [0, sorted_upto) of the window have had their slice's turn
-        self._sorted_at = {}        # first batch of a slice whose sort was issued -> batches in it (engine.sort_chunks at that time)
-        engine._sev_waited = engine._sev_waited_cur = None   # (the slice events are shared by every resolver of the engine)
+        # first batch of a slice whose sort was issued -> (batches in it, the sort's serial: _SORT_SERIAL)
+        self._sorted_at = {}
         if self.sort_chunks:
             skey = ("wsorted", self.CH, self.width)
             if skey not in engine._bufs:
@@ -558,11 +564,12 @@ class WindowResolver:
         self.chunks.pop(c - self.RING, None)
         last = getattr(self.eng, "_last_sort_ev", None)
         if last is not None and c < self.RING:
-            # The slice sorts read the ring slots' slot ids on a least-priority stream of their own.  Inside a window the slot's
+            # The slice sorts read the ring slots' slot ids on TrainEngine.sort_st (the prefetch stream, where this resolve runs
+            # behind them in order; tools/race_check.py also puts them on a stream of their own).  Inside a window the slot's
             # previous holder is chunk c - 3, whose slices were all waited for by the takes of its batches, long ago; the first
             # chunks of a window recycle slots of the PREVIOUS window, which may have been left early -- a sort whose batches
             # were never trained has no take behind it: this resolve (prefetch stream, issued after this call) is ordered behind
-            # every sort issued so far
+            # every sort issued so far, on whichever stream
             self.eng.pref.wait_event(last)
         b0, b1 = c * self.CH, min(self.nb, (c + 1) * self.CH)
         cols = self.idx[:, b0 * self.B:b1 * self.B]
@@ -628,38 +635,37 @@ class WindowResolver:
             j0 = b0 - c * self.CH
             cnt = min(self.SL, nbc - j0)
             if getattr(eng, "sort_chunks", True):       # (switched per slice by tools/ab_step.py)
-                st = eng.sort_stream(self.width)
+                st = getattr(eng, "sort_st", eng.pref)     # (host-logic stand-ins: the prefetch stream)
                 st.wait_event(ev)                       # the chunk's resolve (prefetch stream)
                 # the ring slot's previous lists were read by embedding updates three chunks back; what the wait really picks is
                 # WHERE in the step the sort runs: behind the last step's embedding update = in that step's tail
-                after = getattr(eng, "sort_after", "emb_done")
-                if after == "interacted":
-                    st.wait_event(eng._events["interacted"])
-                elif eng._emb_done is not None:
+                if eng._emb_done is not None:
                     st.wait_event(eng._emb_done)
                 if getattr(eng, "sort_delay", 0):       # (tools/race_check.py: a late sort shows a consumer that is not ordered behind it)
                     with torch.cuda.stream(st):
                         torch.cuda._sleep(int(eng.sort_delay))
                 ops.embbag_bwd_prepare_window(self.ctx, ws[:, self.col0:], self.B, nbc, self.width,
                                               self._sorted_ring[c % self.RING], stream=st, j0=j0, count=cnt)
-                self._sorted_ev[c % self.RING][j0 // self.SL].record(st)
-                eng._last_sort_ev = self._sorted_ev[c % self.RING][j0 // self.SL]
-                self._sorted_at[b0] = cnt
+                sev = self._sorted_ev[c % self.RING][j0 // self.SL]
+                sev.record(st)
+                eng._last_sort_ev = sev
+                self._sorted_at[b0] = (cnt, next(_SORT_SERIAL))
             self.sorted_upto = b0 + cnt
-            self._sorted_at.pop(b0 - 3 * self.CH, None)
+            self._sorted_at.pop(b0 - self.RING * self.CH, None)
 
     def sorted_views(self, j: int):
-        """(keys, meta, once addresses of batch j's sorted lists, elements between two tables' lists, the slice's event) -- or
-        None: not sorted (yet)."""
+        """(keys, meta, once addresses of batch j's sorted lists, elements between two tables' lists, the slice's event, the
+        slice sort's serial) -- or None: not sorted (yet)."""
         if not self.sort_chunks or j >= self.sorted_upto:
             return None
         c = j // self.CH
         nbc = self._chunk_nb(c)
         jl = j - c * self.CH
-        if (j - jl % self.SL) not in self._sorted_at:
+        at = self._sorted_at.get(j - jl % self.SL)
+        if at is None:
             return None
         k, m, o = ops.embbag_bwd_sorted_views(self.ctx, self._sorted_ring[c % self.RING], nbc, self.width, jl)
-        return k, m, o, nbc * self.width, self._sorted_ev[c % self.RING][jl // self.SL]
+        return k, m, o, nbc * self.width, self._sorted_ev[c % self.RING][jl // self.SL], at[1]
 
     def batch(self, j: int):
         """(wslots view, wsrc view, ready event) of this rank's lookups of batch j of the window."""
@@ -754,7 +760,7 @@ class TrainEngine:
         ne = lambda: S.new_event(self.dev)
         self._events = dict(probed={k: ne() for k in range(4)}, probed_inline=ne(), gathered=ne(), interacted=ne(),
                             emb_done=ne(), wgrad_done=ne(), top_dz=ne(), top_updated=ne(), fwd_mark=ne(), res_slot=ne(),
-                            tier_marked=ne(), bot_dz=ne(), bot_wg=ne())
+                            tier_marked=ne())
         if S.is_hip(self.dev):
             # torch creates the HIP event at the first record: give every engine event its handle now (a launch tape stores
             # handles; a wait recorded before the event's first real record would otherwise push that tape back to Python)
@@ -789,14 +795,13 @@ class TrainEngine:
         # (3.718 against 3.741 ms), 4096 is a tie, 2048 / 1024 keep two regions (0.2422 / 0.2433, 0.1798 / 0.1845 the other way).
         self.gather_alone_min = 16384
         # The top MLP's forward and its input-gradient chain run with no other GEMM beside them in every schedule of the step
-        # (the weight gradients start behind the chain, top_wgrad_after): these launches carry CDLRM_GEMM_ALONE and, where their
-        # 128x128 tiles fill the chip (local batch 8192 x 512-wide layers: 256 tiles on 256 CUs; c5), take the one-workgroup-per-CU
-        # kernel (csrc/gemm_wide.h).  The bottom MLP's backward runs beside the weight gradients and never does (round 6: with
-        # the hint on every GEMM the c3 step took 0.5790 ms against 0.5580 without, with it on these 0.5562).
+        # (the weight gradients start behind the chain): these launches carry CDLRM_GEMM_ALONE and, where their 128x128 tiles
+        # fill the chip (local batch 8192 x 512-wide layers: 256 tiles on 256 CUs; c5), take the one-workgroup-per-CU kernel
+        # (csrc/gemm_wide.h).  The bottom MLP's backward runs beside the weight gradients and never does (round 6: with the hint
+        # on every GEMM the c3 step took 0.5790 ms against 0.5580 without, with it on these 0.5562).  The bottom MLP's forward
+        # carries it too (it runs at the end of the previous step, beside the next batch's take and slot sort: small kernels
+        # that fit beside a wide workgroup): its 512 -> 256 layer on 64x128 tiles, c3 0.5495 against 0.5522 ms
         self.wide_gemm = True
-        # ... and the bottom MLP's forward (it runs at the end of the previous step, beside the next batch's take and slot sort:
-        # small kernels that fit beside a wide workgroup): its 512 -> 256 layer on 64x128 tiles, c3 0.5495 against 0.5522 ms
-        self.wide_gemm_bottom = True
         # the SGD step of the slots a batch reads ONCE rides in the fused interaction backward (cdlrm_gather_interact_bwd_sgd):
         # those lookups' gradient rows are never written or read back, the sorted path is left with the repeated slots.
         # Bit-identical (a single addend has no order); costs the training queue one wait for the slot sort
@@ -804,24 +809,17 @@ class TrainEngine:
         # the slot sort of the embedding backward per look-ahead chunk slice instead of per step (WindowResolver.ensure_sorted);
         # steps of batches without sorted lists (no resolver, multi-hot bags) sort their own
         self.sort_chunks = True
-        # batches per slice.  tools/ab_step.py, one box, four rounds each, c3, against the per-step sort (0.547-0.552 ms): slices of
-        # 1 / 2 / 4 / 8 / 16 batches -1.1 / -1.5 .. -2.2 / -1.1 / -0.8 / +0.4 %: what pays is the sort OFF the queues a step waits for
-        # and the folded once-only update it allows, not the batching -- a long slice is a long visitor in one step's tail
-        # (on the prefetch stream, see sort_on: 1 / 2 / 4 batches -2.7 / -3.3 / -2.7 %, 2 batches behind the interaction backward
-        #  instead of the embedding update -3.1 %)
+        # batches per slice.  tools/ab_step.py, one box, c3, against the per-step sort: slices of 1 / 2 / 4 batches -2.7 / -3.3 /
+        # -2.7 %: what pays is the sort OFF the queues a step waits for and the folded once-only update it allows, not the
+        # batching -- a long slice is a long visitor in one step's tail
         self.sort_slice = 2
-        self.sort_after = "emb_done"
-        # The stream of the slice sorts: "pref" -- issued behind a step, they follow that step's top-MLP weight gradients (and its
+        # The stream of the slice sorts: issued behind a step, they follow that step's top-MLP weight gradients (and its
         # `top_updated` record) on the prefetch stream and run in the step's tail; the next take on that stream is behind them in
-        # order, the one after needs them.  "side": behind the embedding update; "own": a least-priority stream of their own.
-        # tools/ab_step.py, one box: c3 0.5364 / 0.5397 / 0.5380 ms, per-rank 1024 0.1804 / 0.1815 / 0.1835, c5 3.651 / 3.615 /
-        # 3.575.  "own" wins at c5 but is fragile: in the CLI's process (tools/run_cli_c3.sh, same kernels, same schedule) the
-        # step took 1.15 ms instead of 0.54 with it -- whatever hardware queue the runtime gives a SIXTH stream there, the
-        # training queue's kernels ended up behind the sort's waits -- and 0.61 again under rocprofv3; no extra stream, no such
-        # dependence on the runtime's queue mapping.  (The slice lengths above were measured with "own".)
-        self.sort_on = "pref"
+        # order, the one after needs them.  (The side stream and a stream of their own measured no better: DESIGN.md, "Which
+        # stream".)
+        self.sort_st = self.pref
         self._cur_sorted = self._next_sorted = None
-        self._sev_waited = self._sev_waited_cur = None
+        self._next_waited = self._cur_waited = 0    # serial of the last slice each take path waited for (_wait_slices)
         self.slice_wait = True      # (False: tools/race_check.py --negative -- nobody waits for the slices: the check must notice)
         self._last_sort_ev = None
         # --evict-victim-cache (main_no_ddp.py:96, parsed and unused by the reference): behind every step's embedding update
@@ -847,34 +845,13 @@ class TrainEngine:
         # cross-stream events of the step complete WITH the kernel they follow (attached to its launch) instead of being
         # recorded behind it: no marker packet, no bubble on the training queue
         self.attach_events = True
-        self.fold_top_wait = True               # short batches: the wait for the deferred top-MLP update rides on the side stream
-        self.chain_take = True                  # long batches: the next batch's take rides behind the embedding update
-        self.fuse_sgd = True                    # one rank: the dense SGD rides in the weight gradients' reduction pass
-        # one rank, long batches: where the top MLP's weight gradients start -- "top_dz" (behind the top MLP's input-gradient
-        # chain, beside the interaction backward and the bottom MLP's backward), "interacted", "bot_dz" (behind the bottom MLP's
-        # input-gradient chain) or "bot_wg" (behind the bottom MLP's weight gradients: they then run into the next step's
-        # bottom MLP, gather and interaction forward, which leave the MFMA idle)
-        self.top_wgrad_after = "top_dz"
-        # (Round 5, measured and removed: the weight gradients of the top MLP's LAST TWO layers started behind the first GEMM of
-        #  the input-gradient chain -- their dZ are final behind the head kernel, that GEMM is the last reader of their weights --
-        #  to use the MFMA capacity the chain leaves: c3 0.5679 against 0.5646 ms, c5 3.788 against 3.719, per-rank 4096 a tie.
-        #  Like every placement beside that chain since round 1, it costs the chain more than it takes off the second half.)
         # Criteo layout + dot interaction: the gather IS the interaction's operand load (cdlrm_gather_interact_fwd / _bwd) -- the
         # [B, T, D] block between cached EmbeddingBag and interact_features is neither written nor read back (c3: 109 MB + 113 MB
         # per step), the backward reads the rows again from the cache, in front of the batch's embedding update.  Bit-identical
         # to the two operators (False: gather + interaction as two launches; multi-hot bags and "cat" always take those).
         self.fuse_gather = True
-        # fused gather, a knob measured and left OFF (round 5): the sort of the batch's slot ids (the embedding backward's prepare;
-        # side stream) started BEHIND the interaction forward -- an event attached to that launch -- instead of at the head of
-        # the step (two aux regions) or at the tail of the previous one (chained take), so that it runs under the top MLP's
-        # forward.  tools/ab_step.py, same box, six rounds: c3 0.5646 against 0.5632 ms (chained take), 0.5660 against 0.5625 (two
-        # aux regions), per-rank 4096 0.3337 / 0.3306, 1024 0.1787 / 0.1776 -- slower everywhere: the first half of the step is
-        # the training queue's GEMM chain alone, and the sort takes its CUs.  (A third placement -- the next batch's sort behind
-        # this batch's embedding update in the step's tail, two aux regions -- measured 0.5669 against 0.5643, 0.1844 / 0.1810 at
-        # 1024, and was removed.)
-        self.sort_after_fwd = False
-        # (Also measured and removed: the sort in FRONT of the side stream's wait for the previous top-MLP update, two aux
-        #  regions: c3 0.5625 against 0.5608, 2048 0.2392 / 0.2378, 1024 0.1801 / 0.1787, only 4096 gained, 0.3304 / 0.3328.)
+        # (Where the sort of a batch's own slot ids and the top MLP's weight gradients start, the fold of the top-update wait
+        #  and the take schedules were measured as knobs, rounds 1-6, and the losers removed: DESIGN_HISTORY.md.)
         # WindowResolver hands the NEXT step a look-ahead chunk to resolve (`_pending_resolve`, taken when `mark_next` is set): the
         # step issues it on the prefetch stream right behind its interaction forward -- in front of its own weight gradients on that
         # stream --, so the resolve (random 128-B tag reads) runs beside the top MLP's GEMMs, which leave HBM idle, instead of
@@ -957,15 +934,6 @@ class TrainEngine:
         if pr is not None:
             self._issue_resolve(pr, lambda fn, *a: fn(*a), S.current_stream(self.dev), placed=False)
 
-    def sort_stream(self, local_batch: int = 0):
-        """Where a look-ahead chunk's slot lists are sorted (WindowResolver.ensure_sorted): `sort_on`.  (The side stream under the
-        chained take, long batches, instead of the prefetch stream: c5 3.645 against 3.614 ms -- no gain, one rule for all.)"""
-        if self.sort_on == "side":
-            return self.side
-        if self.sort_on == "pref":
-            return self.pref
-        return S.low_priority_stream(self.dev)
-
     def _fused_gather(self, lS_o) -> bool:
         """This step's gather rides in the interaction kernels (fuse_gather)."""
         return bool(self.fuse_gather and lS_o is None and not self.cat and S.is_hip(self.dev)
@@ -978,8 +946,34 @@ class TrainEngine:
     def _chain(self, B: int, next_idx, lS_o) -> bool:
         """Long batches on the window-resident probe: the next batch's take rides behind this step's embedding update on
         the side stream (see _fwd_bwd)."""
-        return (self.chain_take and not self._side_gather(B) and next_idx is not None and self._next_res is not None
-                and lS_o is None)
+        return not self._side_gather(B) and next_idx is not None and self._next_res is not None and lS_o is None
+
+    def _take(self, idx, res, phase: int, which, st):
+        """A batch's (slots, miss_pos, miss_count) into the probe buffers `which`, misses into aux region `phase`, on stream st:
+        its take when the window resolved it (res: WindowResolver.batch), else its tag probe."""
+        out = self._probe_bufs(idx.shape[1], which)
+        if res is None:
+            return ops.embbag_probe(self.ctx, idx, stream=st, aux_phase=phase, out=out)
+        ops.embbag_take(self.ctx, idx, res[0], res[1], out[0], aux_phase=phase, stream=st)
+        return out
+
+    def _wait_slices(self, cur, nxt, B: int, next_idx):
+        """The streams of this batch's and the next batch's takes wait for their slices' sorts (cur / nxt: sorted_views() of
+        the two batches, or None; B, next_idx: as step() has them) -- once per slice sort, told apart by its serial: the slice
+        events are a ring, and an event that comes round again has been recorded by another sort."""
+        if not self.slice_wait:
+            return
+        if nxt is not None and nxt[5] != self._next_waited:
+            # the next batch's take (two aux regions: prefetch stream; chained / single region: side stream) waits for its
+            # slice's sort: this step's successor -- gather, interaction backward (the once-only flags), embedding update -- is
+            # ordered behind that take.  (Not on both: with two aux regions the `gathered` record THIS step's fused forward
+            # waits for sits on the side stream -- a wait for a sort that is still running would hold the training queue.)
+            (self.pref if self.ctx.aux_phases >= 2 and not self._chain(B, next_idx, None) else self.side).wait_event(nxt[4])
+            self._next_waited = nxt[5]
+        if cur is not None and cur[5] != self._cur_waited:
+            # this batch's take, if no earlier step issued it, runs in line on the side stream; its gather follows that stream
+            self.side.wait_event(cur[4])
+            self._cur_waited = cur[5]
 
     def _reduce_avg(self) -> bool:
         """grad /= W followed by all-reduce(SUM) (main_no_ddp.py:239-244) as ONE all-reduce(AVG): on RCCL, for a
@@ -1170,28 +1164,13 @@ class TrainEngine:
                 self._cur_sorted = res[3][0].sorted_views(res[3][1])
             if self._next_res is not None and len(next_res) > 3:
                 self._next_sorted = next_res[3][0].sorted_views(next_res[3][1])
-                if self._next_sorted is not None and self._next_sorted[4] is not self._sev_waited and self.slice_wait:
-                    # the next batch's take (two aux regions: prefetch stream; chained / single region: side stream) waits for
-                    # its slice's sort: this step's successor -- gather, interaction backward (the once-only flags), embedding
-                    # update -- is ordered behind that take
-                    if self.ctx.aux_phases >= 2 and not self._chain(B, next_idx, lS_o):
-                        self.pref.wait_event(self._next_sorted[4])
-                    else:
-                        # (not on both: with two aux regions the `gathered` record THIS step's fused forward waits for sits on the
-                        #  side stream -- a wait for a sort that is still running would hold the training queue, as in round 6's
-                        #  first placement of the sort)
-                        self.side.wait_event(self._next_sorted[4])
-                    self._sev_waited = self._next_sorted[4]
             pf = self._pref
             if (self._cur_sorted is not None and pf is not None and pf["ptr"] == lS_i.data_ptr()
                     and pf["shape"] == tuple(lS_i.shape) and not pf.get("sorted_ok")):
                 # this batch's take was issued by the previous step, BEFORE its slice's sort (a chunk resolved late: short chunks):
                 # nothing orders this step behind that sort -- it sorts its own slots
                 self._cur_sorted = None
-            if self._cur_sorted is not None and self._cur_sorted[4] is not self._sev_waited_cur and self.slice_wait:
-                # this batch's take, if no earlier step issued it, runs in line on the side stream; its gather follows that stream
-                self.side.wait_event(self._cur_sorted[4])
-                self._sev_waited_cur = self._cur_sorted[4]
+            self._wait_slices(self._cur_sorted, self._next_sorted, B, next_idx)
         if res is not None:
             # an in-line take (no prefetched result for this batch) runs on the side stream: behind the chunk's resolve
             self.side.wait_event(res[2])
@@ -1299,12 +1278,7 @@ class TrainEngine:
             prepared = bool(pref.get("prepared"))
         else:
             rec(side.wait_stream, main)
-            if self._res is not None and lS_o is None:
-                slots, miss_pos, miss_count = self._probe_bufs(n, self._phase)
-                ops.embbag_take(ctx, lS_i, self._res[0], self._res[1], slots, aux_phase=self._phase, stream=side)
-            else:
-                slots, miss_pos, miss_count = ops.embbag_probe(ctx, lS_i, stream=side, aux_phase=self._phase,
-                                                               out=self._probe_bufs(n, self._phase))
+            slots, miss_pos, miss_count = self._take(lS_i, self._res if lS_o is None else None, self._phase, self._phase, side)
             probed = ev["probed_inline"]
             rec(probed.record, side)
         n_bags = B if lS_o is None else lS_o.shape[1]
@@ -1325,7 +1299,7 @@ class TrainEngine:
         side_gather = self._side_gather(B)
         if side_gather:
             rec(side.wait_event, probed)
-            if self.fold_top_wait and self.defer_top and not self.cat and not top_waited:
+            if self.defer_top and not self.cat and not top_waited:
                 # the previous step's deferred top-MLP update is waited for HERE, on the side stream in front of the gather:
                 # the one wait the training queue has in front of the interaction (`gathered`) then covers it too -- one
                 # barrier packet less on that queue.  (The update has landed long before the embedding update the gather
@@ -1338,7 +1312,7 @@ class TrainEngine:
         bot_acts = [X]
         for i, (l, act) in enumerate(self.bot):
             y = feat[:, 0, :] if i == len(self.bot) - 1 else buf["bot_y"][i]
-            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm_bottom)
+            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm)
             bot_acts.append(y)
             cur = y
         if side_gather:
@@ -1363,11 +1337,7 @@ class TrainEngine:
             if self._emb_done is not None:
                 rec(pst.wait_event, self._emb_done)
             ph = 1 - self._phase
-            if self._next_res is not None:
-                res = self._probe_bufs(n, ph)
-                ops.embbag_take(ctx, next_idx, self._next_res[0], self._next_res[1], res[0], aux_phase=ph, stream=pst)
-            else:
-                res = ops.embbag_probe(ctx, next_idx, stream=pst, aux_phase=ph, out=self._probe_bufs(n, ph))
+            res = self._take(next_idx, self._next_res, ph, ph, pst)
             evp = ev["probed"][ph]
             rec(evp.record, pst)
             self._pref = dict(ptr=next_idx.data_ptr(), shape=tuple(next_idx.shape), phase=ph,
@@ -1377,17 +1347,13 @@ class TrainEngine:
         if not side_gather:
             rec(side.wait_event, probed)
         attach = self.attach_events and S.is_hip(self.dev)
-        # the sort behind the interaction forward (sort_after_fwd): issued below, behind that launch
-        defer_sort = bool(self.sort_after_fwd and fused and attach and not prepared)
         # sv: this batch's slot lists were sorted with its look-ahead chunk (WindowResolver.ensure_sorted): no sort here, and the
         # once-only slots can be updated by the interaction backward (it reads the sort's flags)
         # (the flags of a batch's OWN sort would cost the training queue a wait for the side stream in front of the interaction
         #  backward: measured 21 us, three times what the folding saves)
         sv = self._cur_sorted if (lS_o is None and n == B) else None
         once = bool(self.fuse_once and fused and sv is not None)
-        if sv is not None:
-            defer_sort = False
-        elif not prepared and not defer_sort:     # (prepared: a chained take sorted this batch's slots right behind itself)
+        if sv is None and not prepared:     # (prepared: a chained take sorted this batch's slots right behind itself)
             ops.embbag_bwd_prepare(ctx, slots, emb_work, stream=side)
         if self.defer_top and not self.cat and not top_waited:
             # the previous step's top-MLP update (weight gradients read R / top_y / top_dy, then all-reduce and SGD on
@@ -1398,14 +1364,11 @@ class TrainEngine:
         if fused:
             if self._gslot is not None:         # bench.py: the kernel that does the gather, timed by its own launch
                 ops.time_next_gather(ctx, self._gslot[0], self._gslot[1])
-            if attach and (defer_sort or self._mark_this):
-                # what the side queues start behind the interaction forward waits for an event that completes WITH this launch
+            if attach and self._mark_this:
+                # the placed resolve (prefetch stream) waits for an event that completes WITH this launch
                 ops.event_attach_next(ev["fwd_mark"], main)
                 self._fwd_marked = True
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
-            if defer_sort:
-                rec(side.wait_event, ev["fwd_mark"])
-                ops.embbag_bwd_prepare(ctx, slots, emb_work, stream=side)
         elif not self.cat:
             ops.interact_fwd(feat, self.itself, R)
         if self._mark_this:
@@ -1427,8 +1390,8 @@ class TrainEngine:
         # for the bottom MLP's output, and the bias gradients are column sums taken inside the wgrad GEMMs.
         last_act = self.top[-1][1]
         split = buf["wgrad_split"]
-        attach = self.attach_events and S.is_hip(self.dev)
-        nb_, wst = len(self.bot), self.wst
+        wst = self.wst
+        sgd_in_wgrad = self.defer_top and not self.multi      # one rank: the dense SGD rides in the weight gradients' reduction pass
 
         n_top = len(self.top)
         if fused_head:
@@ -1447,13 +1410,6 @@ class TrainEngine:
                              threshold=self.loss_threshold, Zc=buf["Zc"], sigmoid_bwd=(last_act == 2))
             rec(self.stat_acc.add_, buf["loss"][1:3])
             dY = buf["top_dy"][-1]
-        # where the top MLP's weight gradients start (one rank: a knob; several ranks: behind the input-gradient chain, their
-        # exchange follows them)
-        late = "top_dz"
-        if split is not None and self.defer_top and not self.multi and not self.cat:
-            late = self.top_wgrad_after
-            if late == "bot_dz" and len(self.bot) < 2:
-                late = "interacted"
         for i in reversed(range(n_top - 1 if fused_head else n_top)):
             l, act = self.top[i]
             if i == len(self.top) - 1 and act == 2:
@@ -1461,7 +1417,7 @@ class TrainEngine:
             elif i < len(self.top) - 1:
                 act = 0                                      # applied by the dgrad epilogue of layer i+1
             dX = dR if i == 0 else buf["top_dy"][i - 1]
-            if i == 0 and attach and split is not None and late == "top_dz":
+            if i == 0 and attach and split is not None:
                 # `top_dz` (every top-layer dZ is final: the weight gradients may start) completes WITH the chain's last GEMM
                 # -- attached to its launch instead of recorded behind it: a record is a marker packet of its own and left
                 # a 6-8 us bubble on the training queue
@@ -1469,29 +1425,24 @@ class TrainEngine:
             ops.linear_bwd(top_acts[i], self.W[l], top_acts[i + 1], dY, dX, None, None, act,
                            buf["lin_work"], x_act=(self.top[i - 1][1] if i > 0 else 0), alone=self.wide_gemm)
             dY = dX
-        def top_wgrad(after):
-            # Every top-layer dZ is final: the top MLP's weight gradients run on their own stream, beside the bottom MLP's
-            # backward.  (Launching each layer's weight gradient as soon as ITS dZ exists -- beside the dgrad chain itself
-            # -- measured slower: 0.810 vs 0.782 ms at B=8192; the chain is the critical path and loses CUs to them.)
-            rec(wst.wait_event, after)
-            fused = self.defer_top and not self.multi and self.fuse_sgd
-            ops.mlp_wgrad(split[1], stream=wst, lr=self.lr if fused else None)
-            if not self.defer_top:
-                rec(ev["wgrad_done"].record, wst)
-            elif not self.multi:
-                if not fused:
-                    ops.sgd_step2(self.param_flat, self.grad_flat, *self.rng_top, self.lr, stream=wst)
-                rec(ev["top_updated"].record, wst)
-
         # (One event on the main queue for both side streams -- recorded behind the interaction backward -- instead of one in
         #  front of it for the weight gradients and one behind it for the embedding backward measured slower at c3, 0.698 vs
         #  0.675 ms: the saved bubble is worth less than the 57 us the weight gradients start later.  The interaction backward
         #  split by rows -- the dense feature's row as its own launch, the rest on the side queue -- measured slower too, 0.718
         #  vs 0.663 ms.  Both schedules were removed in round 3.)
-        if split is not None and late == "top_dz":
+        if split is not None:
+            # Every top-layer dZ is final: the top MLP's weight gradients run on their own stream, beside the interaction
+            # backward and the bottom MLP's backward.  (Launching each layer's weight gradient as soon as ITS dZ exists -- beside
+            # the dgrad chain itself -- measured slower: 0.810 vs 0.782 ms at B=8192; the chain is the critical path and loses CUs
+            # to them.  Later starts measured slower too: DESIGN_HISTORY.md.)
             if not (attach and n_top - (1 if fused_head else 0) > 0):
                 rec(ev["top_dz"].record, main)
-            top_wgrad(ev["top_dz"])
+            rec(wst.wait_event, ev["top_dz"])
+            ops.mlp_wgrad(split[1], stream=wst, lr=self.lr if sgd_in_wgrad else None)
+            if not self.defer_top:
+                rec(ev["wgrad_done"].record, wst)
+            elif not self.multi:
+                rec(ev["top_updated"].record, wst)
         if self.cat:
             # dR is the gradient of the feature block itself; only the bottom MLP's output needs its activation's
             # derivative (the dot path applies it in the interaction backward's epilogue)
@@ -1511,8 +1462,6 @@ class TrainEngine:
         if not attach or self.cat:
             rec(ev["interacted"].record, main)
         rec(side.wait_event, ev["interacted"])
-        if late == "interacted":
-            top_wgrad(ev["interacted"])
         if fused_head and not self.loss_sync:
             # the head's partial sums -> loss buffer + running statistics, off the training queue.  The next head kernel
             # overwrites the partials only behind the next gather, which is ordered behind this stream's embedding update
@@ -1529,20 +1478,13 @@ class TrainEngine:
         if next_idx is not None and not two_phase:
             # single aux region: the next batch's fill can only follow this batch's embedding update
             which = 2 + (self.iter & 1)
-            if self._next_res is not None:
-                res = self._probe_bufs(n, which)
-                ops.embbag_take(ctx, next_idx, self._next_res[0], self._next_res[1], res[0], aux_phase=0, stream=side)
-            else:
-                res = ops.embbag_probe(ctx, next_idx, stream=side, out=self._probe_bufs(n, which))
-            chain_sort = chain and not (self.sort_after_fwd and fused and attach) and self._next_sorted is None
+            res = self._take(next_idx, self._next_res, 0, which, side)
+            chain_sort = chain and self._next_sorted is None
             if chain_sort:
                 # ... and the sort of the next batch's slot ids for ITS backward: here it ends well before the step does; issued
-                # at the head of the next step it shared HBM with that step's gather (the roofline kernel).  (sort_after_fwd: the
-                # next step issues it behind its interaction forward instead)
+                # at the head of the next step it shared HBM with that step's gather (the roofline kernel)
                 ops.embbag_bwd_prepare(ctx, res[0], emb_work, stream=side)
-            # (weight gradients that start later are waited for by the next step's training queue, in front of its
-            #  interaction forward: they may run beside the next gather)
-            chained_top = chain and self.defer_top and not self.multi and split is not None and late == "top_dz"
+            chained_top = chain and sgd_in_wgrad and split is not None
             if chained_top:
                 rec(side.wait_event, ev["top_updated"])     # recorded above, behind this step's top-MLP SGD
             evp = ev["probed"][which]
@@ -1554,29 +1496,14 @@ class TrainEngine:
         for i in reversed(range(1, len(self.bot))):         # layer 0 has no input gradient
             l, act = self.bot[i]
             dX = buf["bot_dy"][i - 1]
-            if i == 1 and late == "bot_dz" and attach:
-                ops.event_attach_next(ev["bot_dz"], main)
             ops.linear_bwd(bot_acts[i], self.W[l], bot_acts[i + 1], dY, dX, None, None, 0,
                            buf["lin_work"], x_act=self.bot[i - 1][1])
             dY = dX
-        if late == "bot_dz":
-            if not attach:
-                rec(ev["bot_dz"].record, main)
-            top_wgrad(ev["bot_dz"])
-        sgd_included = False
         if split is not None:
             split[0].set_x(0, X)
-            fused = self.defer_top and not self.multi and self.fuse_sgd
-            ops.mlp_wgrad(split[0], lr=self.lr if fused else None)
+            ops.mlp_wgrad(split[0], lr=self.lr if sgd_in_wgrad else None)
             if not self.defer_top:
                 rec(main.wait_event, ev["wgrad_done"])
-            elif not self.multi:
-                if not fused:
-                    ops.sgd_step2(self.param_flat, self.grad_flat, *self.rng_bot, self.lr)
-                sgd_included = True
-            if late == "bot_wg":
-                rec(ev["bot_wg"].record, main)
-                top_wgrad(ev["bot_wg"])
         else:
             plan = buf["wgrad"]
             plan.set_x(0, X)
@@ -1592,7 +1519,7 @@ class TrainEngine:
         # else: the next step's gather runs on the side stream, in order behind this embedding update, and its probe waits
         # for emb_done on its own stream -- nothing on the main stream reads the cache rows before the next full join
         # (window boundary, row merge, evaluate(), finish()), so the main queue is spared one more wait (6-8 us bubble)
-        return sgd_included
+        return split is not None and sgd_in_wgrad
 
     # ----------------------------------------------------------------------------------------------
     def evaluate(self, X: torch.Tensor, lS_i: torch.Tensor, lS_o: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1682,8 +1609,7 @@ class TrainEngine:
                bool(hit and pref.get("chained_top")), bool(hit and pref.get("prepared")),
                self._gslot is not None, self.loss_sync,
                (int(self._pending_resolve["cols"].shape[1]), self._pending_resolve["cols"].stride(0)) if self._mark_this else None,
-               self.tape_lanes, self.tape_lanes_below, self.attach_events, self.fold_top_wait, self.top_wgrad_after,
-               self.fuse_gather, self.sort_after_fwd, self.wide_gemm, self.wide_gemm_bottom, self.fuse_once,
+               self.tape_lanes, self.tape_lanes_below, self.attach_events, self.fuse_gather, self.wide_gemm, self.fuse_once,
                None if self._cur_sorted is None else self._cur_sorted[3], self._next_sorted is not None,
                self._res[0].stride(0) if (self._res is not None and not hit) else 0,
                self._next_res[0].stride(0) if self._next_res is not None else 0)
@@ -1698,24 +1624,7 @@ class TrainEngine:
             finally:
                 _lib.stop_recording()
             # pointer arguments equal to one of the per-step tensors become shared cells
-            cells = {"X": C.c_void_p(X.data_ptr()), "T": C.c_void_p(T.data_ptr()), "idx": C.c_void_p(lS_i.data_ptr())}
-            if nxt:
-                cells["next"] = C.c_void_p(next_idx.data_ptr())
-            if self._res is not None and not hit:
-                cells["ws"] = C.c_void_p(self._res[0].data_ptr())
-                cells["wsrc"] = C.c_void_p(self._res[1].data_ptr())
-            if self._next_res is not None:
-                cells["nws"] = C.c_void_p(self._next_res[0].data_ptr())
-                cells["nwsrc"] = C.c_void_p(self._next_res[1].data_ptr())
-            if self._cur_sorted is not None:
-                sv = self._cur_sorted
-                cells["skeys"], cells["smeta"], cells["sonce"] = C.c_void_p(sv[0]), C.c_void_p(sv[1]), C.c_void_p(sv[2])
-            if self._gslot is not None:
-                cells["g0"], cells["g1"] = C.c_void_p(self._gslot[0].handle), C.c_void_p(self._gslot[1].handle)
-            if self._mark_this:             # the placed resolve's chunk: index columns, ring slot, the slot's event
-                pr = self._pending_resolve
-                cells["rcols"], cells["rws"] = C.c_void_p(pr["cols"].data_ptr()), C.c_void_p(pr["ws"].data_ptr())
-                cells["rwsrc"], cells["rev"] = C.c_void_p(pr["wsrc"].data_ptr()), C.c_void_p(int(pr["ev"].cuda_event))
+            cells = {k: C.c_void_p(v) for k, v in self._tape_ptrs(X, T, lS_i, next_idx, hit).items()}
             by_value = {c.value: c for c in cells.values()}
             if len(by_value) != len(cells):
                 return not self.multi      # aliased inputs: stay on the untaped path
@@ -1742,26 +1651,8 @@ class TrainEngine:
                                                                     post.get("prepared", False)))
             return not self.multi
         cells = tape["cells"]
-        cells["X"].value = X.data_ptr()
-        cells["T"].value = T.data_ptr()
-        cells["idx"].value = lS_i.data_ptr()
-        if nxt:
-            cells["next"].value = next_idx.data_ptr()
-        if "ws" in cells:
-            cells["ws"].value = self._res[0].data_ptr()
-            cells["wsrc"].value = self._res[1].data_ptr()
-        if "nws" in cells:
-            cells["nws"].value = self._next_res[0].data_ptr()
-            cells["nwsrc"].value = self._next_res[1].data_ptr()
-        if "skeys" in cells:
-            sv = self._cur_sorted
-            cells["skeys"].value, cells["smeta"].value, cells["sonce"].value = sv[0], sv[1], sv[2]
-        if "g0" in cells:
-            cells["g0"].value, cells["g1"].value = self._gslot[0].handle, self._gslot[1].handle
-        if "rcols" in cells:
-            pr = self._pending_resolve
-            cells["rcols"].value, cells["rws"].value = pr["cols"].data_ptr(), pr["ws"].data_ptr()
-            cells["rwsrc"].value, cells["rev"].value = pr["wsrc"].data_ptr(), int(pr["ev"].cuda_event)
+        for k, v in self._tape_ptrs(X, T, lS_i, next_idx, hit).items():
+            cells[k].value = v
         bufs = self._buffers(B)
         (bufs["wgrad_split"][0] if bufs["wgrad_split"] is not None else bufs["wgrad"]).set_x(0, X)
         if tape["native"] is not None:
@@ -1781,6 +1672,26 @@ class TrainEngine:
             self._pref = dict(ptr=next_idx.data_ptr(), shape=tuple(next_idx.shape), phase=tape["pref"][0], res=tape["pref"][1],
                               chained_top=tape["pref"][2], prepared=tape["pref"][3], sorted_ok=self._next_sorted is not None)
         return not self.multi
+
+    def _tape_ptrs(self, X, T, lS_i, next_idx, hit: bool) -> dict:
+        """The per-step pointers a recorded step reads, by cell name (_step_taped): the same names for every step of one control
+        path (its tape key fixes which of them exist)."""
+        p = {"X": X.data_ptr(), "T": T.data_ptr(), "idx": lS_i.data_ptr()}
+        if next_idx is not None:
+            p["next"] = next_idx.data_ptr()
+        if self._res is not None and not hit:
+            p["ws"], p["wsrc"] = self._res[0].data_ptr(), self._res[1].data_ptr()
+        if self._next_res is not None:
+            p["nws"], p["nwsrc"] = self._next_res[0].data_ptr(), self._next_res[1].data_ptr()
+        if self._cur_sorted is not None:
+            p["skeys"], p["smeta"], p["sonce"] = self._cur_sorted[:3]
+        if self._gslot is not None:
+            p["g0"], p["g1"] = self._gslot[0].handle, self._gslot[1].handle
+        if self._mark_this:             # the placed resolve's chunk: index columns, ring slot, the slot's event
+            pr = self._pending_resolve
+            p["rcols"], p["rws"] = pr["cols"].data_ptr(), pr["ws"].data_ptr()
+            p["rwsrc"], p["rev"] = pr["wsrc"].data_ptr(), int(pr["ev"].cuda_event)
+        return p
 
     # ---- the touched-row merge in deadline order ----------------------------------------------------------------------
     # broadcast_and_aggregate (main_no_ddp.py:250-292) replaces every row any rank touched since the last merge by its mean

@@ -114,7 +114,7 @@ def test_loss_trajectory_and_tag_state(golden, name, pipelined, aux_phases, reso
                                                     ("train_c1", True, 2, False), ("train_stream", True, 2, False),
                                                     # the host far ahead of a slow side stream, a ring slot recycled every 3 steps
                                                     ("train_c1", True, 1, True), ("train_c1", False, 2, True)])
-def test_chained_take_long_batch_path(golden, name, defer, chunk, delay):
+def test_chained_take_at_long_batches(golden, name, defer, chunk, delay):
     """The long-batch schedule (gather alone on the main stream, B >= gather_alone_min) on the window-resident probe: the
     next batch's take follows the embedding update on the side stream and the next gather waits for ONE event recorded
     behind it (and behind the deferred top-MLP update).  Forced here at the goldens' small batches; same trajectory,
@@ -128,7 +128,6 @@ def test_chained_take_long_batch_path(golden, name, defer, chunk, delay):
     eng = TrainEngine(cg, dl, host, lr=eng0.lr, lr_embeds=eng0.lr_embeds, table_agg_freq=eng0.agg_freq,
                       table_agg_op=eng0.agg_op, defer_top_update=defer)
     eng.gather_alone_min = 1
-    assert eng.chain_take
     L = int(g["L"])
     batches = make_batches(g)
     dev_idx = [b[1].to(DEV) for b in batches]

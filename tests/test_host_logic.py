@@ -304,14 +304,11 @@ def test_window_resolver_sorts_slices_ahead_of_their_steps(monkeypatch, CH, SL, 
 
     class Eng:
         ctx, world, rank, dev = Ctx(), 1, 0, torch.device("cpu")
-        pref = side = S._NullStream()
-        sort_chunks, sort_slice, sort_after, _emb_done, _events = True, SL, "emb_done", None, {}
+        pref = side = sort_st = S._NullStream()
+        sort_chunks, sort_slice, _emb_done = True, SL, None
 
         def __init__(self):
             self._bufs, self._pending_resolve, self.mark_next = {}, None, False
-
-        def sort_stream(self, local_batch=0):
-            return S._NullStream()
 
     monkeypatch.setattr(engine.ops, "window_resolve",
                         lambda ctx, cols, lbs, ws, wsrc, stream=None, batch_len=0: log.append(("resolve", ws.data_ptr())))
@@ -360,6 +357,79 @@ def test_window_resolver_sorts_slices_ahead_of_their_steps(monkeypatch, CH, SL, 
             assert j + 2 in first_sorted, "the batch after next has its lists before the step that issues its take"
     assert len(first_sorted) >= nb - 2 * sl - 2
     assert rs.sorted_views(nb) is None
+
+
+def test_slice_waits_tell_slices_apart_by_serial(monkeypatch):
+    """engine.TrainEngine._wait_slices: the streams of a step's takes wait for the sorts of the slices that hold this batch and
+    the next, once per slice sort.  The slice events are a ring, re-recorded every RING chunks: when no step waited for two
+    whole chunks, the slice of a batch three chunks on comes back with the very event objects the last waits used -- recorded
+    by another sort, which has to be waited for again.  Host-side protocol with an engine stand-in (no GPU)."""
+    import cdlrm_amd.engine as engine
+    S = engine.S
+    monkeypatch.setattr(S, "is_hip", lambda dev: True)
+    monkeypatch.setattr(S, "new_event", lambda dev, timing=False: S._NullEvent())
+    monkeypatch.setattr(S, "current_stream", lambda dev: S._NullStream())
+    monkeypatch.setattr(engine.ops, "window_resolve", lambda ctx, cols, lbs, ws, wsrc, stream=None, batch_len=0: None)
+    monkeypatch.setattr(engine.ops, "embbag_bwd_sorted", lambda ctx, nbc, n, dev: torch.zeros(8, dtype=torch.uint8))
+    monkeypatch.setattr(engine.ops, "embbag_bwd_prepare_window", lambda *a, **k: None)
+    monkeypatch.setattr(engine.ops, "embbag_bwd_sorted_views", lambda ctx, buf, nbc, n, jl: (buf.data_ptr(), nbc, jl))
+
+    class Ctx:
+        T, aux_phases = 2, 2
+
+    class Stream(S._NullStream):
+        def __init__(self):
+            self.waits = []
+
+        def wait_event(self, ev):
+            self.waits.append(ev)
+
+    class Eng:
+        ctx, world, rank, dev = Ctx(), 1, 0, torch.device("cpu")
+        sort_chunks, sort_slice, _emb_done, slice_wait = True, 2, None, True
+        _wait_slices = engine.TrainEngine._wait_slices
+
+        def __init__(self):
+            self._bufs, self._pending_resolve, self.mark_next = {}, None, False
+            self.pref, self.side, self.sort_st = Stream(), Stream(), S._NullStream()
+            self._next_waited = self._cur_waited = 0
+
+        def _chain(self, B, next_idx, lS_o):        # two aux regions: the next batch's take is on the prefetch stream
+            return False
+
+    B, CH = 8192, 4
+    nb = (engine.WindowResolver.RING + 2) * CH
+    eng = Eng()
+    rs = engine.WindowResolver(eng, torch.zeros(2, nb * B, dtype=torch.int64), B, chunk=CH)
+    assert rs.SL == 2
+
+    def step_waits(cur, nxt):           # (the resolver's own waits on the prefetch stream are not the step's)
+        np_, ns = len(eng.pref.waits), len(eng.side.waits)
+        eng._wait_slices(cur, nxt, B, None)
+        return eng.pref.waits[np_:], eng.side.waits[ns:]
+
+    waits, last = [], None
+    for j in range(nb - 1):
+        rs.batch(j), rs.batch(j + 1)
+        cur, nxt = rs.sorted_views(j), rs.sorted_views(j + 1)
+        assert cur is not None and nxt is not None, j
+        if j < CH:
+            waits.append(step_waits(cur, nxt))
+            last = (cur, nxt)
+        elif j == (engine.WindowResolver.RING + 1) * CH - 1:
+            # no step waited since the last batch of chunk 0: this batch's slice and the next one's are the slices of batches
+            # CH - 1 and CH, three chunks on -- the same event objects, recorded by later sorts
+            assert cur[4] is last[0][4] and nxt[4] is last[1][4]
+            assert cur[5] != last[0][5] and nxt[5] != last[1][5]
+            pw, sw = step_waits(cur, nxt)
+            assert pw == [nxt[4]], "the next batch's take (two aux regions) waits for its re-recorded slice"
+            assert sw == [cur[4]], "this batch's in-line take waits for its re-recorded slice"
+            break
+        rs.ensure(j + CH + 2)
+    else:
+        pytest.fail("the re-recorded slice was never reached")
+    # before the gap, one wait per slice sort (the two batches of a slice share it): next batches 1, 2-3, 4; this batch 0-1, 2-3
+    assert [(len(p), len(s)) for p, s in waits] == [(1, 1), (1, 0), (0, 1), (1, 0)]
 
 
 def test_window_resolver_hands_due_chunks_to_the_next_step(monkeypatch):

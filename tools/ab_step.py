@@ -83,7 +83,7 @@ def main():
                 h = _lib.raw().cdlrm_stream_create(int(v))
                 made[v] = torch.cuda.ExternalStream(int(h), device=dev)
             if a.attr == "pref_priority":
-                eng.pref = eng.wst = made[v]
+                eng.pref = eng.wst = eng.sort_st = made[v]
             else:
                 eng.side = made[v]
             eng._tapes.clear()

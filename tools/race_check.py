@@ -15,33 +15,26 @@ import torch  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+from cdlrm_amd import _streams as S  # noqa: E402
 from cdlrm_amd.engine import WindowResolver  # noqa: E402
 
+OWN = "own"         # sort_st: the slice sorts on a least-priority stream of their own, out of order with every queue a step uses
 VARIANTS = {
-    "default (three lanes, attached events, folded wait, the gather fused into the interaction kernels)": {},
+    "default (three lanes, attached events, the gather fused into the interaction kernels)": {},
     "two lanes": {"tape_lanes": 2},
     "one lane": {"tape_lanes": 1},
     "recorded events": {"attach_events": False},
-    "wait on the training queue": {"fold_top_wait": False},
-    "unchained take (round-1 schedule)": {"chain_take": False},
     "chained take at every batch (one aux region)": {"gather_alone_min": 1},
     "two aux regions at every batch": {"gather_alone_min": 1 << 30},
-    "slot sort behind the interaction forward": {"sort_after_fwd": True},
-    "slot sort behind the interaction forward, chained take": {"sort_after_fwd": True, "gather_alone_min": 1},
-    "top weight gradients behind the interaction backward": {"top_wgrad_after": "interacted"},
-    "top weight gradients behind the bottom input gradients": {"top_wgrad_after": "bot_dz"},
-    "top weight gradients behind the bottom weight gradients": {"top_wgrad_after": "bot_wg"},
     "gather + interaction as two launches (the block written and read back)": {"fuse_gather": False},
     "slot sort per step (no chunk slices, no folded once-only update)": {"sort_chunks": False},
     "chunk slices, once-only slots in the sorted path": {"fuse_once": False},
     "slices of one batch": {"sort_slice": 1},
-    "slices of five batches, sorted on the side stream": {"sort_slice": 5, "sort_on": "side"},
-    "slices sorted on the side stream, chained take": {"sort_on": "side", "gather_alone_min": 1},
-    "slices behind the interaction backward": {"sort_after": "interacted"},
-    "slices on a least-priority stream of their own": {"sort_on": "own"},
-    "slice sorts 0.2 ms late on their own stream (two aux regions)": {"sort_on": "own", "sort_delay": 400000, "gather_alone_min": 1 << 30},
-    "slice sorts 0.2 ms late on their own stream (chained take)": {"sort_on": "own", "sort_delay": 400000, "gather_alone_min": 1},
-    "slice sorts 0.2 ms late, slices of one batch, no tape": {"sort_on": "own", "sort_delay": 400000, "sort_slice": 1, "use_tape": False},
+    "slices of five batches": {"sort_slice": 5},
+    "slices on a least-priority stream of their own": {"sort_st": OWN},
+    "slice sorts 0.2 ms late on their own stream (two aux regions)": {"sort_st": OWN, "sort_delay": 400000, "gather_alone_min": 1 << 30},
+    "slice sorts 0.2 ms late on their own stream (chained take)": {"sort_st": OWN, "sort_delay": 400000, "gather_alone_min": 1},
+    "slice sorts 0.2 ms late, slices of one batch, no tape": {"sort_st": OWN, "sort_delay": 400000, "sort_slice": 1, "use_tape": False},
     "slice sorts 0.2 ms late on the prefetch stream": {"sort_delay": 400000},
     "python tape": {"native_tape": False},
     "no tape": {"use_tape": False},
@@ -56,7 +49,7 @@ def run(a, knobs, host):
     eng, pipe, syn, B, cg = wl["eng"], wl["pipe"], wl["syn"], wl["B"], wl["cg"]
     eng.tape_lanes_below = 1 << 30          # (multi-lane replay at every batch size here)
     for k, v in knobs.items():
-        setattr(eng, k, v)
+        setattr(eng, k, S.low_priority_stream(dev) if v == OWN else v)
     own = torch.cuda.Stream(device=dev, priority=-1)
     own.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(own):
@@ -100,7 +93,7 @@ def main():
     if a.negative:
         # negative control: slice sorts arrive late and NOTHING waits for them -- the run must leave the reference's bits
         ref = run(a, {}, host)
-        r = run(a, {"sort_on": "own", "sort_delay": 2000000, "slice_wait": False, "gather_alone_min": 1}, host)
+        r = run(a, {"sort_st": OWN, "sort_delay": 2000000, "slice_wait": False, "gather_alone_min": 1}, host)
         same = (r[0] == ref[0] and torch.equal(r[1], ref[1]) and r[2] == ref[2] and torch.equal(r[3], ref[3]))
         print("late slices, nobody waits:", "bit-identical (the check is blind)" if same else "DIFFERS (as it must)")
         sys.exit(1 if same else 0)
