@@ -5,6 +5,7 @@
 // fp32 everywhere (1e-5 loss-trajectory parity): v_mfma_f32_32x32x2_f32 is an exact k-ordered fp32
 // fma chain at the fp32 vector peak (MI355X_MICROARCH.md "Matrix cores").
 #include "gemm_wide.h"
+#include "gemm_bf16.h"
 
 
 // Linear forward with a short contraction (K <= 32: the first bottom layer reads the 13 dense features).  An MFMA
@@ -126,10 +127,17 @@ static int linear_fwd(const float* X, int64_t ld_x, const float* W, const float*
                       int32_t K, int32_t act, void* stream, const GemmRec* rec) {
     CDLRM_REQUIRE(X && W && Y && M >= 0 && N >= 1 && K >= 1 && ld_x >= K && ld_y >= N, "bad argument");
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint riding on the activation code
-    act &= ~CDLRM_GEMM_ALONE;
+    const int bf16 = (act & CDLRM_GEMM_BF16) != 0;         // the opt-in bf16 matrix-core mode (gemm_bf16.h)
+    act &= ~(CDLRM_GEMM_ALONE | CDLRM_GEMM_BF16);
     CDLRM_REQUIRE(act >= 0 && act <= 2, "bad activation code");
     if (M == 0) return 0;
     if (!rec) CDLRM_CLEAR_STALE();
+    if (bf16 && bf16_layer_ok(N, K)) {
+        GemmArgs g = gemm_args();
+        g.A = X; g.lda = ld_x; g.B = W; g.ldb = K; g.C = Y; g.ldc = ld_y; g.slab = 0;
+        g.M = M; g.N = N; g.K = K; g.bias = bias; g.act = act;
+        return launch_gemm_bf16<true, true>(g, (hipStream_t)stream, rec);
+    }
     // (Round 6, measured and removed: this layer on the matrix cores -- a wave owning 16 rows x 256 columns, the weights as
     //  16x16x4 fragments in registers, ascending k, bit-identical -- 10.9 us alone against 8.6 for the register kernel below at
     //  M = 8192 (64 scattered 4-byte weight loads per lane for 64 MFMAs), 0.5542 against 0.5519 ms per c3 step.)
@@ -354,7 +362,8 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
                       float* dX, int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N, int32_t K, int32_t act,
                       int32_t x_act, void* work, void* stream, const GemmRec* rec) {
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint for the dgrad GEMM, riding on the activation code
-    act &= ~CDLRM_GEMM_ALONE;
+    const int bf16 = (act & CDLRM_GEMM_BF16) != 0 && bf16_layer_ok(N, K);     // both GEMMs of the layer in bf16 (gemm_bf16.h)
+    act &= ~(CDLRM_GEMM_ALONE | CDLRM_GEMM_BF16);
     CDLRM_REQUIRE(X && W && dY && work && M >= 1 && N >= 1 && K >= 1, "bad argument");
     CDLRM_REQUIRE(dW || !db, "db without dW (the bias gradient is a by-product of the weight-gradient GEMM)");
     CDLRM_REQUIRE(act == 0 || Y, "activation backward needs Y");
@@ -376,12 +385,36 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
         g.vecB = aligned16(W) && K % 4 == 0;
         g.mask = X; g.ldmask = ld_x; g.mask_act = x_act;
         g.alone = alone;
-        int rc = launch_gemm<true, false>(g, 1, s, rec);
+        int rc = bf16 ? launch_gemm_bf16<true, false>(g, s, rec) : launch_gemm<true, false>(g, 1, s, rec);
         if (rc) return rc;
     }
     // dW[N,K] = dZ[M,N]^T X[M,K], split over M into slabs summed in slab order; the first column panel of the
     // same GEMM sums dZ over the batch (bias gradient)
-    if (dW) {
+    if (dW && bf16) {
+        // the same split-M slabs (at most `splits` of them: the work size does not change) and the same slab reduction
+        GemmArgs g = gemm_args();
+        g.A = dY; g.lda = ld_dy; g.B = X; g.ldb = ld_x; g.ldc = K;
+        g.slab = (int64_t)N * K;
+        g.M = N; g.N = K; g.K = M; g.kchunk = bf16_wgrad_kchunk(M, cdiv(N, 64) * cdiv(K, 64), splits);
+        const int va = bf16_vec<false>(dY, ld_dy, N, M), vb = bf16_vec<false>(X, ld_x, K, M);
+        g.vecA = va; g.vecB = vb;
+        const int zs = (int)cdiv(M, g.kchunk);
+        g.C = zs > 1 ? slabs : dW;
+        g.colsum = db ? (zs > 1 ? cs : db) : nullptr;
+        if (rec) {
+            gemm_record(rec + 1, CDLRM_ROUTE_BF16, 1, 1, 0, 0, zs, va, vb, 0);
+            return 0;
+        }
+        int rc = launch_wgrad_bf16(&g, 1, va, vb, s);
+        if (rc) return rc;
+        if (zs > 1) {
+            int64_t gxa = cdiv((int64_t)N * K, 256);
+            if (gxa > 2048) gxa = 2048;
+            const int64_t gxb = db ? cdiv(N, 64) : 0;
+            hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)(gxa + gxb)), dim3(256), 0, s, slabs, (int64_t)N * K, zs, dW,
+                               (int)gxa, cs, (int64_t)N, zs, db);
+        }
+    } else if (dW) {
         GemmArgs g = gemm_args();
         g.A = dY; g.lda = ld_dy; g.B = X; g.ldb = ld_x; g.ldc = K;
         g.slab = (int64_t)N * K;
@@ -411,7 +444,7 @@ extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, co
     CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
     // a completion event waiting for this call (cdlrm_event_attach_next) rides on the dgrad GEMM when that is the call's only
     // launch (the training step's use); with several launches it is recorded behind the last one
-    if ((act & ~CDLRM_GEMM_ALONE) != 0 || dW || !dX) stop_scope.hold((hipStream_t)stream);
+    if ((act & ~(CDLRM_GEMM_ALONE | CDLRM_GEMM_BF16)) != 0 || dW || !dX) stop_scope.hold((hipStream_t)stream);
     return linear_bwd(X, ld_x, W, Y, ld_y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, stream, nullptr);
     // (stop_scope records an event no launch carried)
 }
@@ -439,28 +472,61 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
 // tiled split-M path, layer after layer.
 __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, const float* __restrict__ g, int64_t n, float lr);
 
+// the reductions of `jobs` (dW slabs + bias-gradient partials, the SGD step inside where a job carries parameters): one grouped
+// launch per GEMM_GROUP_MAX layers
+static void launch_reduce_jobs(const std::vector<ReduceJob>& jobs, hipStream_t s) {
+    for (size_t q0 = 0; q0 < jobs.size(); q0 += GEMM_GROUP_MAX) {
+        ReduceGroup red;
+        memset(&red, 0, sizeof(red));
+        unsigned rblocks = 0;
+        for (size_t q = q0; q < jobs.size() && q < q0 + GEMM_GROUP_MAX; ++q) {
+            red.first[red.n] = rblocks;
+            red.j[red.n] = jobs[q];
+            rblocks += (unsigned)(jobs[q].gxa + cdiv(jobs[q].countB, 64));
+            red.n++;
+        }
+        red.first[red.n] = rblocks;
+        hipLaunchKernelGGL(k_reduce_group, dim3(rblocks), dim3(256), 0, s, red);
+    }
+}
+
+// the dense SGD step (W -= lr dW, b -= lr db) of the given layers, whose gradients needed no reduction pass to ride in
+static int sgd_layers(const std::vector<int>& layers, float* const* dW, float* const* db, float* const* P_w, float* const* P_b,
+                      const int32_t* N, const int32_t* K, float lr, hipStream_t s) {
+    for (int i : layers) {
+        const int64_t cnt = (int64_t)N[i] * K[i];
+        int64_t gx = cdiv(cnt, 256);
+        if (gx > 2048) gx = 2048;
+        hipLaunchKernelGGL(k_sgd, dim3((unsigned)gx), dim3(256), 0, s, P_w[i], (const float*)dW[i], cnt, lr);
+        if (db[i] && P_b && P_b[i])
+            hipLaunchKernelGGL(k_sgd, dim3((unsigned)cdiv(N[i], 256)), dim3(256), 0, s, P_b[i], (const float*)db[i], (int64_t)N[i], lr);
+    }
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
 // P_w / P_b (both or neither): the layers' parameters, stepped by -lr * gradient in the reduction pass (layers whose
 // gradient needs no reduction: one elementwise launch behind it)
+static inline void route_set(cdlrm_gemm_route* out, int family, int tm, int tn, int mode, int aligned, int splits, int va, int vb,
+                             int fast) {
+    const GemmRec rec = {out, 0};
+    gemm_record(&rec, family, tm, tn, mode, aligned, splits, va, vb, fast);
+}
+
 static int mlp_wgrad_impl(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
                           const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
-                          const int32_t* K, void* work, void* stream, float* const* P_w, float* const* P_b, float lr) {
+                          const int32_t* K, void* work, void* stream, float* const* P_w, float* const* P_b, float lr,
+                          cdlrm_gemm_route* rout = nullptr, int n_cu = 0, int64_t extra_tiles = 0) {
     CDLRM_REQUIRE(n_layers >= 0 && (n_layers == 0 || (X && ld_x && dZ && ld_dz && dW && db && N && K)) && M >= 1,
                   "bad argument");
     hipStream_t s = (hipStream_t)stream;
     std::vector<char> stepped((size_t)(n_layers > 0 ? n_layers : 0), 0);
     auto step_rest = [&]() -> int {             // layers the reduction did not cover
         if (!P_w) return 0;
-        for (int i = 0; i < n_layers; ++i) {
-            if (stepped[i]) continue;
-            const int64_t cnt = (int64_t)N[i] * K[i];
-            int64_t gx = cdiv(cnt, 256);
-            if (gx > 2048) gx = 2048;
-            hipLaunchKernelGGL(k_sgd, dim3((unsigned)gx), dim3(256), 0, s, P_w[i], (const float*)dW[i], cnt, lr);
-            if (db[i] && P_b && P_b[i])
-                hipLaunchKernelGGL(k_sgd, dim3((unsigned)cdiv(N[i], 256)), dim3(256), 0, s, P_b[i], (const float*)db[i], (int64_t)N[i], lr);
-        }
-        CDLRM_LAUNCH_CHECK();
-        return 0;
+        std::vector<int> rest;
+        for (int i = 0; i < n_layers; ++i)
+            if (!stepped[i]) rest.push_back(i);
+        return sgd_layers(rest, dW, db, P_w, P_b, N, K, lr, s);
     };
     if (M <= WGRAD_DIRECT_MAX_M) {
         // Small batches, all layers at once.  Layers whose operands are 16-byte loadable go through the LDS-tiled
@@ -491,7 +557,10 @@ static int mlp_wgrad_impl(int32_t n_layers, const float* const* X, const int64_t
         // one split count for the whole group (slabs of the batch); 1 = no slabs, no reduction
         int64_t kchunk = M;
         int zs = 1;
-        if (!tiled.empty()) {
+        // (extra_tiles: 64x64 tiles of layers that share this call's slab count but are launched by the caller -- the bf16
+        //  layers of cdlrm_mlp_wgrad_ex, so that the fp32 layers beside them get the slabs they get in an all-fp32 call)
+        tiles += extra_tiles;
+        if (tiles > 0) {
             // workgroups the grouped launch aims at (slabs = target / tiles).  1024 until round 4 (7 slabs for the top MLP's 160
             // tiles); measured in the step, five rounds each: per-rank batch 1024 -- 384 / 640 / 768 / 896 / 1024 / 1536 ->
             // 0.1802 / 0.1814 / 0.1797 / 0.1813 / 0.1856 / 0.1851 ms; 2048 -- 256 / 384 / 512 / 640 / 768 / 1024 / 2048 ->
@@ -504,6 +573,13 @@ static int mlp_wgrad_impl(int32_t n_layers, const float* const* X, const int64_t
             if (splits < 1) splits = 1;
             kchunk = cdiv(cdiv(M, splits), GBK) * GBK;
             zs = (int)cdiv(M, kchunk);
+        }
+        if (rout) {     // the route query (cdlrm_mlp_wgrad_route): one entry per layer, nothing launched
+            for (size_t q = 0; q < tiled.size(); ++q)
+                route_set(&rout[tiled_layer[q]], CDLRM_ROUTE_GEMM, 1, 1, 0, 0, zs, 1, 1, 0);
+            for (size_t q = 0; q < direct.size(); ++q)
+                route_set(&rout[direct_layer[q]], CDLRM_ROUTE_DIRECT, 0, 0, 0, 0, zs, direct[q].vecA, direct[q].vecB, 0);
+            return 0;
         }
         CDLRM_REQUIRE(zs == 1 || (work && ((uintptr_t)work & 255) == 0), "work must be 256-byte aligned");
         char* wp = (char*)work;
@@ -557,25 +633,13 @@ static int mlp_wgrad_impl(int32_t n_layers, const float* const* X, const int64_t
             int rc = launch_wgrad_group(direct.data(), (int)direct.size(), s);
             if (rc) return rc;
         }
-        for (size_t q0 = 0; q0 < jobs.size(); q0 += GEMM_GROUP_MAX) {
-            ReduceGroup red;
-            memset(&red, 0, sizeof(red));
-            unsigned rblocks = 0;
-            for (size_t q = q0; q < jobs.size() && q < q0 + GEMM_GROUP_MAX; ++q) {
-                red.first[red.n] = rblocks;
-                red.j[red.n] = jobs[q];
-                rblocks += (unsigned)(jobs[q].gxa + cdiv(jobs[q].countB, 64));
-                red.n++;
-            }
-            red.first[red.n] = rblocks;
-            hipLaunchKernelGGL(k_reduce_group, dim3(rblocks), dim3(256), 0, s, red);
-        }
+        launch_reduce_jobs(jobs, s);
         CDLRM_LAUNCH_CHECK();
         return step_rest();
     }
     // Long batches: per layer one split-M GEMM of the tiled (or, for degenerate shapes, the LDS-free) kernel into the
     // layer's own slabs, then ONE grouped reduction of all layers' slabs and bias partials.
-    CDLRM_REQUIRE(work && ((uintptr_t)work & 255) == 0, "work must be 256-byte aligned");
+    CDLRM_REQUIRE(rout || (work && ((uintptr_t)work & 255) == 0), "work must be 256-byte aligned");
     char* wp = (char*)work;
     std::vector<ReduceJob> jobs;
     for (int i = 0; i < n_layers; ++i) {
@@ -592,6 +656,11 @@ static int mlp_wgrad_impl(int32_t n_layers, const float* const* X, const int64_t
         const int zs = (int)cdiv(M, g.kchunk);
         g.C = dW[i];
         g.colsum = db[i];
+        if (rout) {
+            const GemmRec rec = {&rout[i], n_cu};
+            (void)launch_gemm<false, false>(g, zs, s, &rec);
+            continue;
+        }
         if (zs > 1) {
             float* slabs = (float*)wp;
             wp += (((uint64_t)zs * cnt * 4) + 255) & ~(uint64_t)255;
@@ -614,19 +683,8 @@ static int mlp_wgrad_impl(int32_t n_layers, const float* const* X, const int64_t
         int rc = launch_gemm<false, false>(g, zs, s);
         if (rc) return rc;
     }
-    for (size_t q0 = 0; q0 < jobs.size(); q0 += GEMM_GROUP_MAX) {
-        ReduceGroup red;
-        memset(&red, 0, sizeof(red));
-        unsigned rblocks = 0;
-        for (size_t q = q0; q < jobs.size() && q < q0 + GEMM_GROUP_MAX; ++q) {
-            red.first[red.n] = rblocks;
-            red.j[red.n] = jobs[q];
-            rblocks += (unsigned)(jobs[q].gxa + cdiv(jobs[q].countB, 64));
-            red.n++;
-        }
-        red.first[red.n] = rblocks;
-        hipLaunchKernelGGL(k_reduce_group, dim3(rblocks), dim3(256), 0, s, red);
-    }
+    if (rout) return 0;
+    launch_reduce_jobs(jobs, s);
     CDLRM_LAUNCH_CHECK();
     return step_rest();
 }
@@ -646,6 +704,165 @@ extern "C" int cdlrm_mlp_wgrad_sgd(int32_t n_layers, const float* const* X, cons
                                    void* stream) {
     CDLRM_REQUIRE(n_layers == 0 || (W && b), "parameters missing");
     return mlp_wgrad_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, work, stream, W, b, lr);
+}
+
+// ---- the bf16 mode of the weight gradients (flags & CDLRM_GEMM_BF16; gemm_bf16.h) --------------------------------------------
+// The layers the shape rule admits (bf16_layer_ok) leave the fp32 plan: one grouped bf16 launch of all of them on 64x64 tiles,
+// one slab length for the group (bf16_wgrad_kchunk), then one grouped reduction of their slabs (k_reduce_group, with the SGD step
+// when asked).  The other layers (the 13-wide input, the 1-wide head) go through the fp32 plan above, unchanged, in front --
+// with the front part of `work`; the bf16 slabs follow it.
+struct Bf16Wgrad {
+    std::vector<int> fp, bf;         // layer indices: fp32 plan, bf16 group
+    int64_t kchunk = 0;              // slab length of the bf16 group
+    int zs = 1;                      // slab count of the bf16 group
+    uint64_t fp_bytes = 0;           // the fp32 plan's work bytes (offset of the bf16 slabs)
+};
+
+static void bf16_wgrad_plan(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K, Bf16Wgrad& p) {
+    int64_t tiles = 0;
+    for (int i = 0; i < n_layers; ++i) {
+        if (bf16_layer_ok(N[i], K[i])) {
+            p.bf.push_back(i);
+            tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
+        } else {
+            p.fp.push_back(i);
+        }
+    }
+    p.kchunk = bf16_wgrad_kchunk(M, tiles, INT64_MAX);
+    p.zs = (int)cdiv(M, p.kchunk);
+    if (!p.fp.empty()) {
+        std::vector<int32_t> n, k;
+        for (int i : p.fp) { n.push_back(N[i]); k.push_back(K[i]); }
+        p.fp_bytes = cdlrm_mlp_wgrad_work_bytes((int32_t)p.fp.size(), M, n.data(), k.data());
+    }
+}
+
+extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes_ex(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K,
+                                                  int32_t flags) {
+    if (!(flags & CDLRM_GEMM_BF16)) return cdlrm_mlp_wgrad_work_bytes(n_layers, M, N, K);
+    if (!N || !K) return 0;
+    Bf16Wgrad p;
+    bf16_wgrad_plan(n_layers, M, N, K, p);
+    uint64_t total = p.fp_bytes + 256;
+    if (p.zs > 1)
+        for (int i : p.bf)
+            total += (((uint64_t)p.zs * N[i] * K[i] * 4 + 255) & ~(uint64_t)255) + (((uint64_t)p.zs * N[i] * 4 + 255) & ~(uint64_t)255);
+    return total;
+}
+
+// rout != nullptr: the route query (one entry per layer), nothing launched
+static int mlp_wgrad_ex_impl(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                             const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
+                             const int32_t* K, int32_t flags, void* work, void* stream, float* const* P_w, float* const* P_b,
+                             float lr, cdlrm_gemm_route* rout, int n_cu) {
+    CDLRM_REQUIRE((flags & ~CDLRM_GEMM_BF16) == 0, "bad flags");
+    if (!(flags & CDLRM_GEMM_BF16))
+        return mlp_wgrad_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, work, stream, P_w, P_b, lr, rout, n_cu);
+    CDLRM_REQUIRE(n_layers >= 0 && (n_layers == 0 || (X && ld_x && dZ && ld_dz && dW && db && N && K)) && M >= 1,
+                  "bad argument");
+    CDLRM_REQUIRE(rout || (work && ((uintptr_t)work & 255) == 0), "work must be 256-byte aligned");
+    for (int i = 0; i < n_layers; ++i)
+        CDLRM_REQUIRE(X[i] && dZ[i] && dW[i] && N[i] >= 1 && K[i] >= 1 && ld_x[i] >= K[i] && ld_dz[i] >= N[i],
+                      "bad layer argument");
+    hipStream_t s = (hipStream_t)stream;
+    Bf16Wgrad p;
+    bf16_wgrad_plan(n_layers, M, N, K, p);
+    if (!p.fp.empty()) {        // the fp32 layers: the fp32 plan of just those layers, with the slab count of the whole call
+        int64_t extra_tiles = 0;        // the bf16 layers the fp32 plan would have put on its tiled kernel (same test)
+        for (int i : p.bf) {
+            const bool va = aligned16(dZ[i]) && ld_dz[i] % 4 == 0 && N[i] % 4 == 0;
+            const bool vb = aligned16(X[i]) && ld_x[i] % 4 == 0 && K[i] % 4 == 0;
+            if (va && vb && M >= 256) extra_tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
+        }
+        const size_t nf = p.fp.size();
+        std::vector<const float*> fx(nf), fdz(nf);
+        std::vector<float*> fdw(nf), fdb(nf), fpw(nf), fpb(nf);
+        std::vector<int64_t> fldx(nf), flddz(nf);
+        std::vector<int32_t> fn(nf), fk(nf);
+        std::vector<cdlrm_gemm_route> fr(nf);
+        for (size_t q = 0; q < nf; ++q) {
+            const int i = p.fp[q];
+            fx[q] = X[i]; fdz[q] = dZ[i]; fdw[q] = dW[i]; fdb[q] = db[i]; fldx[q] = ld_x[i]; flddz[q] = ld_dz[i];
+            fn[q] = N[i]; fk[q] = K[i];
+            fpw[q] = P_w ? P_w[i] : nullptr; fpb[q] = (P_w && P_b) ? P_b[i] : nullptr;
+        }
+        memset(fr.data(), 0, nf * sizeof(cdlrm_gemm_route));
+        int rc = mlp_wgrad_impl((int32_t)nf, fx.data(), fldx.data(), fdz.data(), flddz.data(), fdw.data(), fdb.data(), M, fn.data(),
+                                fk.data(), work, stream, P_w ? fpw.data() : nullptr, P_w ? fpb.data() : nullptr, lr,
+                                rout ? fr.data() : nullptr, n_cu, extra_tiles);
+        if (rc) return rc;
+        if (rout)
+            for (size_t q = 0; q < nf; ++q) rout[p.fp[q]] = fr[q];
+    }
+    if (p.bf.empty()) return 0;
+    std::vector<GemmArgs> probs;
+    std::vector<ReduceJob> jobs;
+    char* wp = (char*)work + p.fp_bytes;
+    int va = 1, vb = 1;
+    for (int i : p.bf) {
+        const int64_t cnt = (int64_t)N[i] * K[i];
+        GemmArgs g = gemm_args();
+        g.A = dZ[i]; g.lda = ld_dz[i]; g.B = X[i]; g.ldb = ld_x[i]; g.ldc = K[i];
+        g.slab = cnt;
+        g.M = N[i]; g.N = K[i]; g.K = M; g.kchunk = p.kchunk;
+        g.vecA = bf16_vec<false>(dZ[i], ld_dz[i], N[i], M);
+        g.vecB = bf16_vec<false>(X[i], ld_x[i], K[i], M);
+        va &= g.vecA; vb &= g.vecB;
+        g.C = dW[i];
+        g.colsum = db[i];
+        if (p.zs > 1) {
+            float* slabs = (float*)wp;
+            wp += (((uint64_t)p.zs * cnt * 4) + 255) & ~(uint64_t)255;
+            float* cs = (float*)wp;
+            wp += (((uint64_t)p.zs * N[i] * 4) + 255) & ~(uint64_t)255;
+            g.C = slabs;
+            g.colsum = db[i] ? cs : nullptr;
+            ReduceJob r;
+            r.partA = slabs; r.countA = cnt; r.outA = dW[i];
+            int64_t gxa = cdiv(cnt, 256);
+            if (gxa > 1024) gxa = 1024;
+            r.gxa = (int)gxa;
+            r.partB = cs; r.countB = db[i] ? N[i] : 0; r.outB = db[i];
+            r.splits = p.zs;
+            r.novec = g_cdlrm_debug[2];
+            r.pA = P_w ? P_w[i] : nullptr; r.pB = (P_w && P_b && db[i]) ? P_b[i] : nullptr; r.lr = lr;
+            jobs.push_back(r);
+        }
+        probs.push_back(g);
+    }
+    if (rout) {
+        for (int i : p.bf) route_set(&rout[i], CDLRM_ROUTE_BF16, 1, 1, 0, 0, p.zs, va, vb, 0);
+        return 0;
+    }
+    int rc = launch_wgrad_bf16(probs.data(), (int)probs.size(), va, vb, s);
+    if (rc) return rc;
+    launch_reduce_jobs(jobs, s);
+    if (P_w && p.zs == 1) return sgd_layers(p.bf, dW, db, P_w, P_b, N, K, lr, s);     // un-split: no reduction pass to ride in
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cdlrm_mlp_wgrad_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                                  const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
+                                  const int32_t* K, int32_t flags, void* work, void* stream) {
+    return mlp_wgrad_ex_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, nullptr, nullptr, 0.f, nullptr, 0);
+}
+
+extern "C" int cdlrm_mlp_wgrad_sgd_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                                      const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W,
+                                      float* const* b, float lr, int64_t M, const int32_t* N, const int32_t* K, int32_t flags,
+                                      void* work, void* stream) {
+    CDLRM_REQUIRE(n_layers == 0 || (W && b), "parameters missing");
+    return mlp_wgrad_ex_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, W, b, lr, nullptr, 0);
+}
+
+extern "C" int cdlrm_mlp_wgrad_route(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                                     const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
+                                     const int32_t* K, int32_t flags, int32_t n_cu, cdlrm_gemm_route* out) {
+    CDLRM_REQUIRE(out && n_cu >= 1 && n_layers >= 0, "bad argument");
+    memset(out, 0, (size_t)n_layers * sizeof(*out));
+    return mlp_wgrad_ex_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, nullptr, nullptr, nullptr, nullptr, 0.f, out,
+                             n_cu);
 }
 
 // =================================================================================================

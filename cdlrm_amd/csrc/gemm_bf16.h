@@ -1,0 +1,347 @@
+// bf16 matrix-core GEMM for gfx950: the opt-in `CDLRM_GEMM_BF16` mode of the MLP layers ("bf16 mode").
+//
+//   C[m,n] = sum_k bf16(A(m,k)) * bf16(B(k,n))     fp32 operands in HBM, fp32 accumulation, fp32 epilogue
+//
+// Same structure as the register-staged k_gemm of gemm.h -- block tile (64*TM) x (64*TN), 4 waves as 2x2, global -> register
+// prefetch of the next K tile under the current tile's MFMAs, one barrier pair per K tile -- with the operand conversion on the
+// way INTO LDS: each fp32 element is rounded ONCE to bf16 (v_cvt_pk_bf16_f32: round-to-nearest-even, a NaN stays a NaN) and the
+// LDS images hold bf16, half the bytes and half the reads of an fp32 image.  The K tile is 64 deep: four
+// v_mfma_f32_32x32x16_bf16 steps per accumulator.  A bf16 x bf16 product is exact in fp32 (8 + 8 significand bits), so the only
+// roundings are the operand casts and the fp32 accumulation, in an order fixed by the tile shape: no atomics, two launches give
+// the same bits.
+//
+// LDS images: both operands contraction-contiguous, [rows][B16_KP] bf16, B16_KP = 64 + 8 (144-byte pitch: an odd multiple of
+// 16 B, so the ds_read_b128 fragment reads of 16 consecutive rows hit disjoint banks).  Operand lane map of the 32x32x16 bf16
+// MFMA (cdna_hip_programming.md): lane l holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][col l & 31], j = 0..7;
+// the C/D layout is that of the fp32 32x32 MFMA, so the epilogue is gemm.h's.
+//
+// Staging pieces (what one thread loads and converts for one operand):
+//   contraction-contiguous (A_KC / B_KC): a row's 8 consecutive k -- two float4 loads, one 16-byte LDS write;
+//   contraction-strided: 4 consecutive k x 4 consecutive rows -- four float4 loads, four 8-byte LDS writes (the transpose
+//   happens in the write pass).
+// Rows past the matrix edge are clamped to valid addresses (their products land in outputs that are never stored), contraction
+// indices past the split's end are zero-filled at LDS-write time -- the K tails (479, 480 not a multiple of 64) included.
+#pragma once
+#include "gemm.h"
+
+#define B16_BK 64
+#define B16_KP (B16_BK + 8)
+
+typedef __bf16 b16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 b16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+
+// two fp32 -> packed bf16 pair (lo in bits 0-15): the plain cast, v_cvt_pk_bf16_f32 (round-to-nearest-even, NaN-preserving)
+__device__ __forceinline__ unsigned b16_pack(float lo, float hi) {
+    const b16x2 v = __builtin_convertvector((f32x2v){lo, hi}, b16x2);
+    return __builtin_bit_cast(unsigned, v);
+}
+
+// float4s one thread holds for one operand tile of ROWS rows x 64 contraction indices (both staging forms: ROWS / 16)
+template <int ROWS>
+struct B16Stage {
+    float4 v[ROWS / 16];
+};
+
+template <bool KC, int ROWS, bool VEC>
+__device__ __forceinline__ void b16_load(const float* __restrict__ P, int64_t ld, int64_t r0, int64_t rmax, int64_t k0,
+                                         int64_t kmax, B16Stage<ROWS>& st) {
+    // straight-line code (see tile_load in gemm.h: a branch around the loads would drain the prefetch)
+    if (KC) {
+#pragma unroll
+        for (int i = 0; i < ROWS / 32; ++i) {
+            const int f = threadIdx.x + i * 256;
+            const int64_t r = f / 8, c = (f % 8) * 8;
+            const int64_t rr = min(r0 + r, rmax - 1);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (VEC) {
+                    st.v[2 * i + h] = *reinterpret_cast<const float4*>(P + rr * ld + min(k0 + c + 4 * h, kmax - 4));
+                } else {
+                    float e[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) e[u] = P[rr * ld + min(k0 + c + 4 * h + u, kmax - 1)];
+                    st.v[2 * i + h] = make_float4(e[0], e[1], e[2], e[3]);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < ROWS / 64; ++i) {
+            const int f = threadIdx.x + i * 256;
+            const int64_t kg = f / (ROWS / 4), r = (f % (ROWS / 4)) * 4;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t kk = min(k0 + 4 * kg + u, kmax - 1);
+                if (VEC) {
+                    st.v[4 * i + u] = *reinterpret_cast<const float4*>(P + kk * ld + min(r0 + r, rmax - 4));
+                } else {
+                    float e[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) e[q] = P[kk * ld + min(r0 + r + q, rmax - 1)];
+                    st.v[4 * i + u] = make_float4(e[0], e[1], e[2], e[3]);
+                }
+            }
+        }
+    }
+}
+
+// convert + write one staged tile into its bf16 LDS image, zero-filling contraction indices >= kmax
+template <bool KC, int ROWS>
+__device__ __forceinline__ void b16_store(unsigned short* __restrict__ S, const B16Stage<ROWS>& st, int64_t k0, int64_t kmax) {
+    if (KC) {
+#pragma unroll
+        for (int i = 0; i < ROWS / 32; ++i) {
+            const int f = threadIdx.x + i * 256;
+            const int r = f / 8, c = (f % 8) * 8;
+            float e[8] = {st.v[2 * i].x, st.v[2 * i].y, st.v[2 * i].z, st.v[2 * i].w,
+                          st.v[2 * i + 1].x, st.v[2 * i + 1].y, st.v[2 * i + 1].z, st.v[2 * i + 1].w};
+#pragma unroll
+            for (int u = 0; u < 8; ++u) e[u] = (k0 + c + u < kmax) ? e[u] : 0.f;     // selects, not branches
+            uint4 w;
+            w.x = b16_pack(e[0], e[1]); w.y = b16_pack(e[2], e[3]); w.z = b16_pack(e[4], e[5]); w.w = b16_pack(e[6], e[7]);
+            *reinterpret_cast<uint4*>(S + r * B16_KP + c) = w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < ROWS / 64; ++i) {
+            const int f = threadIdx.x + i * 256;
+            const int kg = f / (ROWS / 4), r = (f % (ROWS / 4)) * 4;
+            float4 x[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bool ok = k0 + 4 * kg + u < kmax;
+                x[u] = st.v[4 * i + u];
+                x[u].x = ok ? x[u].x : 0.f; x[u].y = ok ? x[u].y : 0.f; x[u].z = ok ? x[u].z : 0.f; x[u].w = ok ? x[u].w : 0.f;
+            }
+            uint2 w0, w1, w2, w3;       // row r + q: its 4 consecutive contraction indices 4 kg .. 4 kg + 3
+            w0.x = b16_pack(x[0].x, x[1].x); w0.y = b16_pack(x[2].x, x[3].x);
+            w1.x = b16_pack(x[0].y, x[1].y); w1.y = b16_pack(x[2].y, x[3].y);
+            w2.x = b16_pack(x[0].z, x[1].z); w2.y = b16_pack(x[2].z, x[3].z);
+            w3.x = b16_pack(x[0].w, x[1].w); w3.y = b16_pack(x[2].w, x[3].w);
+            *reinterpret_cast<uint2*>(S + (r + 0) * B16_KP + 4 * kg) = w0;
+            *reinterpret_cast<uint2*>(S + (r + 1) * B16_KP + 4 * kg) = w1;
+            *reinterpret_cast<uint2*>(S + (r + 2) * B16_KP + 4 * kg) = w2;
+            *reinterpret_cast<uint2*>(S + (r + 3) * B16_KP + 4 * kg) = w3;
+        }
+    }
+}
+
+template <bool A_KC, bool B_KC, int TM, int TN, bool VA, bool VB>
+__device__ __forceinline__ void gemm_bf16_body(const GemmArgs& g, unsigned bx, unsigned by, unsigned bz,
+                                               unsigned short* __restrict__ As, unsigned short* __restrict__ Bs) {
+    constexpr int BM = 64 * TM, BN = 64 * TN;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int64_t m0 = (int64_t)by * BM;
+    const int64_t n0 = (int64_t)bx * BN;
+    const int64_t kbeg = (int64_t)bz * g.kchunk;
+    const int64_t kend = min(g.K, kbeg + g.kchunk);
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    B16Stage<BM> ra;
+    B16Stage<BN> rb;
+    // bias gradient (weight-gradient layout): the first column panel sums its fp32 A values (= dZ^T) over the contraction --
+    // from the registers, before they are rounded
+    const bool do_colsum = !A_KC && g.colsum != nullptr && bx == 0;
+    float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
+    b16_load<A_KC, BM, VA>(g.A, g.lda, m0, g.M, kbeg, kend, ra);
+    b16_load<B_KC, BN, VB>(g.B, g.ldb, n0, g.N, kbeg, kend, rb);
+    const int lr = lane & 31, lh = lane >> 5;
+    for (int64_t k0 = kbeg; k0 < kend; k0 += B16_BK) {
+        __syncthreads();
+        b16_store<A_KC, BM>(As, ra, k0, kend);
+        b16_store<B_KC, BN>(Bs, rb, k0, kend);
+        __syncthreads();
+        if (!A_KC && do_colsum) {       // wave-uniform; no loads inside
+#pragma unroll
+            for (int i = 0; i < BM / 64; ++i) {
+                const int kg = (threadIdx.x + i * 256) / (BM / 4);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const bool ok = k0 + 4 * kg + u < kend;
+                    const float4 x = ra.v[4 * i + u];
+                    csum.x += ok ? x.x : 0.f; csum.y += ok ? x.y : 0.f; csum.z += ok ? x.z : 0.f; csum.w += ok ? x.w : 0.f;
+                }
+            }
+        }
+        // unconditional: past the last tile the clamped addresses just re-read valid data
+        b16_load<A_KC, BM, VA>(g.A, g.lda, m0, g.M, k0 + B16_BK, kend, ra);
+        b16_load<B_KC, BN, VB>(g.B, g.ldb, n0, g.N, k0 + B16_BK, kend, rb);
+#pragma unroll
+        for (int s = 0; s < B16_BK / 16; ++s) {
+            b16x8 a[TM], b[TN];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const int r = wm * (32 * TM) + i * 32 + lr;
+                a[i] = __builtin_bit_cast(b16x8, *reinterpret_cast<const uint4*>(As + r * B16_KP + 16 * s + 8 * lh));
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                const int c = wn * (32 * TN) + j * 32 + lr;
+                b[j] = __builtin_bit_cast(b16x8, *reinterpret_cast<const uint4*>(Bs + c * B16_KP + 16 * s + 8 * lh));
+            }
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+    }
+    if (!A_KC && do_colsum) {
+        // the threads with equal (tid % (BM/4)) hold the same 4 rows for different contraction indices: combine them through
+        // LDS in a fixed order
+        __syncthreads();                        // every wave is done reading As
+        float* red = reinterpret_cast<float*>(As);
+        const int q = threadIdx.x / (BM / 4), r4 = (threadIdx.x % (BM / 4)) * 4;
+        *reinterpret_cast<float4*>(red + q * BM + r4) = csum;
+        __syncthreads();
+        if (threadIdx.x < BM && m0 + threadIdx.x < g.M) {
+            float s = 0.f;
+#pragma unroll
+            for (int qq = 0; qq < 1024 / BM; ++qq) s += red[qq * BM + threadIdx.x];
+            g.colsum[(int64_t)bz * g.M + m0 + threadIdx.x] = s;
+        }
+    }
+    float* C = g.C + (int64_t)bz * g.slab;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int64_t col = n0 + wn * (32 * TN) + j * 32 + lr;
+            if (col >= g.N) continue;
+            const float bv = g.bias ? g.bias[col] : 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t row = m0 + wm * (32 * TM) + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (row >= g.M) continue;
+                float v = acc[i][j][r] + bv;
+                if (g.act == 1) v = v > 0.f ? v : 0.f;
+                else if (g.act == 2) v = 1.0f / (1.0f + expf(-v));
+                if (g.mask_act) {               // activation backward of the layer below, fused into the dgrad
+                    const float x = g.mask[row * g.ldmask + col];
+                    v = g.mask_act == 1 ? (x > 0.f ? v : 0.f) : v * ((1.0f - x) * x);
+                }
+                C[row * g.ldc + col] = v;
+            }
+        }
+}
+
+template <bool A_KC, bool B_KC, int TM, int TN, bool VA, bool VB>
+__global__ void __launch_bounds__(256) k_gemm_bf16(GemmArgs g) {
+    __shared__ __attribute__((aligned(16))) unsigned short As[64 * TM * B16_KP];
+    __shared__ __attribute__((aligned(16))) unsigned short Bs[64 * TN * B16_KP];
+    const unsigned nwg = gridDim.x * gridDim.y * gridDim.z;
+    const unsigned wgid = xcd_remap((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, nwg);
+    gemm_bf16_body<A_KC, B_KC, TM, TN, VA, VB>(g, wgid % gridDim.x, (wgid / gridDim.x) % gridDim.y,
+                                               wgid / (gridDim.x * gridDim.y), As, Bs);
+}
+
+// grouped launch of 64x64-tile problems (the weight gradients of several layers), each with its own contraction split
+template <bool VA, bool VB>
+__global__ void __launch_bounds__(256) k_gemm_bf16_group(GemmGroup grp) {
+    __shared__ __attribute__((aligned(16))) unsigned short As[64 * B16_KP];
+    __shared__ __attribute__((aligned(16))) unsigned short Bs[64 * B16_KP];
+    const unsigned wgid = xcd_remap(blockIdx.x, gridDim.x);
+    int p = 0;
+#pragma unroll
+    for (int q = 1; q < GEMM_GROUP_MAX; ++q)
+        if (q < grp.n && wgid >= grp.first[q]) p = q;
+    const GemmArgs& g = grp.g[p];
+    const unsigned local = wgid - grp.first[p];
+    const unsigned gx = (unsigned)((g.N + 63) / 64), gy = (unsigned)((g.M + 63) / 64);
+    gemm_bf16_body<false, false, 1, 1, VA, VB>(g, local % gx, (local / gx) % gy, local / (gx * gy), As, Bs);
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+
+// The shape rule of the mode (layer terms: N outputs, K inputs): every GEMM of a layer with K >= 32 and N >= 32 -- never M, so
+// results do not depend on the batch size.  The 13-wide first layer and the 1-wide head stay on their fp32 routes.
+static inline bool bf16_layer_ok(int64_t N, int64_t K) { return N >= 32 && K >= 32; }
+
+// 16-byte loads legal for one operand: rows 16-byte aligned, and >= 4 elements along the loaded direction
+template <bool KC>
+static inline bool bf16_vec(const float* P, int64_t ld, int64_t rows, int64_t kdim) {
+    if (!aligned16(P) || ld % 4 != 0) return false;
+    return KC ? kdim % 4 == 0 : (rows % 4 == 0 && rows >= 4);
+}
+
+// tile of an un-split forward / dgrad: the largest of 128x128, 64x128, 64x64 whose grid keeps >= 4 workgroups per CU (the
+// loads, not the MFMAs, set the pace here: more workgroups in flight hide more of their latency).  (128x64 is never picked: its
+// grid is never larger than 64x128's.)
+static inline void bf16_pick_tile(int64_t M, int64_t N, int* tm, int* tn) {
+    const int cand[3][2] = {{2, 2}, {1, 2}, {1, 1}};
+    for (int c = 0; c < 3; ++c) {
+        if (cdiv(M, 64 * cand[c][0]) * cdiv(N, 64 * cand[c][1]) >= 2 * GEMM_MIN_BLOCKS || c == 2) {
+            *tm = cand[c][0]; *tn = cand[c][1];
+            return;
+        }
+    }
+}
+
+template <bool A_KC, bool B_KC, int TM, int TN>
+static void launch_gemm_bf16_v(const GemmArgs& g, dim3 grid, hipStream_t s) {
+    if (g.vecA && g.vecB) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, true, true>), grid, dim3(256), 0, s, g);
+    else if (g.vecA) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, true, false>), grid, dim3(256), 0, s, g);
+    else if (g.vecB) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, false, true>), grid, dim3(256), 0, s, g);
+    else CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, false, false>), grid, dim3(256), 0, s, g);
+}
+
+// An un-split forward (A_KC, B_KC) or dgrad (A_KC, !B_KC) in bf16.  g.vecA / g.vecB are recomputed here from the operands.
+// rec != nullptr: record the route, launch nothing.
+template <bool A_KC, bool B_KC>
+static int launch_gemm_bf16(GemmArgs g, hipStream_t s, const GemmRec* rec) {
+    static_assert(A_KC, "forward / dgrad layouts only; the weight gradient goes through launch_wgrad_bf16");
+    g.vecA = bf16_vec<true>(g.A, g.lda, g.M, g.K);
+    g.vecB = bf16_vec<B_KC>(g.B, g.ldb, g.N, g.K);
+    g.kchunk = g.K;
+    int tm, tn;
+    bf16_pick_tile(g.M, g.N, &tm, &tn);
+    if (rec) {
+        gemm_record(rec, CDLRM_ROUTE_BF16, tm, tn, 0, 0, 1, g.vecA, g.vecB, 0);
+        return 0;
+    }
+    dim3 grid((unsigned)cdiv(g.N, 64 * tn), (unsigned)cdiv(g.M, 64 * tm), 1);
+    if (tm == 2 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 2, 2>(g, grid, s);
+    else if (tm == 1 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 1, 2>(g, grid, s);
+    else launch_gemm_bf16_v<A_KC, B_KC, 1, 1>(g, grid, s);
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+// Contraction slabs of a bf16 weight gradient over the batch M: ~1024 workgroups of 64x64 over `tiles` output tiles, each slab
+// at least 4 K tiles deep, cut on K-tile boundaries.  Returns the slab length (kchunk); the slab count is cdiv(M, kchunk).
+static inline int64_t bf16_wgrad_kchunk(int64_t M, int64_t tiles, int64_t max_splits) {
+    int64_t s = cdiv(1024, tiles > 0 ? tiles : 1);
+    const int64_t smax = cdiv(M, 4 * B16_BK);
+    if (s > smax) s = smax;
+    if (s > max_splits) s = max_splits;
+    if (s < 1) s = 1;
+    return cdiv(cdiv(M, s), B16_BK) * B16_BK;
+}
+
+// weight-gradient problems (dW = dZ^T X layout: both operands contraction-strided) as grouped launches of <= GEMM_GROUP_MAX
+static inline int launch_wgrad_bf16(const GemmArgs* probs, int n, int va, int vb, hipStream_t s) {
+    for (int q0 = 0; q0 < n; q0 += GEMM_GROUP_MAX) {
+        GemmGroup grp;
+        memset(&grp, 0, sizeof(grp));
+        unsigned blocks = 0;
+        for (int q = q0; q < n && q < q0 + GEMM_GROUP_MAX; ++q) {
+            grp.first[grp.n] = blocks;
+            grp.g[grp.n] = probs[q];
+            blocks += (unsigned)(cdiv(probs[q].M, 64) * cdiv(probs[q].N, 64) * cdiv(probs[q].K, probs[q].kchunk));
+            grp.n++;
+        }
+        grp.first[grp.n] = blocks;
+        if (va && vb) CDLRM_LAUNCH_EV((k_gemm_bf16_group<true, true>), dim3(blocks), dim3(256), 0, s, grp);
+        else if (va) CDLRM_LAUNCH_EV((k_gemm_bf16_group<true, false>), dim3(blocks), dim3(256), 0, s, grp);
+        else if (vb) CDLRM_LAUNCH_EV((k_gemm_bf16_group<false, true>), dim3(blocks), dim3(256), 0, s, grp);
+        else CDLRM_LAUNCH_EV((k_gemm_bf16_group<false, false>), dim3(blocks), dim3(256), 0, s, grp);
+    }
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}

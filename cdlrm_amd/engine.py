@@ -703,7 +703,7 @@ class TrainEngine:
     def __init__(self, cache_group: Embedding_Table_Cache_Group, dlrm: DLRM_Net, host_tables: Embedding_Table_Group,
                  *, lr: float, lr_embeds: float, world_size: int = 1, rank: int = 0, table_agg_freq: int = 1,
                  table_agg_op: str = "mean", process_group=None, loss: str = "bce", loss_weights=(1.0, 1.0),
-                 defer_top_update: bool = False, force_collectives: bool = False):
+                 defer_top_update: bool = False, force_collectives: bool = False, matmul_precision: str = "fp32"):
         """loss / loss_weights: --loss-function / --loss-weights (main_no_ddp.py:364-372); the --loss-threshold clamp
         is read from `dlrm.loss_threshold`.
         defer_top_update: the top MLP's weight gradients, their all-reduce and their SGD update leave the critical
@@ -712,7 +712,11 @@ class TrainEngine:
         different schedule; readers of the top MLP's weights outside step()/evaluate() call finish() first.
         force_collectives: run the multi-rank control flow (gradient all-reduce, touched-row flags and merge, exchange
         stream) at world_size 1 as well: over a 1-rank RCCL communicator every collective of the N-rank step executes and is
-        the identity, so the result must equal the one-rank fast path bit for bit (tests/test_rccl_one_rank.py)."""
+        the identity, so the result must equal the one-rank fast path bit for bit (tests/test_rccl_one_rank.py).
+        matmul_precision: "fp32" (default: the reference's arithmetic) or "bf16" -- every MLP layer with K >= 32 and N >= 32
+        runs its forward, dgrad and weight-gradient GEMMs on the bf16 matrix cores (operands rounded once to bf16 inside the
+        kernels, fp32 accumulation, storage and epilogues: DESIGN.md section 4, "bf16 mode").  A plain attribute: set it
+        between steps and the next step / evaluate() follows it."""
         self.cg, self.dlrm, self.host = cache_group, dlrm, host_tables
         self.ctx = cache_group.ctx
         self.dev = cache_group.weight.device
@@ -731,6 +735,7 @@ class TrainEngine:
         thr = float(getattr(dlrm, "loss_threshold", 0.0) or 0.0)
         self.loss_threshold = thr if 0.0 < thr < 1.0 else 0.0
         self.defer_top = bool(defer_top_update)
+        self.matmul_precision = matmul_precision
         self.bot = dlrm._acts(dlrm.bot_l, dlrm.sigmoid_bot)
         self.top = dlrm._acts(dlrm.top_l, dlrm.sigmoid_top)
         self._flatten_params()
@@ -987,6 +992,39 @@ class TrainEngine:
             self._avg_ok = r
         return r
 
+    def _mm(self, l) -> dict:
+        """The extra keyword of layer l's linear_fwd / linear_bwd calls: {} in fp32 mode (the calls stay what they were),
+        {"bf16": True} in bf16 mode for a layer the shape rule admits (ops.bf16_eligible)."""
+        if self.matmul_precision == "fp32":
+            return {}
+        assert self.matmul_precision == "bf16", "matmul_precision: 'fp32' or 'bf16', not %r" % (self.matmul_precision,)
+        return {"bf16": True} if ops.bf16_eligible(l.out_features, self.W[l].shape[1]) else {}
+
+    def _wplans(self, buf):
+        """(whole-network plan, (bottom plan, top plan) or None) of the weight gradients at the current matmul precision: the
+        fp32 plans of _buffers, or bf16 plans with their own scratch, built on first use (the whole-network one only where
+        the step has no split plans: it is None otherwise)."""
+        if self.matmul_precision == "fp32":
+            return buf["wgrad"], buf["wgrad_split"]
+        self._mm(self.bot[0][0])            # validates the attribute
+        if "wgrad_bf16" not in buf:
+            xs, dzs, layers, B, dev = buf["wgrad_args"]
+            gw = [self.gW[l] for l in layers]
+            gb = [self.gb[l] for l in layers]
+            wk = lambda ls: ops.mlp_wgrad_work(B, [l.out_features for l in ls], [self.W[l].shape[1] for l in ls], dev,
+                                               precision="bf16")
+            whole, split = None, None
+            if buf["wgrad_split"] is None:
+                whole = ops.WgradPlan(xs, dzs, gw, gb, wk(layers), precision="bf16")
+            else:
+                nb = len(self.bot)
+                split = (ops.WgradPlan(xs[:nb], dzs[:nb], gw[:nb], gb[:nb], wk(layers[:nb]), precision="bf16"),
+                         ops.WgradPlan(xs[nb:], dzs[nb:], gw[nb:], gb[nb:], wk(layers[nb:]), precision="bf16"))
+                split[0].set_params([self.W[l] for l in layers[:nb]], [l.bias.data for l in layers[:nb]])
+                split[1].set_params([self.W[l] for l in layers[nb:]], [l.bias.data for l in layers[nb:]])
+            buf["wgrad_bf16"] = (whole, split)
+        return buf["wgrad_bf16"]
+
     def _buffers(self, B):
         if B in self._bufs:
             return self._bufs[B]
@@ -1030,6 +1068,7 @@ class TrainEngine:
         xs = [x0] + b["bot_y"] + [b["R"]] + b["top_y"][:-1]
         dzs = b["bot_dy"] + [b["dfeat"][:, 0, :]] + b["top_dy"]
         b["wgrad"] = ops.WgradPlan(xs, dzs, [self.gW[l] for l in layers], [self.gb[l] for l in layers], b["lin_work"])
+        b["wgrad_args"] = (xs, dzs, layers, B, dev)       # for the bf16 plans (_wplans)
         # long local batches: the top MLP's weight gradients run on their own stream beside the interaction backward
         # and the bottom MLP's backward -- (bottom plan, top plan), each with its own scratch
         b["wgrad_split"] = None
@@ -1312,7 +1351,7 @@ class TrainEngine:
         bot_acts = [X]
         for i, (l, act) in enumerate(self.bot):
             y = feat[:, 0, :] if i == len(self.bot) - 1 else buf["bot_y"][i]
-            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm)
+            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm, **self._mm(l))
             bot_acts.append(y)
             cur = y
         if side_gather:
@@ -1379,7 +1418,7 @@ class TrainEngine:
         for i, (l, act) in enumerate(self.top):
             y = buf["top_y"][i]
             if not (fused_head and i == len(self.top) - 1):
-                ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm)
+                ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm, **self._mm(l))
             top_acts.append(y)
             cur = y
         Z = cur
@@ -1389,7 +1428,7 @@ class TrainEngine:
         # the activation that produced its input (x_act) in its epilogue, the interaction backward does the same
         # for the bottom MLP's output, and the bias gradients are column sums taken inside the wgrad GEMMs.
         last_act = self.top[-1][1]
-        split = buf["wgrad_split"]
+        whole_plan, split = self._wplans(buf)
         wst = self.wst
         sgd_in_wgrad = self.defer_top and not self.multi      # one rank: the dense SGD rides in the weight gradients' reduction pass
 
@@ -1423,7 +1462,7 @@ class TrainEngine:
                 # a 6-8 us bubble on the training queue
                 ops.event_attach_next(ev["top_dz"], main)
             ops.linear_bwd(top_acts[i], self.W[l], top_acts[i + 1], dY, dX, None, None, act,
-                           buf["lin_work"], x_act=(self.top[i - 1][1] if i > 0 else 0), alone=self.wide_gemm)
+                           buf["lin_work"], x_act=(self.top[i - 1][1] if i > 0 else 0), alone=self.wide_gemm, **self._mm(l))
             dY = dX
         # (One event on the main queue for both side streams -- recorded behind the interaction backward -- instead of one in
         #  front of it for the weight gradients and one behind it for the embedding backward measured slower at c3, 0.698 vs
@@ -1497,7 +1536,7 @@ class TrainEngine:
             l, act = self.bot[i]
             dX = buf["bot_dy"][i - 1]
             ops.linear_bwd(bot_acts[i], self.W[l], bot_acts[i + 1], dY, dX, None, None, 0,
-                           buf["lin_work"], x_act=self.bot[i - 1][1])
+                           buf["lin_work"], x_act=self.bot[i - 1][1], **self._mm(l))
             dY = dX
         if split is not None:
             split[0].set_x(0, X)
@@ -1505,7 +1544,7 @@ class TrainEngine:
             if not self.defer_top:
                 rec(main.wait_event, ev["wgrad_done"])
         else:
-            plan = buf["wgrad"]
+            plan = whole_plan
             plan.set_x(0, X)
             ops.mlp_wgrad(plan)
         if self.multi:
@@ -1552,7 +1591,7 @@ class TrainEngine:
         cur = X
         for i, (l, act) in enumerate(self.bot):
             y = feat[:, 0, :] if i == len(self.bot) - 1 else buf["bot_y"][i]
-            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act)
+            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, **self._mm(l))
             cur = y
         if self._fused_gather(lS_o):
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
@@ -1563,7 +1602,7 @@ class TrainEngine:
         cur = R
         for i, (l, act) in enumerate(self.top):
             y = buf["top_y"][i]
-            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm)
+            ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, alone=self.wide_gemm, **self._mm(l))
             cur = y
         if self.loss_threshold > 0.0:       # DLRM_Net.forward returns the clamped prediction (model_no_ddp.py:311-314)
             cur = torch.clamp(cur, min=self.loss_threshold, max=1.0 - self.loss_threshold)
@@ -1610,6 +1649,7 @@ class TrainEngine:
                self._gslot is not None, self.loss_sync,
                (int(self._pending_resolve["cols"].shape[1]), self._pending_resolve["cols"].stride(0)) if self._mark_this else None,
                self.tape_lanes, self.tape_lanes_below, self.attach_events, self.fuse_gather, self.wide_gemm, self.fuse_once,
+               self.matmul_precision,
                None if self._cur_sorted is None else self._cur_sorted[3], self._next_sorted is not None,
                self._res[0].stride(0) if (self._res is not None and not hit) else 0,
                self._next_res[0].stride(0) if self._next_res is not None else 0)
@@ -1654,7 +1694,8 @@ class TrainEngine:
         for k, v in self._tape_ptrs(X, T, lS_i, next_idx, hit).items():
             cells[k].value = v
         bufs = self._buffers(B)
-        (bufs["wgrad_split"][0] if bufs["wgrad_split"] is not None else bufs["wgrad"]).set_x(0, X)
+        whole_plan, split = self._wplans(bufs)
+        (split[0] if split is not None else whole_plan).set_x(0, X)
         if tape["native"] is not None:
             rc = tape["native"].replay()
             if rc:

@@ -47,6 +47,9 @@ def ProcessArgs(argv=None):
     # ---- activation and loss ----
     parser.add_argument("--activation-function", type=str, default="relu")
     parser.add_argument("--loss-function", type=str, default="mse")  # or bce or wbce
+    # opt-in bf16 matrix-core mode of the MLP GEMMs (K >= 32 and N >= 32 layers; fp32 storage and accumulation): TrainEngine's
+    # matmul_precision.  fp32 is the reference's arithmetic.
+    parser.add_argument("--matmul-precision", type=str, default="fp32", choices=["fp32", "bf16"])
     parser.add_argument("--loss-weights", type=str, default="1.0-1.0")
     parser.add_argument("--loss-threshold", type=float, default=0.0)
     parser.add_argument("--round-targets", type=bool, default=False)
@@ -392,7 +395,8 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             dist.barrier()
     eng = TrainEngine(cache_group, dlrm, emb_tables, lr=args.learning_rate, lr_embeds=args.lr_embeds, world_size=world,
                       rank=rank, table_agg_freq=args.table_agg_freq, table_agg_op=args.table_agg_op,
-                      loss=args.loss_function, loss_weights=loss_ws, defer_top_update=True)
+                      loss=args.loss_function, loss_weights=loss_ws, defer_top_update=True,
+                      **({} if getattr(args, "matmul_precision", "fp32") == "fp32" else {"matmul_precision": args.matmul_precision}))
     for kv in filter(None, os.environ.get("CDLRM_ENGINE_ATTR", "").split(",")):
         # development (as bench.py --engine-attr): TrainEngine schedule knobs for same-box A/B runs of the CLI, 'name=value,...'
         k_, v_ = kv.split("=")

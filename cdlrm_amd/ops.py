@@ -555,16 +555,29 @@ ACT = {"none": 0, "relu": 1, "sigmoid": 2}
 
 
 GEMM_ALONE = 0x100        # include/cdlrm_hip.h: CDLRM_GEMM_ALONE
+GEMM_BF16 = 0x200         # include/cdlrm_hip.h: CDLRM_GEMM_BF16
+PRECISIONS = {"fp32": 0, "bf16": GEMM_BF16}
+
+
+def bf16_eligible(N: int, K: int) -> bool:
+    """The shape rule of the bf16 mode (CDLRM_GEMM_BF16): a layer with N outputs and K inputs runs its GEMMs in bf16 when
+    K >= 32 and N >= 32; other layers keep their fp32 routes."""
+    return int(N) >= 32 and int(K) >= 32
+
+
+def _flags(alone: bool = False, bf16: bool = False) -> int:
+    return (GEMM_ALONE if alone else 0) | (GEMM_BF16 if bf16 else 0)
 
 
 def linear_fwd(X: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], Y: torch.Tensor, act: int, stream=None,
-               alone: bool = False):
-    """alone: no other GEMM runs beside this launch (scheduling hint, CDLRM_GEMM_ALONE)."""
+               alone: bool = False, bf16: bool = False):
+    """alone: no other GEMM runs beside this launch (scheduling hint, CDLRM_GEMM_ALONE).  bf16: the opt-in bf16 matrix-core
+    mode (CDLRM_GEMM_BF16: X and W rounded once to bf16 inside the kernel, fp32 accumulation; eligible shapes only)."""
     M, K = X.shape
     N = W.shape[0]
     assert W.shape[1] == K and W.is_contiguous() and X.stride(1) == 1 and Y.stride(1) == 1
     check(_lib.lib().cdlrm_linear_fwd(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(b), Y.data_ptr(), Y.stride(0), M, N,
-                                      K, act | (GEMM_ALONE if alone else 0), stream_ptr(stream)))
+                                      K, act | _flags(alone, bf16), stream_ptr(stream)))
 
 
 def linear_bwd_work(M: int, N: int, K: int, device) -> torch.Tensor:
@@ -572,18 +585,21 @@ def linear_bwd_work(M: int, N: int, K: int, device) -> torch.Tensor:
     return torch.empty((nbytes + 255) // 256 * 256, dtype=torch.uint8, device=device)
 
 
-def linear_bwd(X, W, Y, dY, dX, dW, db, act: int, work: torch.Tensor, stream=None, x_act: int = 0, alone: bool = False):
+def linear_bwd(X, W, Y, dY, dX, dW, db, act: int, work: torch.Tensor, stream=None, x_act: int = 0, alone: bool = False,
+               bf16: bool = False):
     """act: this layer's activation, applied backward to dY in place (0: dY already is the pre-activation
-    gradient).  x_act: the activation that produced X; dX then leaves as the layer below's pre-activation gradient."""
+    gradient).  x_act: the activation that produced X; dX then leaves as the layer below's pre-activation gradient.
+    bf16: as linear_fwd (dgrad operands dZ and W, weight-gradient operands dZ and X)."""
     M, K = X.shape
     N = W.shape[0]
     check(_lib.lib().cdlrm_linear_bwd(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(Y), 0 if Y is None else Y.stride(0),
                                       dY.data_ptr(), dY.stride(0), ptr(dX), 0 if dX is None else dX.stride(0),
-                                      ptr(dW), ptr(db), M, N, K, act | (GEMM_ALONE if alone else 0), int(x_act), work.data_ptr(),
+                                      ptr(dW), ptr(db), M, N, K, act | _flags(alone, bf16), int(x_act), work.data_ptr(),
                                       stream_ptr(stream)))
 
 
-ROUTE_FAMILIES = {0: None, 1: "smallk_rows", 2: "smallk", 3: "direct", 4: "staged", 5: "gemm2", 6: "gemm3", 7: "gemm"}
+ROUTE_FAMILIES = {0: None, 1: "smallk_rows", 2: "smallk", 3: "direct", 4: "staged", 5: "gemm2", 6: "gemm3", 7: "gemm",
+                  8: "bf16"}
 
 
 def _route(r: _lib.GemmRoute) -> Optional[dict]:
@@ -594,7 +610,7 @@ def _route(r: _lib.GemmRoute) -> Optional[dict]:
                 fast=r.fast)
 
 
-def linear_fwd_route(X, W, b, Y, act: int, alone: bool = False, n_cu: int = 256) -> dict:
+def linear_fwd_route(X, W, b, Y, act: int, alone: bool = False, n_cu: int = 256, bf16: bool = False) -> dict:
     """The kernel linear_fwd(X, W, b, Y, act, alone=alone) launches, from the same decision code, without launching it:
     family (ROUTE_FAMILIES), tile (tm, tn), direct mode / aligned, splits, vec_a / vec_b, fast (the full-tile epilogue).
     X, W, b, Y: tensors or anything with .shape, .stride(0) and .data_ptr() -- addresses are looked at for their alignment
@@ -603,11 +619,12 @@ def linear_fwd_route(X, W, b, Y, act: int, alone: bool = False, n_cu: int = 256)
     N = W.shape[0]
     out = _lib.GemmRoute()
     check(_lib.raw().cdlrm_linear_fwd_route(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(b), Y.data_ptr(), Y.stride(0), M, N, K,
-                                            act | (GEMM_ALONE if alone else 0), None, int(n_cu), C.byref(out)))
+                                            act | _flags(alone, bf16), None, int(n_cu), C.byref(out)))
     return _route(out)
 
 
-def linear_bwd_route(X, W, Y, dY, dX, dW, db, act: int, x_act: int = 0, alone: bool = False, n_cu: int = 256):
+def linear_bwd_route(X, W, Y, dY, dX, dW, db, act: int, x_act: int = 0, alone: bool = False, n_cu: int = 256,
+                     bf16: bool = False):
     """(dgrad, wgrad): the kernels linear_bwd with the same arguments launches for dX and for dW / db (None where it launches
     none), as linear_fwd_route."""
     M, K = X.shape
@@ -615,25 +632,35 @@ def linear_bwd_route(X, W, Y, dY, dX, dW, db, act: int, x_act: int = 0, alone: b
     out = (_lib.GemmRoute * 2)()
     check(_lib.raw().cdlrm_linear_bwd_route(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(Y), 0 if Y is None else Y.stride(0),
                                             dY.data_ptr(), dY.stride(0), ptr(dX), 0 if dX is None else dX.stride(0), ptr(dW),
-                                            ptr(db), M, N, K, act | (GEMM_ALONE if alone else 0), int(x_act), 256, None,
+                                            ptr(db), M, N, K, act | _flags(alone, bf16), int(x_act), 256, None,
                                             int(n_cu), out))
     return _route(out[0]), _route(out[1])
 
 
-def mlp_wgrad_work(M: int, Ns: Sequence[int], Ks: Sequence[int], device) -> torch.Tensor:
-    """Scratch for mlp_wgrad over layers with output widths Ns and input widths Ks at batch M."""
+def _wgrad_work_bytes(M: int, Ns, Ks, precision: str) -> int:
     n = len(Ns)
     NA = C.c_int32 * n
-    nbytes = int(_lib.lib().cdlrm_mlp_wgrad_work_bytes(n, int(M), NA(*[int(x) for x in Ns]), NA(*[int(x) for x in Ks])))
+    N, K = NA(*[int(x) for x in Ns]), NA(*[int(x) for x in Ks])
+    if precision == "fp32":
+        return int(_lib.lib().cdlrm_mlp_wgrad_work_bytes(n, int(M), N, K))
+    return int(_lib.lib().cdlrm_mlp_wgrad_work_bytes_ex(n, int(M), N, K, PRECISIONS[precision]))
+
+
+def mlp_wgrad_work(M: int, Ns: Sequence[int], Ks: Sequence[int], device, precision: str = "fp32") -> torch.Tensor:
+    """Scratch for mlp_wgrad over layers with output widths Ns and input widths Ks at batch M (precision: that of the plan)."""
+    nbytes = _wgrad_work_bytes(M, Ns, Ks, precision)
     return torch.empty((nbytes + 255) // 256 * 256, dtype=torch.uint8, device=device)
 
 
 class WgradPlan:
     """Host-side argument block of cdlrm_mlp_wgrad for a fixed set of layers and buffers (built once per batch shape;
-    `set_x` re-points one layer's input, e.g. the dense features of the current batch)."""
+    `set_x` re-points one layer's input, e.g. the dense features of the current batch).  precision: "fp32", or "bf16" for
+    the opt-in bf16 mode of the eligible layers (K >= 32 and N >= 32; work from mlp_wgrad_work(..., precision="bf16"))."""
 
-    def __init__(self, Xs, dZs, dWs, dbs, work: torch.Tensor):
+    def __init__(self, Xs, dZs, dWs, dbs, work: torch.Tensor, precision: str = "fp32"):
         import ctypes as C
+        assert precision in PRECISIONS, precision
+        self.precision = precision
         n = len(Xs)
         assert len(dZs) == n and len(dWs) == n and len(dbs) == n
         self.n = n
@@ -651,7 +678,7 @@ class WgradPlan:
         for x, d, w in zip(Xs, dZs, dWs):
             assert x.shape[0] == self.M and d.shape[0] == self.M and x.stride(1) == 1 and d.stride(1) == 1
             assert w.is_contiguous() and d.shape[1] == w.shape[0] and x.shape[1] <= w.shape[1] <= x.stride(0)
-        need = int(_lib.lib().cdlrm_mlp_wgrad_work_bytes(n, self.M, self.N, self.K))
+        need = _wgrad_work_bytes(self.M, list(self.N), list(self.K), precision)
         assert work.numel() * work.element_size() >= need and work.data_ptr() % 256 == 0, "work too small: ops.mlp_wgrad_work"
         self.work = work
 
@@ -677,6 +704,16 @@ class WgradPlan:
 def mlp_wgrad(plan: WgradPlan, stream=None, lr: Optional[float] = None):
     """dW[i] = dZ[i]^T X[i], db[i] = column sums of dZ[i] for every layer of the plan (one grouped launch at small M).
     lr given (and plan.set_params called): W[i] -= lr * dW[i], b[i] -= lr * db[i] in the same launches."""
+    if plan.precision != "fp32":
+        flags = PRECISIONS[plan.precision]
+        if lr is None:
+            check(_lib.lib().cdlrm_mlp_wgrad_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.M, plan.N,
+                                                plan.K, flags, plan.work.data_ptr(), stream_ptr(stream)))
+        else:
+            check(_lib.lib().cdlrm_mlp_wgrad_sgd_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
+                                                    plan.P_b, float(lr), plan.M, plan.N, plan.K, flags, plan.work.data_ptr(),
+                                                    stream_ptr(stream)))
+        return
     if lr is None:
         check(_lib.lib().cdlrm_mlp_wgrad(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.M, plan.N,
                                          plan.K, plan.work.data_ptr(), stream_ptr(stream)))
@@ -684,6 +721,16 @@ def mlp_wgrad(plan: WgradPlan, stream=None, lr: Optional[float] = None):
         check(_lib.lib().cdlrm_mlp_wgrad_sgd(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
                                              plan.P_b, float(lr), plan.M, plan.N, plan.K, plan.work.data_ptr(),
                                              stream_ptr(stream)))
+
+
+def mlp_wgrad_route(plan: WgradPlan, n_cu: int = 256, precision: Optional[str] = None) -> list:
+    """One route per layer of the plan (as linear_fwd_route's dict): the weight-gradient GEMM mlp_wgrad(plan) launches for it,
+    from the same decision code, without launching.  precision: the plan's unless given."""
+    out = (_lib.GemmRoute * max(plan.n, 1))()
+    flags = PRECISIONS[precision or plan.precision]
+    check(_lib.raw().cdlrm_mlp_wgrad_route(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.M, plan.N,
+                                           plan.K, flags, int(n_cu), out))
+    return [_route(out[i]) for i in range(plan.n)]
 
 
 def bce_fwd_bwd(Z: torch.Tensor, target: torch.Tensor, loss_buf: torch.Tensor, dZ: Optional[torch.Tensor], stream=None,

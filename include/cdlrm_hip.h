@@ -457,6 +457,12 @@ int cdlrm_gather_interact_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, int64_t 
  * the chip then take the one-workgroup-per-CU kernel (csrc/gemm_wide.h), which must not share its CU.  Same fp32 fma arithmetic;
  * the contraction order inside a 16-deep group differs from the default kernel's, so results may differ in the last bits. */
 #define CDLRM_GEMM_ALONE 0x100
+/* CDLRM_GEMM_BF16, or-ed into `act` of cdlrm_linear_fwd / cdlrm_linear_bwd (and their route queries), or passed as `flags` of the
+ * cdlrm_mlp_wgrad*_ex calls: the opt-in bf16 matrix-core mode.  A layer with K >= 32 and N >= 32 (its shape only, never M) runs
+ * all of its GEMMs on v_mfma_f32_32x32x16_bf16: each operand element is rounded once to bf16 (round-to-nearest-even, NaN kept)
+ * on its way into LDS, products are exact, accumulation is fp32 in a fixed order.  Storage, bias, activations, act' masks, bias
+ * gradients, slab reductions and SGD steps stay fp32.  Other layers take their fp32 route as without the flag. */
+#define CDLRM_GEMM_BF16 0x200
 int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y,
                      int64_t ld_y, int64_t M, int32_t N, int32_t K, int32_t act, void* stream);
 /* Backward of the same layer.  act != 0: dY is the gradient w.r.t. the layer's OUTPUT and is overwritten
@@ -483,6 +489,7 @@ int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, const float* 
 #define CDLRM_ROUTE_GEMM2 5         /* k_gemm2: LDS-DMA, (64 tm) x (64 tn) tiles */
 #define CDLRM_ROUTE_GEMM3 6         /* k_gemm3: the wide kernel, (32 tm) x (32 tn) tiles, one workgroup per CU */
 #define CDLRM_ROUTE_GEMM 7          /* k_gemm: register-staged, (64 tm) x (64 tn) tiles */
+#define CDLRM_ROUTE_BF16 8          /* k_gemm_bf16 / k_gemm_bf16_group (CDLRM_GEMM_BF16): bf16 MFMA, (64 tm) x (64 tn) tiles */
 typedef struct cdlrm_gemm_route {
     int32_t family;         /* CDLRM_ROUTE_* */
     int32_t tm, tn;         /* tile: k_gemm / k_gemm2 in units of 64 rows / columns, k_gemm3 IM / JN in units of 32 */
@@ -523,6 +530,24 @@ int cdlrm_mlp_wgrad(int32_t n_layers, const float* const* X, const int64_t* ld_x
 int cdlrm_mlp_wgrad_sgd(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
                         const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W, float* const* b,
                         float lr, int64_t M, const int32_t* N, const int32_t* K, void* work, void* stream);
+
+/* The same three calls with a flags word (0 or CDLRM_GEMM_BF16).  flags = 0: exactly cdlrm_mlp_wgrad_work_bytes /
+ * cdlrm_mlp_wgrad / cdlrm_mlp_wgrad_sgd.  CDLRM_GEMM_BF16: the layers with K[i] >= 32 and N[i] >= 32 run in bf16 (one grouped
+ * launch, split-M slabs, the same fixed-order slab reduction with the SGD step inside), the others on their fp32 plan; work is
+ * sized by cdlrm_mlp_wgrad_work_bytes_ex with the same flags. */
+uint64_t cdlrm_mlp_wgrad_work_bytes_ex(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K, int32_t flags);
+int cdlrm_mlp_wgrad_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                       const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
+                       const int32_t* K, int32_t flags, void* work, void* stream);
+int cdlrm_mlp_wgrad_sgd_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                           const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W, float* const* b,
+                           float lr, int64_t M, const int32_t* N, const int32_t* K, int32_t flags, void* work, void* stream);
+/* The plan of cdlrm_mlp_wgrad_ex with the same arguments, without the launches (no pointer is read, no device touched): out[i] is
+ * layer i's weight-gradient GEMM -- family, tile where the family has one, splits (slab count), vec_a / vec_b -- from the same
+ * decision code.  n_cu as for cdlrm_linear_fwd_route. */
+int cdlrm_mlp_wgrad_route(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                          const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
+                          const int32_t* K, int32_t flags, int32_t n_cu, cdlrm_gemm_route* out);
 
 /* BCELoss(mean) forward + backward on the sigmoid output (torch clamps log at -100):
  * loss_out device fp32 [65]: [0] = loss, [1..64] = partial sums (fixed-order, reproducible);
