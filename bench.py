@@ -15,11 +15,15 @@ Between the W warm-up steps and the timed region the GPU is kept busy for --prew
 training state; reported as config.gpu_prewarm_ms): the part needs that long under load to reach its clocks after set-up, and a
 short timed region would otherwise report the ramp.  --prewarm-ms 0 switches it off.
 
-Behind the K timed steps (whose figure `value` / `ms_per_step` stay) a one-GPU run trains on through ONE WHOLE look-ahead window and
-reports it as config.whole_window: L steps timed on their own with exactly one background plan launched and one window commit
-inside -- the look-ahead side of the path inside a measurement, which 20 steps of a 3000-step window cannot hold.  Then the
-stand-alone legs (roofline.gather_operator, roofline.alone) and, at N = 1, cpu_baseline: the oracle on the host cores in the
-workload's cache regime.  `--gpus N --plan-only` prints what every rank will ask the node for and exits without a HIP call.
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs, the JSON line.
+`--full` adds the legs that are measured on their own behind the timed region.  Behind the K timed steps (whose figure `value` /
+`ms_per_step` stay) a one-GPU run trains on through ONE WHOLE look-ahead window and reports it as config.whole_window: L steps
+timed on their own with exactly one background plan launched and one window commit inside -- the look-ahead side of the path
+inside a measurement, which 20 steps of a 3000-step window cannot hold.  Then the stand-alone legs (roofline.gather_operator,
+roofline.alone) and, at N = 1, cpu_baseline: the oracle on the host cores in the workload's cache regime.  Without --full these
+fields are null (config.whole_window says why; cpu_baseline is absent); a timed region that itself crossed a window boundary and
+launched a plan is reported as the whole window either way.  `--gpus N --plan-only` prints what every rank will ask the node for
+and exits without a HIP call.
 
 `--dump-outputs DIR` writes what the last timed step computed (loss, predictions, MLP parameters, a fixed sample of the embedding
 rows; dump_outputs) as DIR/<name>.npy: the inputs depend on the arguments only, so two builds can be compared output for output.
@@ -84,7 +88,11 @@ def parse():
     ap.add_argument("--max-ind-range", type=int, default=-1, help="cap rows per table (main_no_ddp.py:64)")
     ap.add_argument("--lookahead", type=int, default=-1, help="override the config's lookahead window")
     ap.add_argument("--batch", type=int, default=-1, help="override the config's global batch (development)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed region also run the legs measured on their own: the whole-window leg, the stand-alone "
+                         "gather timings (roofline.gather_operator, roofline.alone) and, at one GPU, cpu_baseline.  A plain run "
+                         "does only what value / ms_per_step need")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--gather-sample", type=int, default=8, help="time the gather kernel every k-th step")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="keep the GPU busy this long between the warm-up steps and the timed region (0: off)")
@@ -92,17 +100,18 @@ def parse():
     ap.add_argument("--debug", default="", help="development switches inside the library, 'key=value,key=value' "
                                                 "(cdlrm_debug_set; csrc/common.h): kernel-variant A/Bs, all zero in production")
     ap.add_argument("--whole-window", default="auto", choices=["auto", "on", "off"],
-                    help="one GPU: after the K timed steps keep training through one whole look-ahead window (L steps: one window "
-                         "commit + one WHOLE background plan) and report it as config.whole_window; value / ms_per_step stay the "
-                         "K-step figure.  auto: when the timed region itself held no commit + plan and the leg takes < 20 s")
+                    help="one GPU, with --full: after the K timed steps keep training through one whole look-ahead window (L steps: "
+                         "one window commit + one WHOLE background plan) and report it as config.whole_window; value / ms_per_step "
+                         "stay the K-step figure.  auto: when the timed region itself held no commit + plan and the leg takes < 20 s")
     ap.add_argument("--plan-only", action="store_true",
                     help="print what every rank of this command would ask the node for (host / pinned / HBM bytes, threads, "
                          "streams, hardware queues, port) and exit -- no HIP call, no process group")
     ap.add_argument("--engine-attr", default="", help="development: TrainEngine schedule knobs for A/B lines, 'name=value,name=value' "
                                                       "(python literals); reported as config.engine_attr")
     ap.add_argument("--no-standalone-legs", action="store_true",
-                    help="skip the stand-alone timings behind the timed region (roofline.gather_operator, roofline.alone): the "
-                         "rocprofv3 passes of tools/profile_round.sh, whose kernel statistics should hold the step's launches only")
+                    help="with --full: skip the stand-alone timings behind the timed region (roofline.gather_operator, "
+                         "roofline.alone): the rocprofv3 passes of tools/profile_round.sh, whose kernel statistics should hold the "
+                         "step's launches only")
     ap.add_argument("--no-fuse-gather", action="store_true",
                     help="gather + interaction as two launches (TrainEngine.fuse_gather = False): the schedule up to round 4's "
                          "first session, kept for A/B lines")
@@ -542,7 +551,7 @@ def main():
     t_start = a.warmup + cold_steps
     total_steps = t_start + a.steps
     plan_at = max(1, min(L // 2, 64))      # iteration inside a window at which the next window's plan is launched
-    # The whole-window leg (one GPU): the driver's K = 20 timed steps of a 3000-step window hold neither a window commit nor a
+    # The whole-window leg (one GPU, --full): the driver's K = 20 timed steps of a 3000-step window hold neither a window commit nor a
     # background plan, so after them the run keeps training through ONE WHOLE WINDOW -- L more steps, timed on their own, holding
     # exactly one plan launch (at iteration plan_at of the window, the plan running beside the steps that follow) and the commit of
     # that plan at the window boundary -- and reports it as config.whole_window.  value / ms_per_step stay the K-step figure.
@@ -553,6 +562,8 @@ def main():
     ww_why = None
     if world > 1:
         ww_why = "one GPU only"
+    elif not a.full:
+        ww_why = "a plain run (--full runs the leg)"
     elif a.whole_window == "off":
         ww_why = "--whole-window off"
     elif L < 2 * WW_LEAD or total_steps + WW_LEAD > plan_at:
@@ -799,15 +810,15 @@ def main():
     # The cached EmbeddingBag gather as an OPERATOR of its own (cdlrm_embbag_fwd: the product path of multi-hot bags, "cat" and
     # shapes outside the fused kernels; up to round 4's first session also this step's) -- when the step runs the fused kernel,
     # the operator is timed here, stand-alone, after the timed region: 30 launches on the last batch's slot ids into the
-    # engine's own feature block, each with its launch-attached events.
+    # engine's own feature block, each with its launch-attached events.  (--full: a plain run stops at the timed region)
     op_us, alone_us = [], []
     gpu_regime = refills.get("regime")
-    if rank == 0:
+    if rank == 0 and a.full:
         idx_l = batch_indices(last_j)
         slots_l, _, mc_l = _ops.embbag_probe(cg.ctx, idx_l, aux_phase=eng._phase)
         if gpu_regime is not None:      # lookups of the last batch served from the cache (the others read aux rows)
             gpu_regime["hit_rate_last_batch"] = 1.0 - float(mc_l.sum().item()) / float(idx_l.numel())
-    if rank == 0 and fused and a.gather_sample > 0 and not a.no_standalone_legs:
+    if rank == 0 and a.full and fused and a.gather_sample > 0 and not a.no_standalone_legs:
         feat_l = eng._buffers(lbs)["feat"]
         pairs = [(_ops.TimingEvent(), _ops.TimingEvent()) for _ in range(35)]
         # between two launches 1 GB of scratch is copied: the rows of the launch before (113 MB at c3) would otherwise wait in
@@ -1023,7 +1034,7 @@ def main():
                                        "mean_without_those": float(np.mean(quiet)) if quiet else None},
                          "launches_timed": len(ev_pairs), "sampled_every": sample_every},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, ln_emb, a.seed, gpu_regime)
         print(json.dumps(out))
     barrier()

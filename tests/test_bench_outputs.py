@@ -108,6 +108,14 @@ def test_bench_refuses_a_run_without_timed_steps(args):
     assert p.returncode == 2 and "--steps must be at least 1" in p.stderr, p.stderr[-800:]
 
 
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.parse().full is True
+
+
 # ------------------------------------------------------------------------------------------------ GPU
 
 @pytest.mark.gpu
@@ -133,3 +141,32 @@ def test_two_runs_dump_the_same_outputs(tmp_path):
     assert r["config"]["dump_outputs"] == {k: list(v.shape) for k, v in a.items()}
     assert a["prediction"].shape == (128,) and a["emb_rows"].shape == (8 * 128, 16)
     assert 0 < a["emb_lookups"][:, 2].sum(), "the last step's rows come (partly) from the cache"
+
+
+@pytest.mark.gpu
+def test_full_adds_its_legs_behind_the_same_timed_steps(tmp_path):
+    """A plain run stops at the JSON line; --full trains on through a whole window, times the stand-alone gather legs and the CPU
+    baseline behind the timed region.  The timed steps are the same: same loss, same dumped outputs to the bit."""
+    recs = {}
+    for run, extra in (("plain", []), ("full", ["--full"])):
+        # (2 + 1 steps end in front of the window's plan launch at iteration 16 of c1's 32: the whole-window leg runs)
+        p = subprocess.run([sys.executable, "bench.py", "--config", "c1", "--steps", "2", "--warmup", "1", "--prewarm-ms", "0",
+                            "--dump-outputs", str(tmp_path / run)] + extra, env=_env(), capture_output=True, text=True,
+                           timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
+        assert len(lines) == 1, p.stdout[-3000:]
+        recs[run] = json.loads(lines[0])
+    plain, full = recs["plain"], recs["full"]
+    for r in (plain, full):
+        assert r["steps"] == 2 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["unit"] == "samples/s"
+        assert r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert plain["config"]["final_loss"] == full["config"]["final_loss"]
+    a, b = _load(tmp_path / "plain"), _load(tmp_path / "full")
+    assert set(a) == NAMES and all(np.array_equal(a[k], b[k]) for k in NAMES)
+    assert "cpu_baseline" not in plain and "skipped" in plain["config"]["whole_window"]
+    assert plain["roofline"]["alone"] is None and plain["roofline"]["gather_operator"] is None
+    assert full["cpu_baseline"]["value"] > 0
+    assert full["config"]["whole_window"]["steps"] == 32 and full["config"]["whole_window"]["window_commits"] == 1
+    if full["roofline"]["fused_gather"]:
+        assert full["roofline"]["alone"] is not None and full["roofline"]["gather_operator"] is not None

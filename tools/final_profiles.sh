@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/final
 mkdir -p $OUT
 cd $ROOT
 line() { tail -n 1 "$1" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('  ms/step %.4f  value %.4g  gather %.2f us  frac %.3f  loss %.6f' % (d['ms_per_step'], d['value'], r['avg_launch_us'] or 0, r['frac'] or 0, d['config']['final_loss']))"; }
-run() { name=$1; shift; echo "== $name: bench.py $*"; python3 bench.py "$@" > $OUT/${TAG}_bench_$name.json 2> $OUT/${TAG}_bench_$name.err; line $OUT/${TAG}_bench_$name.json; }
+run() { name=$1; shift; echo "== $name: bench.py $*"; python3 bench.py --full "$@" > $OUT/${TAG}_bench_$name.json 2> $OUT/${TAG}_bench_$name.err; line $OUT/${TAG}_bench_$name.json; }
 # PART=lines: the bench lines only; PART=prof: the rocprofv3 passes only (a gpurun call is at most 20 minutes: the two halves
 # of a round's profiles go in two calls, on two boxes -- each half is self-consistent); default: both
 if [ "${PART:-all}" != prof ]; then
