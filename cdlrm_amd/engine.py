@@ -81,6 +81,115 @@ def pad_window(lists, device=None):
     return out.to(device) if device is not None else out
 
 
+def rank_bag_slice(off: torch.Tensor, lens: torch.Tensor, lbs: int, rank: int, multiple: int = 256):
+    """The rank slice of one batch of ragged multi-hot bags.  off: int64 [T, B] global offsets, lens:
+    int64 [T] lengths of the batch's table lists, both on the host; lbs: the local batch size ceil(mini_batch_size / world)
+    -- of the run, not of this batch: a short last batch (--data-size not a multiple of the batch) is cut where the
+    reference and the one-lookup path cut it, X[r * lbs:(r + 1) * lbs] (main_no_ddp.py:344, 388-391).  Rank r trains
+    samples [s0, s1) = [min(B, r * lbs), min(B, (r + 1) * lbs)); of table k it takes the lookups of exactly those bags,
+    [a_k, e_k) = [off[k, s0], off[k, s1]) (e_k = lens[k] when s1 = B).  With one lookup per bag this is the reference's
+    lS_i[:, s0:s1].  Returns (s0, s1, a [T], e [T], n); n = the squared width of the rank's lists, max(e - a) rounded up to
+    `multiple` as square_bags() rounds.  O(T) tensor ops, no loop over the tables.  Raises ValueError when the rank has no
+    sample or a table slice holds no lookup: padding such a table would need an index the rank never looked up, which would
+    add an untouched row to its merge set."""
+    T, B = off.shape
+    s0, s1 = min(B, rank * lbs), min(B, (rank + 1) * lbs)
+    if s0 >= s1:
+        raise ValueError("multi-hot bags: rank %d has no sample of a batch of %d (local batch %d): every rank needs >= 1 "
+                         "sample per batch" % (rank, B, lbs))
+    a = off[:, s0]
+    e = off[:, s1] if s1 < B else lens
+    m = e - a
+    if int(m.min()) < 1:
+        k = int(torch.argmin(m))
+        raise ValueError("multi-hot bags: rank %d's slice [%d, %d) of table %d holds no lookup (every table needs >= 1 "
+                         "lookup per rank slice)" % (rank, s0, s1, k))
+    n = (int(m.max()) + multiple - 1) // multiple * multiple
+    return s0, s1, a, e, n
+
+
+class BagWindow:
+    """One look-ahead window of ragged multi-hot batches in HBM (BagWindows.load): the plan's rectangle and every step's
+    per-rank squared lists, each one launch on the current stream."""
+
+    def __init__(self, owner, buf, bpos, dev_off, host_off, lens, n_win):
+        self._o, self.buf, self.bpos = owner, buf, bpos
+        self.dev_off, self.host_off, self.lens = dev_off, host_off, lens
+        self.L, self.n_win = len(dev_off), n_win
+
+    def window_indices(self) -> torch.Tensor:
+        """int64 [T, n_win]: pad_window() of the window's global lists."""
+        return ops.bags_window(self.buf, self.bpos, self.L, self.n_win)
+
+    def rank_batch(self, b: int):
+        """(off int64 [T, nb + 1], idx int64 [T, n], samples) of batch b for this rank: square_bags() of the rank's rebased
+        lookups, and slice(s0, s1) -- the rows of the batch's X and T they belong to."""
+        o = self._o
+        s0, s1, _, _, n = rank_bag_slice(self.host_off[b], self.lens[b], o.lbs, o.rank, o.multiple)
+        off, idx = ops.bags_rank_slice(self.buf, self.bpos, self.L, b, self.dev_off[b], s0, s1, n)
+        return off, idx, slice(s0, s1)
+
+
+class BagWindows:
+    """Ragged multi-hot batches on the device for the rank slices at world_size > 1.  load(win) packs a window's global
+    lists -- per table the window's batches concatenated, then the list positions, then every batch's offsets -- into
+    pinned staging and moves them with ONE host-to-device copy into the next buffer of a ring of two: with --device-rng
+    the next window is loaded and planned while the current one trains.  Every launch (copy, slices) is on the current
+    stream, so a buffer is refilled two windows later behind every slice cut from it.  local_batch_size: ceil(mini_batch_size
+    / world_size), the run's rank slice width (rank_bag_slice).  At world_size 1 the host path (square_bags / pad_window)
+    stays."""
+
+    RING = 2
+
+    def __init__(self, num_tables: int, device, local_batch_size: int, world_size: int = 1, rank: int = 0, multiple: int = 256):
+        self.T, self.dev = int(num_tables), torch.device(device)
+        self.lbs, self.world, self.rank, self.multiple = int(local_batch_size), int(world_size), int(rank), int(multiple)
+        self._stage = [None] * self.RING       # pinned int64 staging
+        self._buf = [None] * self.RING         # int64 device buffer
+        self._copied = [None] * self.RING      # event behind the copy out of the staging buffer
+        self._next = 0
+
+    def load(self, win) -> BagWindow:
+        """win: the window's batches (X, lS_o, lS_i, T) as the loader hands them out -- lS_o [T, B] (or T lists of B), lS_i T
+        ragged lists.  Checks every rank's slices (the same decision on every rank), then stages and copies."""
+        T, L = self.T, len(win)
+        host_off = [torch.as_tensor(b[1]).to(torch.int64).reshape(T, -1) if isinstance(b[1], torch.Tensor) else
+                    torch.stack([torch.as_tensor(o).reshape(-1).to(torch.int64) for o in b[1]]) for b in win]
+        lists = [[torch.as_tensor(b[2][k]).reshape(-1) for b in win] for k in range(T)]     # table-major
+        lens = torch.tensor([[int(lists[k][j].numel()) for k in range(T)] for j in range(L)], dtype=torch.int64)  # [L, T]
+        if int(lens.min()) < 1:
+            raise ValueError("multi-hot bags: every table needs >= 1 lookup per batch")
+        for j in range(L):
+            for r in range(self.world):
+                rank_bag_slice(host_off[j], lens[j], self.lbs, r, self.multiple)
+        tab_len = lens.sum(0)                                           # [T]
+        tab_start = torch.cumsum(tab_len, 0) - tab_len
+        bpos = torch.cat([tab_start.view(1, T), tab_start.view(1, T) + torch.cumsum(lens, 0)])   # [L + 1, T]
+        total = int(tab_len.sum())
+        n_pos, n_off = (L + 1) * T, sum(int(o.numel()) for o in host_off)
+        N = total + n_pos + n_off
+        i = self._next
+        self._next = (i + 1) % self.RING
+        if self._copied[i] is not None:
+            self._copied[i].synchronize()           # the previous copy out of this staging buffer has been read
+        if self._stage[i] is None or self._stage[i].numel() < N:
+            cap = 1 << max(16, (N - 1).bit_length())
+            self._stage[i] = S.pinned(torch.empty(cap, dtype=torch.int64), self.dev)
+            self._buf[i] = torch.empty(cap, dtype=torch.int64, device=self.dev)
+        st, buf = self._stage[i], self._buf[i]
+        torch.cat([x.to(torch.int64) for row in lists for x in row] + [bpos.reshape(-1)] + [o.reshape(-1) for o in host_off],
+                  out=st[:N])
+        buf[:N].copy_(st[:N], non_blocking=True)
+        ev = S.new_event(self.dev)
+        ev.record(S.current_stream(self.dev))
+        self._copied[i] = ev
+        dev_off, p = [], total + n_pos
+        for o in host_off:
+            dev_off.append(buf[p:p + o.numel()].view(o.shape))
+            p += o.numel()
+        return BagWindow(self, buf[:total], buf[total:total + n_pos], dev_off, host_off, lens, int(tab_len.max()))
+
+
 class WindowPipeline:
     def __init__(self, cache_group: Embedding_Table_Cache_Group, host_tables: Embedding_Table_Group, max_window: int,
                  *, parity_rng: bool = False, seed: int = 0, average_on_writeback: bool = False, rank: int = 0,
@@ -1173,7 +1282,11 @@ class TrainEngine:
         self.mark_next = False
         self._res, self._next_res = res, (next_res if next_idx is not None else None)
         if lS_o is not None:
-            assert lS_o.shape[1] in (B, B + 1) and (not self.multi or lS_o.shape[1] == B)
+            # [T, B + 1]: squared-off ragged bags (square_bags, BagWindow.rank_batch).  Their padding lookups go through the
+            # embedding backward like any lookup and set the touched flag of their slot, which decides what the row merge
+            # averages at world > 1.  They repeat the first index of THIS rank's lookups of the table: a slot this rank's
+            # own lookups flag anyway (a hit) or an aux row (never flagged), so the merge set is the rank's real lookups'.
+            assert lS_o.shape[1] in (B, B + 1)
         if j is None:
             j = self.iter
         # (the row merge at the end of a table-agg step leaves aux rows alone -- the backward never flags them --, so the

@@ -335,7 +335,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         emb_tables, args):
     """main_no_ddp.py:324-502 on the fused engine.  One process per GPU; `rank` is the device index and the
     distributed rank.  train_ld yields (X, lS_o, lS_i, T) global batches; every rank takes its slice."""
-    from .engine import TrainEngine, WindowPipeline, WindowResolver, pad_window, square_bags
+    from .engine import BagWindows, TrainEngine, WindowPipeline, WindowResolver, pad_window, square_bags
     try:
         from setproctitle import setproctitle
         setproctitle("DlrmTrainer:" + str(rank))
@@ -366,13 +366,20 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
     # table, each miss takes its own aux row (model_no_ddp.py:176-179) -- the reference sizes the aux region for one
     # lookup per sample and would index past it; here the region covers the squared-off width (slot ids of the first
     # mini_batch_size misses are the reference's)
+    # At world > 1 rank r trains the bags of samples [r * lbs, (r + 1) * lbs), lbs = local_batch_size (also on a short last
+    # batch: the rows of X and T), and takes of every table exactly their lookups (engine.rank_bag_slice; the reference's
+    # lS_i[:, rank*b:(rank+1)*b] slice, :388-391, holds for one lookup per bag only).
+    # A rank's squared width is round256 of at most local_batch_size * num_indices_per_lookup lookups: the bound below covers it.
+    # Every rank draws the same global batches: the random front end draws from numpy's global generator only, reseeds it to
+    # --numpy-rand-seed when batch 0 is read (RandomDataset.reset_seed_on_access), in this process (num_workers 0), and
+    # nothing else in Run draws from that generator after the model is built.
     multi_hot = getattr(train_ld, "multi_hot", False)
     aux_rows = args.mini_batch_size
+    bag_windows = None
     if multi_hot:
-        if world > 1:
-            sys.exit("ERROR: multi-hot bags (--data-generation=random) run on one rank; the rank slice "
-                     "(main_no_ddp.py:388-391) is defined for one lookup per sample")
         aux_rows = (args.mini_batch_size * max(1, args.num_indices_per_lookup) + 255) // 256 * 256
+        if world > 1:       # a window's global lists go to HBM once; each step's rank slice is cut there
+            bag_windows = BagWindows(len(ln_emb), dev, local_batch_size, world_size=world, rank=rank)
     cache_group = Embedding_Table_Cache_Group(m_spa, ln_emb, max_cache_size=args.cache_size,
                                               aux_table_size=aux_rows, num_ways=args.num_ways).to(dev)
     dlrm = DLRM_Net(ln_bot, ln_top, arch_interaction_op=args.arch_interaction_op,
@@ -441,6 +448,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         window = []
         next_window = None          # look-ahead plan: the window whose plan is already in flight
         next_win_idx = cur_win_idx = None
+        next_bags = cur_bags = None     # world > 1 multi-hot: the window's engine.BagWindow, kept beside its plan indices
         resolver, wj = None, 0
         carried_idx = None          # device indices of the batch whose probe the previous step already issued
         j = 0
@@ -458,11 +466,18 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             return win
 
         def window_indices(win):
+            """-> (the plan's int64 [T, n] on the device, the window's engine.BagWindow at world > 1 multi-hot, else None)"""
+            if bag_windows is not None:
+                try:
+                    bw = bag_windows.load(win)
+                except ValueError as e:     # (every rank checks every rank's slices: all of them stop here together)
+                    sys.exit("ERROR: " + str(e))
+                return bw.window_indices(), bw
             if multi_hot:           # ragged per-table lists: the plan only needs each table's set of indices
                 return pad_window([torch.cat([torch.as_tensor(b[2][k]).reshape(-1) for b in win])
-                                   for k in range(len(ln_emb))]).to(dev)
+                                   for k in range(len(ln_emb))]).to(dev), None
             return torch.cat([torch.as_tensor(b[2]) if not isinstance(b[2], (list, tuple)) else
-                              torch.stack([torch.as_tensor(s).reshape(-1) for s in b[2]]) for b in win], dim=1).to(dev)
+                              torch.stack([torch.as_tensor(s).reshape(-1) for s in b[2]]) for b in win], dim=1).to(dev), None
 
         while True:
             if not window:
@@ -473,9 +488,10 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                     break
                 torch.cuda.synchronize(dev)     # the steps issued so far belong to the iteration time, not to the refill
                 start = timer()
-                cur_win_idx = next_win_idx if planned else None
+                cur_win_idx, cur_bags = (next_win_idx, next_bags) if planned else (None, None)
+                next_win_idx = next_bags = None
                 if not planned:
-                    cur_win_idx = window_indices(window)
+                    cur_win_idx, cur_bags = window_indices(window)
                     pipe.plan_window(cur_win_idx)
                 if world > 1:
                     eng.sync_touched_to_rank0()
@@ -485,7 +501,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                 resolver, wj = None, 0
                 if not multi_hot:
                     if cur_win_idx is None:
-                        cur_win_idx = window_indices(window)
+                        cur_win_idx, _ = window_indices(window)
                     if cur_win_idx.shape[1] == len(window) * args.mini_batch_size:      # whole batches only
                         # (chunks of 32 batches at world > 1: the row merge orders its rows by the batches resolved ahead)
                         resolver = WindowResolver(eng, cur_win_idx, args.mini_batch_size, chunk=16 if world == 1 else 32)
@@ -494,7 +510,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                 if lookahead_plan:
                     next_window = read_window() or None
                     if next_window is not None:     # evictions are in the host tables: the next plan may read them
-                        next_win_idx = window_indices(next_window)
+                        next_win_idx, next_bags = window_indices(next_window)
                         pipe.plan_window(next_win_idx)
             X, lS_o, lS_i, T = window.pop(0)
             Or = nxt = None
@@ -510,7 +526,10 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                 # the take and the probe read rows at a pitch -- packing it cost a 1.7 MB copy kernel on the training queue per step
                 return v.to(dev)
 
-            if multi_hot:
+            if cur_bags is not None:
+                Or, Ir, rs_ = cur_bags.rank_batch(wj)       # (rs_ = the rows of X and T its bags belong to)
+                Xr, Tr = X[rs_, :].to(dev), T[rs_, :].to(dev)
+            elif multi_hot:
                 Or, Ir = square_bags([lS_o[k] for k in range(len(ln_emb))], lS_i, dev)
                 Xr, Tr = X.to(dev), T.to(dev)
             else:

@@ -812,6 +812,39 @@ def scatter_rows(dst_ptr: int, index: torch.Tensor, rows: torch.Tensor, average:
                                         1 if average else 0, stream_ptr(stream)))
 
 
+def bags_window(buf: torch.Tensor, bpos: torch.Tensor, L: int, n_win: int, out: Optional[torch.Tensor] = None,
+                stream=None) -> torch.Tensor:
+    """int64 [T, n_win] window rectangle (engine.pad_window's contract) of a device window buffer: buf int64 [total], bpos
+    int64 [(L + 1) * T] (include/cdlrm_hip.h: cdlrm_bags_window)."""
+    _require_cuda(buf, "buf"); _require_cuda(bpos, "bpos")
+    assert buf.dtype == torch.int64 and bpos.dtype == torch.int64 and buf.is_contiguous() and bpos.is_contiguous()
+    T = bpos.numel() // (L + 1)
+    assert bpos.numel() == (L + 1) * T
+    if out is None:
+        out = torch.empty(T, n_win, dtype=torch.int64, device=buf.device)
+    assert out.shape == (T, n_win) and out.is_contiguous() and out.dtype == torch.int64
+    check(_lib.lib().cdlrm_bags_window(buf.data_ptr(), buf.numel(), bpos.data_ptr(), L, T, n_win, out.data_ptr(),
+                                       stream_ptr(stream)))
+    return out
+
+
+def bags_rank_slice(buf: torch.Tensor, bpos: torch.Tensor, L: int, b: int, off: torch.Tensor, s0: int, s1: int, n: int,
+                    stream=None):
+    """Batch b of a device window buffer, a rank's samples [s0, s1) -> (off int64 [T, s1 - s0 + 1], idx int64 [T, n]): the
+    layout engine.square_bags() gives the rank's rebased lookups (include/cdlrm_hip.h: cdlrm_bags_rank_slice).  off: the
+    batch's global offsets, int64 [T, nbag] on the device (a view of the window buffer may do)."""
+    _require_cuda(buf, "buf"); _require_cuda(bpos, "bpos"); _require_cuda(off, "off")
+    assert buf.dtype == torch.int64 and bpos.dtype == torch.int64 and off.dtype == torch.int64
+    assert buf.is_contiguous() and bpos.is_contiguous() and off.is_contiguous() and off.dim() == 2
+    T, nbag = off.shape
+    assert bpos.numel() == (L + 1) * T
+    idx = torch.empty(T, n, dtype=torch.int64, device=buf.device)
+    off_out = torch.empty(T, s1 - s0 + 1, dtype=torch.int64, device=buf.device)
+    check(_lib.lib().cdlrm_bags_rank_slice(buf.data_ptr(), buf.numel(), bpos.data_ptr(), L, b, T, off.data_ptr(), nbag, s0, s1,
+                                           n, idx.data_ptr(), off_out.data_ptr(), stream_ptr(stream)))
+    return off_out, idx
+
+
 def mark_rows(ctx: CacheCtx, slots: torch.Tensor, touched: torch.Tensor, stream=None):
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[0] == ctx.T
     check(_lib.lib().cdlrm_mark_rows(ctx.handle, slots.data_ptr(), slots.shape[1], touched.data_ptr(),

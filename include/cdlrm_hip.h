@@ -608,6 +608,22 @@ int cdlrm_scale_div(float* x, int64_t n, float divisor, void* stream);
  * second pass over the same indices (cache_manager.py:87-90) regenerate identical data independently, one launch per table. */
 int cdlrm_synth_indices(int64_t* out, int64_t count, int64_t first, int64_t n_rows, double alpha, uint64_t key, void* stream);
 
+/* ---- ragged multi-hot bags on the device (engine.BagWindows; the reference slices by sample position,
+ * main_no_ddp.py:388-391, which holds for one lookup per bag only) ---------------------------------------------------------
+ * buf [total] int64: a look-ahead window of L batches, table k's list = the concatenation of its batches' table-k lists.
+ * bpos [(L + 1) * T] int64: bpos[b * T + k] = position in buf of batch b's table-k list, bpos[L * T + k] = the end of table
+ * k's list.  Every table list must hold >= 1 index (the host checks).  One launch covers every table. */
+/* out [T, n_win] = engine.pad_window(): table k's window list, padded with its own first index (n_win >= the longest). */
+int cdlrm_bags_window(const int64_t* buf, int64_t total, const int64_t* bpos, int32_t L, int32_t T, int64_t n_win,
+                      int64_t* out, void* stream);
+/* Batch b (global offsets off [T, nbag]), a rank's samples [s0, s1), nb = s1 - s0: engine.square_bags() of the rank's
+ * lookups, rebased.  With a_k = off[k, s0], e_k = off[k, s1] (s1 < nbag) or the batch's table-k length, m_k = e_k - a_k:
+ * idx [T, n] (16-byte aligned, n even and >= every m_k) = list_k[a_k + i] for i < m_k, padded with list_k[a_k];
+ * off_out [T, nb + 1] = off[k, s0 + i] - a_k, and off_out[k, nb] = m_k (the padding lookups pool into the scratch bag nb). */
+int cdlrm_bags_rank_slice(const int64_t* buf, int64_t total, const int64_t* bpos, int32_t L, int32_t b, int32_t T,
+                          const int64_t* off, int64_t nbag, int64_t s0, int64_t s1, int64_t n, int64_t* idx, int64_t* off_out,
+                          void* stream);
+
 /* ---- launch tapes -------------------------------------------------------------------------------------------------
  * A training step's call sequence (this library's entry points + event records / stream waits), recorded once per control
  * path by the host and re-issued by ONE call per step (the reference issues the same ops from Python every iteration,
