@@ -129,6 +129,10 @@ def ProcessArgs(argv=None):
     # ---- this build (not in the reference) ----
     parser.add_argument("--synthetic-alpha", type=float, default=1.05,
                         help="Zipf exponent of --data-generation=criteo-synthetic indices (0 = uniform)")
+    parser.add_argument("--day-file-loader", type=str, default="host", choices=["host", "device"],
+                        help="--data-generation=dataset: `host` = the reference's per-batch host loader; `device` = the raw rows "
+                             "of a whole look-ahead window are uploaded ahead and cut into batches on the GPU "
+                             "(data_loader_terabyte.DeviceDayLoader)")
     parser.add_argument("--device-rng", action="store_true", default=False,
                         help="way choice by counter-based Philox on the GPU (perf mode; not bit-comparable with the "
                              "reference's torch-CPU Categorical draw)")
@@ -467,6 +471,13 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
 
         def window_indices(win):
             """-> (the plan's int64 [T, n] on the device, the window's engine.BagWindow at world > 1 multi-hot, else None)"""
+            b0 = win[0]
+            if getattr(b0, "window_rect", None) is not None and b0.win_pos == 0 and len(win) == b0.win_batches:
+                # DeviceDayLoader: the batches are columns of their window's rectangle, which is the plan's input as it lies.
+                # The streams that read it beside the training queue (plan, resolve, takes / sorts) go behind its upload.
+                for st in {pipe.side, eng.pref, eng.side, getattr(eng, "sort_st", eng.pref)}:
+                    b0.wait_upload(st)
+                return b0.window_rect, None
             if bag_windows is not None:
                 try:
                     bw = bag_windows.load(win)
@@ -597,7 +608,8 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                     total_test_acc += np.sum((np.round(S_, 0) == Tn).astype(np.uint32))
                     test_samp += Tn.shape[0]
                     test_scores.append(Zt.reshape(-1).clone())
-                    test_targets.append(Tt.reshape(-1).to(dev))
+                    # (a DeviceDayLoader batch is a view of a ring the loader reuses two windows later: keep a copy)
+                    test_targets.append(Tt.reshape(-1).clone() if Tt.is_cuda else Tt.reshape(-1).to(dev))
                 print('Test accuracy = {}%'.format(100 * (total_test_acc / test_samp)), flush=True)
                 # the second figure the reference's MLPerf flags speak of (main_no_ddp.py:117-120) and never compute: the AUC of
                 # the test scores, rank-sum on the device (ops.roc_auc; an extra line behind the reference's own)
@@ -692,7 +704,7 @@ def main(argv=None):
     if args.data_generation == "dataset":
         # the pre-processed day files of the reference's terabyte path (dlrm_data_pytorch.py:440-492): table sizes
         # from <raw>_fea_count.npz (:180-181), batches from <raw>_<day>_reordered.npz
-        from .data_loader_terabyte import DataLoader
+        from .data_loader_terabyte import DataLoader, DeviceDayLoader
         d_dir, d_name = os.path.dirname(args.raw_data_file) or ".", os.path.basename(args.raw_data_file)
         with np.load(args.raw_data_file + "_fea_count.npz") as data:
             counts = data["counts"]
@@ -701,9 +713,15 @@ def main(argv=None):
         if not days:
             sys.exit("ERROR: no %s_<day>_reordered.npz under %s" % (d_name, d_dir))
         train_days, test_days = (days[:-1], days[-1:]) if len(days) > 1 else (days, days)
-        train_ld = DataLoader(d_name, d_dir, train_days, args.mini_batch_size, args.max_ind_range, "train", True)
         tb = args.test_mini_batch_size if args.test_mini_batch_size > 0 else args.mini_batch_size
-        test_ld = DataLoader(d_name, d_dir, test_days, tb, args.max_ind_range, "test")
+        if args.day_file_loader == "device":
+            # (the device is chosen below: the loaders touch it when they are first iterated)
+            train_ld = DeviceDayLoader(d_name, d_dir, train_days, args.mini_batch_size, args.max_ind_range, "train", True,
+                                       window=args.lookahead)
+            test_ld = DeviceDayLoader(d_name, d_dir, test_days, tb, args.max_ind_range, "test", window=16)
+        else:
+            train_ld = DataLoader(d_name, d_dir, train_days, args.mini_batch_size, args.max_ind_range, "train", True)
+            test_ld = DataLoader(d_name, d_dir, test_days, tb, args.max_ind_range, "test")
     ln_emb = np.fromstring(args.arch_embedding_size, dtype=int, sep="-")
     if args.max_ind_range > 0:
         ln_emb = np.minimum(ln_emb, args.max_ind_range)
@@ -749,6 +767,11 @@ def main(argv=None):
         else:
             dist.init_process_group("nccl", rank=rank, world_size=args.world_size, device_id=dev)
     launch.check_world(args.world_size)
+    if args.data_generation == "dataset" and args.day_file_loader == "device":
+        train_ld.device = test_ld.device = dev
+        if rank == 0:
+            print("Day-file loader: device (windows of %d batches cut on the GPU, one window uploaded ahead)" % train_ld.window,
+                  flush=True)
     from . import synth
     from .hostmem import make_host_tables
     emb_tables = make_host_tables(ln_emb, m_spa, device=dev, seed=args.numpy_rand_seed, rank=rank, world=args.world_size,
@@ -765,7 +788,10 @@ def main(argv=None):
         syn = synth.CriteoSynth(ln_emb, int(m_den), args.mini_batch_size, seed=args.numpy_rand_seed,
                                 alpha=args.synthetic_alpha, device=dev)
         train_ld = _SyntheticLoader(syn, nb, args.mini_batch_size)
-    Run(local_rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, None, None, None, emb_tables, args)
+    eng = Run(local_rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, None, None, None, emb_tables, args)
+    if os.environ.get("CDLRM_DUMP_TAGS"):
+        # development (tests/test_dayfile_device.py): every rank's final cache tags, for bit-for-bit comparison of two runs
+        torch.save(eng.cg.tags.cpu(), "%s.rank%d" % (os.environ["CDLRM_DUMP_TAGS"], rank))
     if args.world_size > 1:
         dist.destroy_process_group()
 

@@ -845,6 +845,35 @@ def bags_rank_slice(buf: torch.Tensor, bpos: torch.Tensor, L: int, b: int, off: 
     return off_out, idx
 
 
+def dayfile_tile() -> int:
+    """Samples per workgroup of `dayfile_window`'s kernel."""
+    return int(_lib.lib().cdlrm_dayfile_tile())
+
+
+def dayfile_window(x_int: torch.Tensor, x_cat: torch.Tensor, y: torch.Tensor, max_ind_range: int, X: torch.Tensor,
+                   lS_i: torch.Tensor, T: torch.Tensor, col0: int = 0, stream=None) -> None:
+    """n raw day-file rows on the device (x_int int32 [n, n_dense], x_cat int32 [n, n_cat], y int32 [n]) -> samples
+    [col0, col0 + n) of a window: X fp32 [rows, n_dense] = log(x_int + 1), lS_i int64 [n_cat, pitch] = x_cat^T (floor-mod
+    max_ind_range when > 0), T fp32 [rows] or [rows, 1] = y (include/cdlrm_hip.h: cdlrm_dayfile_window).  lS_i may be a
+    column range of a wider rectangle (unit column stride); nothing outside the n samples is written."""
+    for t, name in ((x_int, "x_int"), (x_cat, "x_cat"), (y, "y"), (X, "X"), (lS_i, "lS_i"), (T, "T")):
+        _require_cuda(t, name)
+    assert x_int.dtype == torch.int32 and x_cat.dtype == torch.int32 and y.dtype == torch.int32
+    assert X.dtype == torch.float32 and T.dtype == torch.float32 and lS_i.dtype == torch.int64
+    assert x_int.dim() == 2 and x_cat.dim() == 2 and y.dim() == 1 and X.dim() == 2 and lS_i.dim() == 2
+    assert x_int.is_contiguous() and x_cat.is_contiguous() and y.is_contiguous() and X.is_contiguous() and T.is_contiguous()
+    n, nd, nc = y.shape[0], x_int.shape[1], x_cat.shape[1]
+    col0 = int(col0)
+    assert x_int.shape[0] == n and x_cat.shape[0] == n and X.shape[1] == nd and lS_i.shape[0] == nc and nd >= 1 and nc >= 1
+    assert col0 >= 0 and col0 + n <= X.shape[0] and col0 + n <= T.numel() and col0 + n <= lS_i.shape[1], \
+        "samples [%d, %d) do not fit the window buffers" % (col0, col0 + n)
+    assert lS_i.stride(1) == 1 or lS_i.shape[1] == 1
+    pitch = lS_i.stride(0) if nc > 1 else lS_i.shape[1]
+    assert pitch >= lS_i.shape[1]
+    check(_lib.lib().cdlrm_dayfile_window(x_int.data_ptr(), x_cat.data_ptr(), y.data_ptr(), n, nd, nc, int(max_ind_range),
+                                          X.data_ptr(), lS_i.data_ptr(), pitch, col0, T.data_ptr(), stream_ptr(stream)))
+
+
 def mark_rows(ctx: CacheCtx, slots: torch.Tensor, touched: torch.Tensor, stream=None):
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[0] == ctx.T
     check(_lib.lib().cdlrm_mark_rows(ctx.handle, slots.data_ptr(), slots.shape[1], touched.data_ptr(),

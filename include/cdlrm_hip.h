@@ -624,6 +624,25 @@ int cdlrm_bags_rank_slice(const int64_t* buf, int64_t total, const int64_t* bpos
                           const int64_t* off, int64_t nbag, int64_t s0, int64_t s1, int64_t n, int64_t* idx, int64_t* off_out,
                           void* stream);
 
+/* ---- Criteo day-file batches cut on the device (data_loader_terabyte.DeviceDayLoader) ---------------------------------
+ * Replaces, for n raw rows of a pre-processed day file that lie in HBM as the file stores them (x_int int32 [n, n_dense],
+ * x_cat int32 [n, n_cat], y int32 [n], row-major), the reference's per-batch host transform _transform_features
+ * (data_loader_terabyte.py:68-87) and the trainer's per-step uploads of its result (main_no_ddp.py:388-391):
+ *   X[col0 + i, :]                 fp32  = log((float)x_int[i, :] + 1.0f)    (int32 -> fp32 first, an fp32 add, as :73; the
+ *                                          logarithm is taken in double and rounded once)
+ *   lS_i[k * lS_i_pitch + col0 + i] int64 = x_cat[i, k], reduced by numpy's floor-mod when max_ind_range > 0 (:70-71: a negative
+ *                                          entry gives a non-negative result), untouched otherwise
+ *   T[col0 + i]                    fp32  = y[i]
+ * X is fp32 [>= col0 + n, n_dense] row-major, T fp32 [>= col0 + n], lS_i int64 [n_cat, lS_i_pitch] with lS_i_pitch >= col0 + n:
+ * several file segments of one look-ahead window land in one rectangle, one launch each; cells outside columns
+ * [col0, col0 + n) are not written.  n_cat <= 60 (a tile of samples is staged in LDS).  Not a tape entry point: it never runs
+ * on the training queue. */
+int cdlrm_dayfile_window(const int32_t* x_int, const int32_t* x_cat, const int32_t* y, int64_t n, int32_t n_dense, int32_t n_cat,
+                         int64_t max_ind_range, float* X, int64_t* lS_i, int64_t lS_i_pitch, int64_t col0, float* T,
+                         void* stream);
+/* samples per workgroup of cdlrm_dayfile_window (tests probe its edges; tools size their grids by it) */
+int cdlrm_dayfile_tile(void);
+
 /* ---- launch tapes -------------------------------------------------------------------------------------------------
  * A training step's call sequence (this library's entry points + event records / stream waits), recorded once per control
  * path by the host and re-issued by ONE call per step (the reference issues the same ops from Python every iteration,
