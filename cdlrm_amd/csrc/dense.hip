@@ -315,9 +315,13 @@ __global__ void __launch_bounds__(256) k_reduce_group(ReduceGroup grp) {
                       r.splits, r.outB, red, r.pA, r.pB, r.lr, r.novec);
 }
 
-// Weight-gradient contraction (over the batch) is cut into slabs when the batch is long: small batches go to the
-// LDS-free kernel un-split (no reduction launch at all), long ones to the tiled kernel with ~1024 workgroups.
-#define WGRAD_DIRECT_MAX_M 2048
+// ---- weight gradients: dW = dZ^T X over the batch, db = column sums of dZ -------------------------------------------------
+// The contraction (the batch) is cut into slabs: a GEMM writes one partial dW (and one row of bias partials) per slab into
+// `work`, a reduction sums them in slab order (fixed order: reproducible) and can take the SGD step in the same pass.
+#define WGRAD_DIRECT_MAX_M 2048     // up to here cdlrm_mlp_wgrad* groups the layers; cdlrm_linear_bwd does not split at all
+static inline uint64_t r256(uint64_t bytes) { return (bytes + 255) & ~(uint64_t)255; }
+
+// slab count of ONE layer at a long batch (cdlrm_linear_bwd, and every fp32 layer of cdlrm_mlp_wgrad* above WGRAD_DIRECT_MAX_M)
 static int wgrad_splits(int64_t M, int N, int K) {
     if (M <= WGRAD_DIRECT_MAX_M) return 1;
     const int64_t tiles = cdiv(N, 64) * cdiv(K, 64);    // the 64x64 tile launch_gemm picks for these shapes
@@ -329,32 +333,41 @@ static int wgrad_splits(int64_t M, int N, int K) {
     return (int)s;
 }
 
+// One layer's slabs inside `work` from byte `off`: zs partial dW [N, K], then (from *cs) zs rows of bias partials [N], each block
+// rounded up to 256 bytes.  Returns the end.
+static inline uint64_t wgrad_carve(uint64_t off, int zs, int N, int K, uint64_t* cs) {
+    *cs = off + r256((uint64_t)zs * N * K * 4);
+    return *cs + r256((uint64_t)zs * N * 4);
+}
+
+// Point the weight-gradient problem g of a layer at its zs > 1 slabs and describe their reduction (gxa: workgroups of the dW part;
+// pW / pB: the layer's parameters when the SGD step rides in the reduction, else NULL).
+static inline ReduceJob wgrad_slabbed(GemmArgs& g, void* work, uint64_t slabs, uint64_t cs, int zs, int gxa, float* dW, float* db,
+                                      float* pW, float* pB, float lr) {
+    g.C = (float*)((char*)work + slabs);
+    g.colsum = db ? (float*)((char*)work + cs) : nullptr;
+    ReduceJob r;
+    r.partA = g.C; r.countA = g.M * g.N; r.outA = dW; r.gxa = gxa;
+    r.partB = (float*)((char*)work + cs); r.countB = db ? g.M : 0; r.outB = db;
+    r.splits = zs;
+    r.pA = pW; r.pB = db ? pB : nullptr; r.lr = lr;
+    r.novec = g_cdlrm_debug[2];
+    return r;
+}
+
+static inline int reduce_gxa(int64_t cnt, int per_wg, int cap) {
+    const int64_t gxa = cdiv(cnt, per_wg);
+    return (int)(gxa > cap ? cap : gxa);
+}
+
 // (Round 5, measured and removed: a STREAMING kernel for the weight gradient of the 13-wide layer at long batches -- a thread owns
 //  four columns of dZ, 16-byte loads, eight rows in flight, the slab's X rows in LDS, 128-row slabs into the grouped reduction;
 //  correct against fp64 at M = 16384 / 20011 -- because the LDS-free MFMA kernel takes 251 us for it inside a c5 step (134 MB of
 //  dZ, 17 us of HBM time).  In the step: c5 3.7080 against 3.7059 ms, a tie; forced at c3 0.5680 against 0.5599, at 4096 0.3394
 //  against 0.3288.  That launch lies in the half of the step that is bound by the SUM of its work, not by any kernel's length.)
 extern "C" uint64_t cdlrm_linear_bwd_work_bytes(int64_t M, int32_t N, int32_t K) {
-    const uint64_t splits = (uint64_t)wgrad_splits(M, N, K);
-    const uint64_t slabs = splits * N * K * 4;
-    const uint64_t cs = splits * N * 4;
-    return ((slabs + 255) & ~(uint64_t)255) + ((cs + 255) & ~(uint64_t)255) + 256;
-}
-
-// scratch for cdlrm_mlp_wgrad: every layer's slabs at once on the grouped small-batch path, the largest layer's
-// otherwise
-extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K) {
-    uint64_t total = 256, largest = 0;
-    if (!N || !K) return 0;
-    if (M <= WGRAD_DIRECT_MAX_M) {
-        const uint64_t zs = (uint64_t)cdiv(M, 4 * GBK) + 1;         // upper bound of the split count
-        for (int i = 0; i < n_layers; ++i)
-            total += ((zs * N[i] * K[i] * 4 + 255) & ~(uint64_t)255) + ((zs * N[i] * 4 + 255) & ~(uint64_t)255);
-        return total;
-    }
-    (void)largest;
-    for (int i = 0; i < n_layers; ++i) total += cdlrm_linear_bwd_work_bytes(M, N[i], K[i]);      // every layer its own slabs
-    return total;
+    uint64_t cs;
+    return wgrad_carve(0, wgrad_splits(M, N, K), N, K, &cs) + 256;
 }
 
 // rec != nullptr: the route query (cdlrm_linear_bwd_route): rec[0] the dgrad, rec[1] the weight gradient; nothing launched
@@ -370,9 +383,6 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
     CDLRM_REQUIRE(act >= 0 && act <= 2 && x_act >= 0 && x_act <= 2, "bad activation code");
     CDLRM_REQUIRE(((uintptr_t)work & 255) == 0, "work must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const int splits = wgrad_splits(M, N, K);
-    float* slabs = (float*)work;
-    float* cs = (float*)((char*)work + ((((uint64_t)splits * N * K * 4) + 255) & ~(uint64_t)255));
     if (act != 0 && !rec) {     // dZ = dY * act'(Y) in place
         const int64_t nb = cdiv(M * N, 256), blocks = nb < 2048 ? nb : 2048;
         hipLaunchKernelGGL(k_act_grad, dim3((unsigned)blocks), dim3(256), 0, s, Y, ld_y, dY, ld_dy, M, N, act);
@@ -389,50 +399,39 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
         if (rc) return rc;
     }
     // dW[N,K] = dZ[M,N]^T X[M,K], split over M into slabs summed in slab order; the first column panel of the
-    // same GEMM sums dZ over the batch (bias gradient)
-    if (dW && bf16) {
-        // the same split-M slabs (at most `splits` of them: the work size does not change) and the same slab reduction
+    // same GEMM sums dZ over the batch (bias gradient).  bf16: the same split-M slabs (at most `splits` of them: the work size
+    // does not change) and the same slab reduction.
+    if (dW) {
+        const int splits = wgrad_splits(M, N, K);
         GemmArgs g = gemm_args();
-        g.A = dY; g.lda = ld_dy; g.B = X; g.ldb = ld_x; g.ldc = K;
+        g.A = dY; g.lda = ld_dy; g.B = X; g.ldb = ld_x; g.C = dW; g.ldc = K; g.colsum = db;
         g.slab = (int64_t)N * K;
-        g.M = N; g.N = K; g.K = M; g.kchunk = bf16_wgrad_kchunk(M, cdiv(N, 64) * cdiv(K, 64), splits);
-        const int va = bf16_vec<false>(dY, ld_dy, N, M), vb = bf16_vec<false>(X, ld_x, K, M);
-        g.vecA = va; g.vecB = vb;
-        const int zs = (int)cdiv(M, g.kchunk);
-        g.C = zs > 1 ? slabs : dW;
-        g.colsum = db ? (zs > 1 ? cs : db) : nullptr;
-        if (rec) {
-            gemm_record(rec + 1, CDLRM_ROUTE_BF16, 1, 1, 0, 0, zs, va, vb, 0);
-            return 0;
+        g.M = N; g.N = K; g.K = M;
+        if (bf16) {
+            g.kchunk = bf16_wgrad_kchunk(M, cdiv(N, 64) * cdiv(K, 64), splits);
+            g.vecA = bf16_vec<false>(dY, ld_dy, N, M);
+            g.vecB = bf16_vec<false>(X, ld_x, K, M);
+        } else {
+            g.kchunk = cdiv(cdiv(M, splits), GBK) * GBK;
+            g.vecA = aligned16(dY) && ld_dy % 4 == 0 && N % 4 == 0;
+            g.vecB = aligned16(X) && ld_x % 4 == 0 && K % 4 == 0;
         }
-        int rc = launch_wgrad_bf16(&g, 1, va, vb, s);
-        if (rc) return rc;
-        if (zs > 1) {
-            int64_t gxa = cdiv((int64_t)N * K, 256);
-            if (gxa > 2048) gxa = 2048;
-            const int64_t gxb = db ? cdiv(N, 64) : 0;
-            hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)(gxa + gxb)), dim3(256), 0, s, slabs, (int64_t)N * K, zs, dW,
-                               (int)gxa, cs, (int64_t)N, zs, db);
-        }
-    } else if (dW) {
-        GemmArgs g = gemm_args();
-        g.A = dY; g.lda = ld_dy; g.B = X; g.ldb = ld_x; g.ldc = K;
-        g.slab = (int64_t)N * K;
-        g.M = N; g.N = K; g.K = M; g.kchunk = cdiv(cdiv(M, splits), GBK) * GBK; g.bias = nullptr; g.act = 0;
-        g.vecA = aligned16(dY) && ld_dy % 4 == 0 && N % 4 == 0;
-        g.vecB = aligned16(X) && ld_x % 4 == 0 && K % 4 == 0;
         const int zs = (int)cdiv(M, g.kchunk);      // <= splits
-        g.C = zs > 1 ? slabs : dW;
-        g.colsum = db ? (zs > 1 ? cs : db) : nullptr;
-        int rc = launch_gemm<false, false>(g, zs, s, rec ? rec + 1 : nullptr);
-        if (rc) return rc;
-        if (zs > 1 && !rec) {   // one launch sums the dW slabs and the bias-gradient partials
-            int64_t gxa = cdiv((int64_t)N * K, 256);
-            if (gxa > 2048) gxa = 2048;
-            const int64_t gxb = db ? cdiv(N, 64) : 0;
-            hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)(gxa + gxb)), dim3(256), 0, s, slabs, (int64_t)N * K, zs, dW,
-                               (int)gxa, cs, (int64_t)N, zs, db);
+        ReduceJob r{};
+        if (zs > 1) {
+            uint64_t cs;
+            wgrad_carve(0, zs, N, K, &cs);
+            // (one layer alone on the queue: a reduction up to 2048 workgroups wide)
+            r = wgrad_slabbed(g, work, 0, cs, zs, reduce_gxa(g.slab, 256, 2048), dW, db, nullptr, nullptr, 0.f);
         }
+        int rc = 0;
+        if (!bf16) rc = launch_gemm<false, false>(g, zs, s, rec ? rec + 1 : nullptr);
+        else if (rec) gemm_record(rec + 1, CDLRM_ROUTE_BF16, 1, 1, 0, 0, zs, g.vecA, g.vecB, 0);
+        else rc = launch_wgrad_bf16(&g, 1, g.vecA, g.vecB, s);
+        if (rc) return rc;
+        if (zs > 1 && !rec)     // one launch sums the dW slabs and the bias-gradient partials
+            hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)(r.gxa + cdiv(r.countB, 64))), dim3(256), 0, s, r.partA, r.countA, zs,
+                               dW, r.gxa, r.partB, r.countB, zs, db);
     }
     if (!rec) CDLRM_LAUNCH_CHECK();
     return 0;
@@ -459,6 +458,27 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
     return linear_bwd(X, ld_x, W, Y, ld_y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, stream, rec);
 }
 
+// ---- cdlrm_mlp_wgrad*: the weight (and bias) gradients of SEVERAL layers at once ------------------------------------------------
+// ... from the pre-activation gradients dZ[i] that the dgrad chain left behind (cdlrm_linear_bwd with dW = NULL).
+// What a call launches is decided in ONE place, wgrad_layout; the launching entry points, the route query and the size queries
+// all read the layout it returns.
+//
+// Kernel families, in launch order:
+//   short batches (M <= WGRAD_DIRECT_MAX_M), all fp32 layers at once:
+//     WG_DIRECT  the grouped LDS-free kernel: layers whose operands are not 16-byte loadable (13-wide input, 1-wide output), and
+//                every layer below M = 256
+//     WG_TILED   the LDS-tiled kernel as one grouped launch; the LDS-free layers ride in front of its first group where the
+//                combination allows (launch_wgrad_mixed)
+//     one slab count for all of them, then ONE grouped reduction
+//   long batches:
+//     WG_SPLIT   per layer one split-M GEMM (launch_gemm picks the kernel: tiled, or LDS-free for degenerate shapes) into the
+//                layer's own slabs, then ONE grouped reduction of all layers
+//   flags & CDLRM_GEMM_BF16 (gemm_bf16.h), any batch:
+//     WG_BF16    the layers the shape rule admits (bf16_layer_ok) as one grouped bf16 launch on 64x64 tiles with one slab length
+//                (bf16_wgrad_kchunk), then one grouped reduction of their slabs.  The other layers (the 13-wide input, the 1-wide
+//                head) keep the family AND slab count they have in the all-fp32 call of the same layer list, run in front, and
+//                own the front part of `work`; the bf16 slabs follow it.
+//
 // (Round 4 built the two layers with a thin side -- the 13-wide first layer and the 1-wide output layer -- as vector-ALU
 //  reductions over the batch: lanes <-> columns of the wide operand, the thin operand's rows staged in LDS and read back as
 //  broadcasts, sixteen rows in flight per wave, the four waves of a workgroup summed through LDS in a fixed order, into the same
@@ -466,10 +486,123 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
 //  the LDS-free MFMA kernel they were to replace: 0.6125 against 0.6113 ms (13-wide), 0.6148 against 0.6146 (1-wide), same box,
 //  same process, tools/ab_step.py.  Where these launches sit -- the end of the backward, three queues deep -- a kernel's
 //  duration is set by what runs beside it (30 us in the trace for either version), not by its own instruction mix.  Removed.)
-// Weight (and bias) gradients of SEVERAL layers at once, from the pre-activation gradients dZ[i] that the dgrad chain
-// left behind (cdlrm_linear_bwd with dW = NULL): dW[i] = dZ[i]^T X[i], db[i] = column sums of dZ[i].
-// Small batches: all layers in one grouped launch of the LDS-free kernel (no slabs, no reduction); long batches: the
-// tiled split-M path, layer after layer.
+enum { WG_DIRECT, WG_TILED, WG_SPLIT, WG_BF16, WG_FAMILIES };
+struct WgradLayer {
+    int family;
+    int vecA, vecB;         // 16-byte loads legal for dZ / X
+    int zs;                 // slab count.  1: the GEMM writes dW / db itself -- no slabs, no reduction, and an SGD step needs the
+                            // elementwise pass; > 1: the step rides in the reduction
+    int gxa;                // zs > 1: workgroups of the dW part of the layer's reduction
+    int64_t kchunk;         // slab length (rows of the batch)
+    uint64_t slabs, cs;     // zs > 1: byte offsets in `work` of the dW slabs and the bias-gradient partials
+};
+struct WgradLayout {
+    std::vector<WgradLayer> L;      // one per layer, in the caller's order
+    int n_bf = 0;                   // layers of the bf16 group
+    int bf_vecA = 1, bf_vecB = 1;   // ... which runs one kernel variant: 16-byte loads where every member allows them
+    uint64_t high = 0;              // bytes of `work` the call writes: the end of the last block carved
+    uint64_t reserve = 0;           // what the size queries return; high <= reserve
+};
+
+// X == NULL (the size queries): no operand is known; only `reserve` is meaningful then, and it depends on none of them.
+static void wgrad_layout(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K, int32_t flags, const float* const* X,
+                         const int64_t* ld_x, const float* const* dZ, const int64_t* ld_dz, WgradLayout& p) {
+    const bool shortb = M <= WGRAD_DIRECT_MAX_M;
+    p.L.resize((size_t)(n_layers > 0 ? n_layers : 0));
+    // families; the tiles that set the slab counts
+    int64_t tiles = 0, bf_tiles = 0;
+    bool any_fp = false;
+    for (int i = 0; i < n_layers; ++i) {
+        WgradLayer& l = p.L[i];
+        l.vecA = N[i] % 4 == 0 && (!X || (aligned16(dZ[i]) && ld_dz[i] % 4 == 0));
+        l.vecB = K[i] % 4 == 0 && (!X || (aligned16(X[i]) && ld_x[i] % 4 == 0));
+        const bool tiled = l.vecA && l.vecB && M >= 256;
+        // (a layer that leaves for the bf16 group still counts: the slab count of the fp32 layers beside it is that of the all-fp32 call)
+        if (shortb && tiled) tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
+        if ((flags & CDLRM_GEMM_BF16) && bf16_layer_ok(N[i], K[i])) {
+            l.family = WG_BF16;
+            p.n_bf++;
+            bf_tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
+            if (X) {
+                l.vecA = bf16_vec<false>(dZ[i], ld_dz[i], N[i], M);
+                l.vecB = bf16_vec<false>(X[i], ld_x[i], K[i], M);
+            }
+            p.bf_vecA &= l.vecA; p.bf_vecB &= l.vecB;
+        } else {
+            l.family = !shortb ? WG_SPLIT : tiled ? WG_TILED : WG_DIRECT;
+            any_fp = true;
+        }
+    }
+    // slab length and count.  Short batches: one for all fp32 layers (1 = no slabs, no reduction)
+    int64_t kchunk = M;
+    if (shortb && tiles > 0) {
+        // workgroups the grouped launch aims at (slabs = target / tiles).  1024 until round 4 (7 slabs for the top MLP's 160
+        // tiles); measured in the step, five rounds each: per-rank batch 1024 -- 384 / 640 / 768 / 896 / 1024 / 1536 ->
+        // 0.1802 / 0.1814 / 0.1797 / 0.1813 / 0.1856 / 0.1851 ms; 2048 -- 256 / 384 / 512 / 640 / 768 / 1024 / 2048 ->
+        // 0.2495 / 0.2489 / 0.2372 / 0.2367 / 0.2404 / 0.2416 / 0.2405: four to five slabs, not seven (fewer partial
+        // slabs to write and reduce; three is too few workgroups at 2048)
+        const int64_t target_wgs = M <= 1024 ? 768 : 640;
+        int64_t splits = cdiv(target_wgs, tiles);
+        const int64_t smax = cdiv(M, 4 * GBK);
+        if (splits > smax) splits = smax;
+        if (splits < 1) splits = 1;
+        kchunk = cdiv(cdiv(M, splits), GBK) * GBK;
+    }
+    const int64_t bf_kchunk = bf16_wgrad_kchunk(M, bf_tiles, INT64_MAX);
+    // The reserve of the fp32 layers is a LEGACY UPPER BOUND, not the layout's own high-water mark: callers hold persistent
+    // scratch of the sizes these queries have always returned, so the formulas stay -- short batches one slab more than the
+    // split rule's cap for every layer (tiled or not), long batches cdlrm_linear_bwd_work_bytes per layer (wgrad_splits slabs
+    // where the layout may need fewer, 256 bytes of slack each), 256 bytes in front.  In a bf16 call it is also where the bf16
+    // group's slabs start; a call without fp32 layers reserves nothing for them.
+    uint64_t fp_reserve = (flags & CDLRM_GEMM_BF16) && !any_fp ? 0 : 256;
+    uint64_t cs;
+    // blocks in `work`, in launch order
+    for (int f = 0; f < WG_FAMILIES; ++f) {
+        if (f == WG_BF16 && (flags & CDLRM_GEMM_BF16)) p.high = fp_reserve;     // (the fp32 layers own the front part, used or not)
+        for (int i = 0; i < n_layers; ++i) {
+            WgradLayer& l = p.L[i];
+            if (l.family != f) continue;
+            const int64_t cnt = (int64_t)N[i] * K[i];
+            if (f == WG_BF16) {
+                l.kchunk = bf_kchunk;
+                // (a reduction beside nothing else: 256 elements per workgroup, up to 1024 workgroups per layer, as WG_SPLIT)
+                l.gxa = reduce_gxa(cnt, 256, 1024);
+            } else if (f == WG_SPLIT) {
+                l.kchunk = cdiv(cdiv(M, wgrad_splits(M, N[i], K[i])), GBK) * GBK;
+                l.gxa = reduce_gxa(cnt, 256, 1024);
+                fp_reserve += cdlrm_linear_bwd_work_bytes(M, N[i], K[i]);
+            } else {
+                l.kchunk = kchunk;
+                // (the short-batch step is bound by its launches and four to five slabs are little to sum: 1024 elements per
+                //  workgroup, at most 256 workgroups per layer.  None of the three grid widths has an A/B on record; they are
+                //  part of the launch sequence and stay as they are.)
+                l.gxa = reduce_gxa(cnt, 1024, 256);
+                fp_reserve += wgrad_carve(0, (int)cdiv(M, 4 * GBK) + 1, N[i], K[i], &cs);
+            }
+            l.zs = l.kchunk > 0 ? (int)cdiv(M, l.kchunk) : 1;
+            l.slabs = l.cs = 0;
+            if (l.zs > 1) {
+                l.slabs = p.high;
+                p.high = wgrad_carve(l.slabs, l.zs, N[i], K[i], &l.cs);
+            }
+        }
+    }
+    if (flags & CDLRM_GEMM_BF16) p.reserve = p.high + 256;
+    else p.reserve = fp_reserve;
+}
+
+extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes_ex(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K,
+                                                  int32_t flags) {
+    if (!N || !K) return 0;
+    WgradLayout p;
+    wgrad_layout(n_layers, M, N, K, flags & CDLRM_GEMM_BF16, nullptr, nullptr, nullptr, nullptr, p);
+    return p.reserve;
+}
+
+extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K) {
+    return cdlrm_mlp_wgrad_work_bytes_ex(n_layers, M, N, K, 0);
+}
+
 __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, const float* __restrict__ g, int64_t n, float lr);
 
 // the reductions of `jobs` (dW slabs + bias-gradient partials, the SGD step inside where a job carries parameters): one grouped
@@ -490,370 +623,167 @@ static void launch_reduce_jobs(const std::vector<ReduceJob>& jobs, hipStream_t s
     }
 }
 
-// the dense SGD step (W -= lr dW, b -= lr db) of the given layers, whose gradients needed no reduction pass to ride in
-static int sgd_layers(const std::vector<int>& layers, float* const* dW, float* const* db, float* const* P_w, float* const* P_b,
-                      const int32_t* N, const int32_t* K, float lr, hipStream_t s) {
-    for (int i : layers) {
-        const int64_t cnt = (int64_t)N[i] * K[i];
-        int64_t gx = cdiv(cnt, 256);
-        if (gx > 2048) gx = 2048;
-        hipLaunchKernelGGL(k_sgd, dim3((unsigned)gx), dim3(256), 0, s, P_w[i], (const float*)dW[i], cnt, lr);
-        if (db[i] && P_b && P_b[i])
-            hipLaunchKernelGGL(k_sgd, dim3((unsigned)cdiv(N[i], 256)), dim3(256), 0, s, P_b[i], (const float*)db[i], (int64_t)N[i], lr);
-    }
-    CDLRM_LAUNCH_CHECK();
-    return 0;
-}
-
-// P_w / P_b (both or neither): the layers' parameters, stepped by -lr * gradient in the reduction pass (layers whose
-// gradient needs no reduction: one elementwise launch behind it)
 static inline void route_set(cdlrm_gemm_route* out, int family, int tm, int tn, int mode, int aligned, int splits, int va, int vb,
                              int fast) {
     const GemmRec rec = {out, 0};
     gemm_record(&rec, family, tm, tn, mode, aligned, splits, va, vb, fast);
 }
 
-static int mlp_wgrad_impl(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
-                          const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
-                          const int32_t* K, void* work, void* stream, float* const* P_w, float* const* P_b, float lr,
-                          cdlrm_gemm_route* rout = nullptr, int n_cu = 0, int64_t extra_tiles = 0) {
-    CDLRM_REQUIRE(n_layers >= 0 && (n_layers == 0 || (X && ld_x && dZ && ld_dz && dW && db && N && K)) && M >= 1,
-                  "bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<char> stepped((size_t)(n_layers > 0 ? n_layers : 0), 0);
-    auto step_rest = [&]() -> int {             // layers the reduction did not cover
-        if (!P_w) return 0;
-        std::vector<int> rest;
-        for (int i = 0; i < n_layers; ++i)
-            if (!stepped[i]) rest.push_back(i);
-        return sgd_layers(rest, dW, db, P_w, P_b, N, K, lr, s);
-    };
-    if (M <= WGRAD_DIRECT_MAX_M) {
-        // Small batches, all layers at once.  Layers whose operands are 16-byte loadable go through the LDS-tiled
-        // kernel as ONE grouped launch, the contraction (the batch) cut into slabs so that the group has ~1000
-        // workgroups; the rest (13-wide input, 1-wide output) through the grouped LDS-free kernel with the same slabs;
-        // then ONE grouped reduction of all layers (fixed slab order).  
-        const int use_tiled = 1;
-        std::vector<GemmArgs> direct, tiled;
-        std::vector<int> direct_layer, tiled_layer;
-        int64_t tiles = 0;
-        for (int i = 0; i < n_layers; ++i) {
-            CDLRM_REQUIRE(X[i] && dZ[i] && dW[i] && N[i] >= 1 && K[i] >= 1 && ld_x[i] >= K[i] && ld_dz[i] >= N[i],
-                          "bad layer argument");
-            GemmArgs g = gemm_args();
-            g.A = dZ[i]; g.lda = ld_dz[i]; g.B = X[i]; g.ldb = ld_x[i]; g.C = dW[i]; g.ldc = K[i];
-            g.M = N[i]; g.N = K[i]; g.K = M; g.kchunk = M; g.colsum = db[i];
-            g.vecA = aligned16(dZ[i]) && ld_dz[i] % 4 == 0 && N[i] % 4 == 0;
-            g.vecB = aligned16(X[i]) && ld_x[i] % 4 == 0 && K[i] % 4 == 0;
-            if (use_tiled && g.vecA && g.vecB && M >= 256) {
-                tiled.push_back(g);
-                tiled_layer.push_back(i);
-                tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
-            } else {
-                direct.push_back(g);
-                direct_layer.push_back(i);
-            }
-        }
-        // one split count for the whole group (slabs of the batch); 1 = no slabs, no reduction
-        int64_t kchunk = M;
-        int zs = 1;
-        // (extra_tiles: 64x64 tiles of layers that share this call's slab count but are launched by the caller -- the bf16
-        //  layers of cdlrm_mlp_wgrad_ex, so that the fp32 layers beside them get the slabs they get in an all-fp32 call)
-        tiles += extra_tiles;
-        if (tiles > 0) {
-            // workgroups the grouped launch aims at (slabs = target / tiles).  1024 until round 4 (7 slabs for the top MLP's 160
-            // tiles); measured in the step, five rounds each: per-rank batch 1024 -- 384 / 640 / 768 / 896 / 1024 / 1536 ->
-            // 0.1802 / 0.1814 / 0.1797 / 0.1813 / 0.1856 / 0.1851 ms; 2048 -- 256 / 384 / 512 / 640 / 768 / 1024 / 2048 ->
-            // 0.2495 / 0.2489 / 0.2372 / 0.2367 / 0.2404 / 0.2416 / 0.2405: four to five slabs, not seven (fewer partial
-            // slabs to write and reduce; three is too few workgroups at 2048)
-            const int64_t target_wgs = M <= 1024 ? 768 : 640;
-            int64_t splits = cdiv(target_wgs, tiles);
-            const int64_t smax = cdiv(M, 4 * GBK);
-            if (splits > smax) splits = smax;
-            if (splits < 1) splits = 1;
-            kchunk = cdiv(cdiv(M, splits), GBK) * GBK;
-            zs = (int)cdiv(M, kchunk);
-        }
-        if (rout) {     // the route query (cdlrm_mlp_wgrad_route): one entry per layer, nothing launched
-            for (size_t q = 0; q < tiled.size(); ++q)
-                route_set(&rout[tiled_layer[q]], CDLRM_ROUTE_GEMM, 1, 1, 0, 0, zs, 1, 1, 0);
-            for (size_t q = 0; q < direct.size(); ++q)
-                route_set(&rout[direct_layer[q]], CDLRM_ROUTE_DIRECT, 0, 0, 0, 0, zs, direct[q].vecA, direct[q].vecB, 0);
-            return 0;
-        }
-        CDLRM_REQUIRE(zs == 1 || (work && ((uintptr_t)work & 255) == 0), "work must be 256-byte aligned");
-        char* wp = (char*)work;
-        std::vector<ReduceJob> jobs;
-        auto slabbed = [&](GemmArgs& g, int li) {          // redirect one problem's outputs to its slabs
-            const int64_t cnt = (int64_t)N[li] * K[li];
-            g.kchunk = kchunk;
-            g.slab = cnt;
-            if (zs == 1) return;
-            float* slabs = (float*)wp;
-            wp += (((uint64_t)zs * cnt * 4) + 255) & ~(uint64_t)255;
-            float* cs = (float*)wp;
-            wp += (((uint64_t)zs * N[li] * 4) + 255) & ~(uint64_t)255;
-            g.C = slabs;
-            g.colsum = db[li] ? cs : nullptr;
-            ReduceJob r;
-            r.partA = slabs; r.countA = cnt; r.outA = dW[li];
-            int64_t gxa = cdiv(cnt, 1024);
-            if (gxa > 256) gxa = 256;
-            r.gxa = (int)gxa;
-            r.partB = cs; r.countB = db[li] ? N[li] : 0; r.outB = db[li];
-            r.splits = zs;
-            r.novec = g_cdlrm_debug[2];
-            r.pA = P_w ? P_w[li] : nullptr; r.pB = (P_w && P_b && db[li]) ? P_b[li] : nullptr; r.lr = lr;
-            if (P_w) stepped[li] = 1;
-            jobs.push_back(r);
-        };
-        for (size_t q = 0; q < direct.size(); ++q) slabbed(direct[q], direct_layer[q]);
-        for (size_t q = 0; q < tiled.size(); ++q) slabbed(tiled[q], tiled_layer[q]);
-        bool direct_done = direct.empty();
-        for (size_t q0 = 0; q0 < tiled.size(); q0 += GEMM_GROUP_MAX) {
-            GemmGroup grp;
-            memset(&grp, 0, sizeof(grp));
-            unsigned blocks = 0;
-            for (size_t q = q0; q < tiled.size() && q < q0 + GEMM_GROUP_MAX; ++q) {
-                grp.first[grp.n] = blocks;
-                grp.g[grp.n] = tiled[q];
-                blocks += (unsigned)(cdiv(tiled[q].M, 64) * cdiv(tiled[q].N, 64) * zs);
-                grp.n++;
-            }
-            grp.first[grp.n] = blocks;
-            // the LDS-free layers ride in front of the first tiled group's launch where the combination allows (one launch less
-            // per sub-network on a launch-bound step: 0.2008 -> 0.1963 ms at a local batch of 1024, 0.2955 -> 0.2883 at 2048)
-            if (!direct_done && launch_wgrad_mixed(direct.data(), (int)direct.size(), grp, blocks, s)) {
-                direct_done = true;
-                continue;
-            }
-            hipLaunchKernelGGL((k_gemm_group<false, false, true, true>), dim3(blocks), dim3(256), 0, s, grp);
-        }
-        if (!direct_done) {
-            int rc = launch_wgrad_group(direct.data(), (int)direct.size(), s);
-            if (rc) return rc;
-        }
-        launch_reduce_jobs(jobs, s);
-        CDLRM_LAUNCH_CHECK();
-        return step_rest();
-    }
-    // Long batches: per layer one split-M GEMM of the tiled (or, for degenerate shapes, the LDS-free) kernel into the
-    // layer's own slabs, then ONE grouped reduction of all layers' slabs and bias partials.
-    CDLRM_REQUIRE(rout || (work && ((uintptr_t)work & 255) == 0), "work must be 256-byte aligned");
-    char* wp = (char*)work;
-    std::vector<ReduceJob> jobs;
-    for (int i = 0; i < n_layers; ++i) {
-        CDLRM_REQUIRE(X[i] && dZ[i] && dW[i] && N[i] >= 1 && K[i] >= 1 && ld_x[i] >= K[i] && ld_dz[i] >= N[i],
-                      "bad layer argument");
-        const int splits = wgrad_splits(M, N[i], K[i]);
-        const int64_t cnt = (int64_t)N[i] * K[i];
-        GemmArgs g = gemm_args();
-        g.A = dZ[i]; g.lda = ld_dz[i]; g.B = X[i]; g.ldb = ld_x[i]; g.ldc = K[i];
-        g.slab = cnt;
-        g.M = N[i]; g.N = K[i]; g.K = M; g.kchunk = cdiv(cdiv(M, splits), GBK) * GBK;
-        g.vecA = aligned16(dZ[i]) && ld_dz[i] % 4 == 0 && N[i] % 4 == 0;
-        g.vecB = aligned16(X[i]) && ld_x[i] % 4 == 0 && K[i] % 4 == 0;
-        const int zs = (int)cdiv(M, g.kchunk);
-        g.C = dW[i];
-        g.colsum = db[i];
-        if (rout) {
-            const GemmRec rec = {&rout[i], n_cu};
-            (void)launch_gemm<false, false>(g, zs, s, &rec);
-            continue;
-        }
-        if (zs > 1) {
-            float* slabs = (float*)wp;
-            wp += (((uint64_t)zs * cnt * 4) + 255) & ~(uint64_t)255;
-            float* cs = (float*)wp;
-            wp += (((uint64_t)zs * N[i] * 4) + 255) & ~(uint64_t)255;
-            g.C = slabs;
-            g.colsum = db[i] ? cs : nullptr;
-            ReduceJob r;
-            r.partA = slabs; r.countA = cnt; r.outA = dW[i];
-            int64_t gxa = cdiv(cnt, 256);
-            if (gxa > 1024) gxa = 1024;
-            r.gxa = (int)gxa;
-            r.partB = cs; r.countB = db[i] ? N[i] : 0; r.outB = db[i];
-            r.splits = zs;
-            r.novec = g_cdlrm_debug[2];
-            r.pA = P_w ? P_w[i] : nullptr; r.pB = (P_w && P_b && db[i]) ? P_b[i] : nullptr; r.lr = lr;
-            if (P_w) stepped[i] = 1;
-            jobs.push_back(r);
-        }
-        int rc = launch_gemm<false, false>(g, zs, s);
-        if (rc) return rc;
-    }
-    if (rout) return 0;
-    launch_reduce_jobs(jobs, s);
-    CDLRM_LAUNCH_CHECK();
-    return step_rest();
-}
-
-extern "C" int cdlrm_mlp_wgrad(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
-                               const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
-                               const int32_t* K, void* work, void* stream) {
-    return mlp_wgrad_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, work, stream, nullptr, nullptr, 0.f);
-}
-
-// cdlrm_mlp_wgrad followed by the dense SGD step of the same layers (W[i] -= lr * dW[i], b[i] -= lr * db[i]:
-// optimizer_mlps.step(), main_no_ddp.py:415) in the same launches -- for callers with nothing between the two (one rank: no
-// gradient exchange).  Same arithmetic as cdlrm_mlp_wgrad + cdlrm_sgd_step.
-extern "C" int cdlrm_mlp_wgrad_sgd(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
-                                   const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W,
-                                   float* const* b, float lr, int64_t M, const int32_t* N, const int32_t* K, void* work,
-                                   void* stream) {
-    CDLRM_REQUIRE(n_layers == 0 || (W && b), "parameters missing");
-    return mlp_wgrad_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, work, stream, W, b, lr);
-}
-
-// ---- the bf16 mode of the weight gradients (flags & CDLRM_GEMM_BF16; gemm_bf16.h) --------------------------------------------
-// The layers the shape rule admits (bf16_layer_ok) leave the fp32 plan: one grouped bf16 launch of all of them on 64x64 tiles,
-// one slab length for the group (bf16_wgrad_kchunk), then one grouped reduction of their slabs (k_reduce_group, with the SGD step
-// when asked).  The other layers (the 13-wide input, the 1-wide head) go through the fp32 plan above, unchanged, in front --
-// with the front part of `work`; the bf16 slabs follow it.
-struct Bf16Wgrad {
-    std::vector<int> fp, bf;         // layer indices: fp32 plan, bf16 group
-    int64_t kchunk = 0;              // slab length of the bf16 group
-    int zs = 1;                      // slab count of the bf16 group
-    uint64_t fp_bytes = 0;           // the fp32 plan's work bytes (offset of the bf16 slabs)
-};
-
-static void bf16_wgrad_plan(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K, Bf16Wgrad& p) {
-    int64_t tiles = 0;
-    for (int i = 0; i < n_layers; ++i) {
-        if (bf16_layer_ok(N[i], K[i])) {
-            p.bf.push_back(i);
-            tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
-        } else {
-            p.fp.push_back(i);
-        }
-    }
-    p.kchunk = bf16_wgrad_kchunk(M, tiles, INT64_MAX);
-    p.zs = (int)cdiv(M, p.kchunk);
-    if (!p.fp.empty()) {
-        std::vector<int32_t> n, k;
-        for (int i : p.fp) { n.push_back(N[i]); k.push_back(K[i]); }
-        p.fp_bytes = cdlrm_mlp_wgrad_work_bytes((int32_t)p.fp.size(), M, n.data(), k.data());
-    }
-}
-
-extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes_ex(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K,
-                                                  int32_t flags) {
-    if (!(flags & CDLRM_GEMM_BF16)) return cdlrm_mlp_wgrad_work_bytes(n_layers, M, N, K);
-    if (!N || !K) return 0;
-    Bf16Wgrad p;
-    bf16_wgrad_plan(n_layers, M, N, K, p);
-    uint64_t total = p.fp_bytes + 256;
-    if (p.zs > 1)
-        for (int i : p.bf)
-            total += (((uint64_t)p.zs * N[i] * K[i] * 4 + 255) & ~(uint64_t)255) + (((uint64_t)p.zs * N[i] * 4 + 255) & ~(uint64_t)255);
-    return total;
-}
-
-// rout != nullptr: the route query (one entry per layer), nothing launched
-static int mlp_wgrad_ex_impl(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
-                             const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
-                             const int32_t* K, int32_t flags, void* work, void* stream, float* const* P_w, float* const* P_b,
-                             float lr, cdlrm_gemm_route* rout, int n_cu) {
+// All of cdlrm_mlp_wgrad*: build the layout, then either translate it into routes (rout: the route query, one entry per layer,
+// nothing launched, no pointer read) or walk it and launch.  P_w / P_b (both or neither): the layers' parameters, stepped by
+// -lr * gradient in the reduction pass (layers whose gradient needs no reduction: one elementwise launch behind it).
+static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                         const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
+                         const int32_t* K, int32_t flags, void* work, void* stream, float* const* P_w, float* const* P_b, float lr,
+                         cdlrm_gemm_route* rout, int n_cu) {
     CDLRM_REQUIRE((flags & ~CDLRM_GEMM_BF16) == 0, "bad flags");
-    if (!(flags & CDLRM_GEMM_BF16))
-        return mlp_wgrad_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, work, stream, P_w, P_b, lr, rout, n_cu);
     CDLRM_REQUIRE(n_layers >= 0 && (n_layers == 0 || (X && ld_x && dZ && ld_dz && dW && db && N && K)) && M >= 1,
                   "bad argument");
-    CDLRM_REQUIRE(rout || (work && ((uintptr_t)work & 255) == 0), "work must be 256-byte aligned");
     for (int i = 0; i < n_layers; ++i)
         CDLRM_REQUIRE(X[i] && dZ[i] && dW[i] && N[i] >= 1 && K[i] >= 1 && ld_x[i] >= K[i] && ld_dz[i] >= N[i],
                       "bad layer argument");
     hipStream_t s = (hipStream_t)stream;
-    Bf16Wgrad p;
-    bf16_wgrad_plan(n_layers, M, N, K, p);
-    if (!p.fp.empty()) {        // the fp32 layers: the fp32 plan of just those layers, with the slab count of the whole call
-        int64_t extra_tiles = 0;        // the bf16 layers the fp32 plan would have put on its tiled kernel (same test)
-        for (int i : p.bf) {
-            const bool va = aligned16(dZ[i]) && ld_dz[i] % 4 == 0 && N[i] % 4 == 0;
-            const bool vb = aligned16(X[i]) && ld_x[i] % 4 == 0 && K[i] % 4 == 0;
-            if (va && vb && M >= 256) extra_tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
-        }
-        const size_t nf = p.fp.size();
-        std::vector<const float*> fx(nf), fdz(nf);
-        std::vector<float*> fdw(nf), fdb(nf), fpw(nf), fpb(nf);
-        std::vector<int64_t> fldx(nf), flddz(nf);
-        std::vector<int32_t> fn(nf), fk(nf);
-        std::vector<cdlrm_gemm_route> fr(nf);
-        for (size_t q = 0; q < nf; ++q) {
-            const int i = p.fp[q];
-            fx[q] = X[i]; fdz[q] = dZ[i]; fdw[q] = dW[i]; fdb[q] = db[i]; fldx[q] = ld_x[i]; flddz[q] = ld_dz[i];
-            fn[q] = N[i]; fk[q] = K[i];
-            fpw[q] = P_w ? P_w[i] : nullptr; fpb[q] = (P_w && P_b) ? P_b[i] : nullptr;
-        }
-        memset(fr.data(), 0, nf * sizeof(cdlrm_gemm_route));
-        int rc = mlp_wgrad_impl((int32_t)nf, fx.data(), fldx.data(), fdz.data(), flddz.data(), fdw.data(), fdb.data(), M, fn.data(),
-                                fk.data(), work, stream, P_w ? fpw.data() : nullptr, P_w ? fpb.data() : nullptr, lr,
-                                rout ? fr.data() : nullptr, n_cu, extra_tiles);
-        if (rc) return rc;
-        if (rout)
-            for (size_t q = 0; q < nf; ++q) rout[p.fp[q]] = fr[q];
-    }
-    if (p.bf.empty()) return 0;
-    std::vector<GemmArgs> probs;
-    std::vector<ReduceJob> jobs;
-    char* wp = (char*)work + p.fp_bytes;
-    int va = 1, vb = 1;
-    for (int i : p.bf) {
-        const int64_t cnt = (int64_t)N[i] * K[i];
+    WgradLayout p;
+    wgrad_layout(n_layers, M, N, K, flags, X, ld_x, dZ, ld_dz, p);
+    // the GEMM of layer i as the layout has it, writing dW / db (un-split) ...
+    auto problem = [&](int i) {
+        const WgradLayer& l = p.L[i];
         GemmArgs g = gemm_args();
-        g.A = dZ[i]; g.lda = ld_dz[i]; g.B = X[i]; g.ldb = ld_x[i]; g.ldc = K[i];
-        g.slab = cnt;
-        g.M = N[i]; g.N = K[i]; g.K = M; g.kchunk = p.kchunk;
-        g.vecA = bf16_vec<false>(dZ[i], ld_dz[i], N[i], M);
-        g.vecB = bf16_vec<false>(X[i], ld_x[i], K[i], M);
-        va &= g.vecA; vb &= g.vecB;
-        g.C = dW[i];
-        g.colsum = db[i];
-        if (p.zs > 1) {
-            float* slabs = (float*)wp;
-            wp += (((uint64_t)p.zs * cnt * 4) + 255) & ~(uint64_t)255;
-            float* cs = (float*)wp;
-            wp += (((uint64_t)p.zs * N[i] * 4) + 255) & ~(uint64_t)255;
-            g.C = slabs;
-            g.colsum = db[i] ? cs : nullptr;
-            ReduceJob r;
-            r.partA = slabs; r.countA = cnt; r.outA = dW[i];
-            int64_t gxa = cdiv(cnt, 256);
-            if (gxa > 1024) gxa = 1024;
-            r.gxa = (int)gxa;
-            r.partB = cs; r.countB = db[i] ? N[i] : 0; r.outB = db[i];
-            r.splits = p.zs;
-            r.novec = g_cdlrm_debug[2];
-            r.pA = P_w ? P_w[i] : nullptr; r.pB = (P_w && P_b && db[i]) ? P_b[i] : nullptr; r.lr = lr;
-            jobs.push_back(r);
-        }
-        probs.push_back(g);
-    }
+        g.A = dZ[i]; g.lda = ld_dz[i]; g.B = X[i]; g.ldb = ld_x[i]; g.C = dW[i]; g.ldc = K[i];
+        g.slab = (int64_t)N[i] * K[i];
+        g.M = N[i]; g.N = K[i]; g.K = M; g.kchunk = l.kchunk; g.colsum = db[i];
+        g.vecA = l.vecA; g.vecB = l.vecB;
+        return g;
+    };
     if (rout) {
-        for (int i : p.bf) route_set(&rout[i], CDLRM_ROUTE_BF16, 1, 1, 0, 0, p.zs, va, vb, 0);
+        for (int i = 0; i < n_layers; ++i) {
+            const WgradLayer& l = p.L[i];
+            if (l.family == WG_TILED) route_set(&rout[i], CDLRM_ROUTE_GEMM, 1, 1, 0, 0, l.zs, 1, 1, 0);
+            else if (l.family == WG_DIRECT) route_set(&rout[i], CDLRM_ROUTE_DIRECT, 0, 0, 0, 0, l.zs, l.vecA, l.vecB, 0);
+            else if (l.family == WG_BF16) route_set(&rout[i], CDLRM_ROUTE_BF16, 1, 1, 0, 0, l.zs, p.bf_vecA, p.bf_vecB, 0);
+            else {      // the kernel and its tile are launch_gemm's choice
+                const GemmRec rec = {&rout[i], n_cu};
+                (void)launch_gemm<false, false>(problem(i), l.zs, s, &rec);
+            }
+        }
         return 0;
     }
-    int rc = launch_wgrad_bf16(probs.data(), (int)probs.size(), va, vb, s);
+    // (a short fp32 call without slabs never touches `work`)
+    CDLRM_REQUIRE((!flags && M <= WGRAD_DIRECT_MAX_M && p.high == 0) || (work && ((uintptr_t)work & 255) == 0),
+                  "work must be 256-byte aligned");
+    std::vector<GemmArgs> probs;
+    std::vector<ReduceJob> jobs;
+    probs.reserve(p.L.size());
+    jobs.reserve(p.L.size());
+    // ... and into its slabs, with their reduction queued in `jobs`, where it has any
+    auto stage = [&](int f) {
+        for (int i = 0; i < n_layers; ++i) {
+            const WgradLayer& l = p.L[i];
+            if (l.family != f) continue;
+            probs.push_back(problem(i));
+            if (l.zs > 1)
+                jobs.push_back(wgrad_slabbed(probs.back(), work, l.slabs, l.cs, l.zs, l.gxa, dW[i], db[i], P_w ? P_w[i] : nullptr,
+                                             (P_w && P_b) ? P_b[i] : nullptr, lr));
+        }
+    };
+    // the reductions queued so far; then the dense SGD step (W -= lr dW, b -= lr db) of the layers of these families that had no
+    // reduction pass to ride in
+    auto finish = [&](bool bf) -> int {
+        launch_reduce_jobs(jobs, s);
+        jobs.clear();
+        for (int i = 0; P_w && i < n_layers; ++i) {
+            if ((p.L[i].family == WG_BF16) != bf || p.L[i].zs > 1) continue;
+            const int64_t cnt = (int64_t)N[i] * K[i];
+            int64_t gx = cdiv(cnt, 256);
+            if (gx > 2048) gx = 2048;
+            hipLaunchKernelGGL(k_sgd, dim3((unsigned)gx), dim3(256), 0, s, P_w[i], (const float*)dW[i], cnt, lr);
+            if (db[i] && P_b && P_b[i])
+                hipLaunchKernelGGL(k_sgd, dim3((unsigned)cdiv(N[i], 256)), dim3(256), 0, s, P_b[i], (const float*)db[i], (int64_t)N[i], lr);
+        }
+        CDLRM_LAUNCH_CHECK();
+        return 0;
+    };
+    if (p.n_bf < n_layers || !flags) {
+        if (M <= WGRAD_DIRECT_MAX_M) {
+            stage(WG_DIRECT);
+            const size_t nd = probs.size();
+            stage(WG_TILED);
+            const GemmArgs* direct = probs.data();
+            const GemmArgs* tiled = probs.data() + nd;
+            const size_t nt = probs.size() - nd;
+            bool direct_done = nd == 0;
+            for (size_t q0 = 0; q0 < nt; q0 += GEMM_GROUP_MAX) {
+                GemmGroup grp;
+                memset(&grp, 0, sizeof(grp));
+                unsigned blocks = 0;
+                for (size_t q = q0; q < nt && q < q0 + GEMM_GROUP_MAX; ++q) {
+                    grp.first[grp.n] = blocks;
+                    grp.g[grp.n] = tiled[q];
+                    blocks += (unsigned)(cdiv(tiled[q].M, 64) * cdiv(tiled[q].N, 64) * cdiv(M, tiled[q].kchunk));
+                    grp.n++;
+                }
+                grp.first[grp.n] = blocks;
+                // the LDS-free layers ride in front of the first tiled group's launch where the combination allows (one launch less
+                // per sub-network on a launch-bound step: 0.2008 -> 0.1963 ms at a local batch of 1024, 0.2955 -> 0.2883 at 2048)
+                if (!direct_done && launch_wgrad_mixed(direct, (int)nd, grp, blocks, s)) {
+                    direct_done = true;
+                    continue;
+                }
+                hipLaunchKernelGGL((k_gemm_group<false, false, true, true>), dim3(blocks), dim3(256), 0, s, grp);
+            }
+            if (!direct_done) {
+                int rc = launch_wgrad_group(direct, (int)nd, s);
+                if (rc) return rc;
+            }
+        } else {
+            stage(WG_SPLIT);
+            size_t q = 0;
+            for (int i = 0; i < n_layers; ++i) {
+                if (p.L[i].family != WG_SPLIT) continue;
+                int rc = launch_gemm<false, false>(probs[q++], p.L[i].zs, s);
+                if (rc) return rc;
+            }
+        }
+        int rc = finish(false);
+        if (rc) return rc;
+    }
+    if (p.n_bf == 0) return 0;
+    probs.clear();
+    stage(WG_BF16);
+    int rc = launch_wgrad_bf16(probs.data(), (int)probs.size(), p.bf_vecA, p.bf_vecB, s);
     if (rc) return rc;
-    launch_reduce_jobs(jobs, s);
-    if (P_w && p.zs == 1) return sgd_layers(p.bf, dW, db, P_w, P_b, N, K, lr, s);     // un-split: no reduction pass to ride in
-    CDLRM_LAUNCH_CHECK();
-    return 0;
+    return finish(true);
 }
 
 extern "C" int cdlrm_mlp_wgrad_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
                                   const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
                                   const int32_t* K, int32_t flags, void* work, void* stream) {
-    return mlp_wgrad_ex_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, nullptr, nullptr, 0.f, nullptr, 0);
+    return mlp_wgrad_run(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, nullptr, nullptr, 0.f, nullptr, 0);
 }
 
+// cdlrm_mlp_wgrad_ex followed by the dense SGD step of the same layers (W[i] -= lr * dW[i], b[i] -= lr * db[i]:
+// optimizer_mlps.step(), main_no_ddp.py:415) in the same launches -- for callers with nothing between the two (one rank: no
+// gradient exchange).  Same arithmetic as cdlrm_mlp_wgrad_ex + cdlrm_sgd_step.
 extern "C" int cdlrm_mlp_wgrad_sgd_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
                                       const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W,
                                       float* const* b, float lr, int64_t M, const int32_t* N, const int32_t* K, int32_t flags,
                                       void* work, void* stream) {
     CDLRM_REQUIRE(n_layers == 0 || (W && b), "parameters missing");
-    return mlp_wgrad_ex_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, W, b, lr, nullptr, 0);
+    return mlp_wgrad_run(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, W, b, lr, nullptr, 0);
+}
+
+// flags = 0
+extern "C" int cdlrm_mlp_wgrad(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                               const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
+                               const int32_t* K, void* work, void* stream) {
+    return cdlrm_mlp_wgrad_ex(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, 0, work, stream);
+}
+
+extern "C" int cdlrm_mlp_wgrad_sgd(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                                   const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W,
+                                   float* const* b, float lr, int64_t M, const int32_t* N, const int32_t* K, void* work,
+                                   void* stream) {
+    return cdlrm_mlp_wgrad_sgd_ex(n_layers, X, ld_x, dZ, ld_dz, dW, db, W, b, lr, M, N, K, 0, work, stream);
 }
 
 extern "C" int cdlrm_mlp_wgrad_route(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
@@ -861,8 +791,7 @@ extern "C" int cdlrm_mlp_wgrad_route(int32_t n_layers, const float* const* X, co
                                      const int32_t* K, int32_t flags, int32_t n_cu, cdlrm_gemm_route* out) {
     CDLRM_REQUIRE(out && n_cu >= 1 && n_layers >= 0, "bad argument");
     memset(out, 0, (size_t)n_layers * sizeof(*out));
-    return mlp_wgrad_ex_impl(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, nullptr, nullptr, nullptr, nullptr, 0.f, out,
-                             n_cu);
+    return mlp_wgrad_run(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, nullptr, nullptr, nullptr, nullptr, 0.f, out, n_cu);
 }
 
 // =================================================================================================

@@ -1111,28 +1111,41 @@ class TrainEngine:
 
     def _wplans(self, buf):
         """(whole-network plan, (bottom plan, top plan) or None) of the weight gradients at the current matmul precision: the
-        fp32 plans of _buffers, or bf16 plans with their own scratch, built on first use (the whole-network one only where
-        the step has no split plans: it is None otherwise)."""
-        if self.matmul_precision == "fp32":
-            return buf["wgrad"], buf["wgrad_split"]
-        self._mm(self.bot[0][0])            # validates the attribute
-        if "wgrad_bf16" not in buf:
-            xs, dzs, layers, B, dev = buf["wgrad_args"]
-            gw = [self.gW[l] for l in layers]
-            gb = [self.gb[l] for l in layers]
-            wk = lambda ls: ops.mlp_wgrad_work(B, [l.out_features for l in ls], [self.W[l].shape[1] for l in ls], dev,
-                                               precision="bf16")
-            whole, split = None, None
-            if buf["wgrad_split"] is None:
-                whole = ops.WgradPlan(xs, dzs, gw, gb, wk(layers), precision="bf16")
-            else:
-                nb = len(self.bot)
-                split = (ops.WgradPlan(xs[:nb], dzs[:nb], gw[:nb], gb[:nb], wk(layers[:nb]), precision="bf16"),
-                         ops.WgradPlan(xs[nb:], dzs[nb:], gw[nb:], gb[nb:], wk(layers[nb:]), precision="bf16"))
-                split[0].set_params([self.W[l] for l in layers[:nb]], [l.bias.data for l in layers[:nb]])
-                split[1].set_params([self.W[l] for l in layers[nb:]], [l.bias.data for l in layers[nb:]])
-            buf["wgrad_bf16"] = (whole, split)
-        return buf["wgrad_bf16"]
+        fp32 plans of _buffers, or bf16 plans built on first use."""
+        if self.matmul_precision != "fp32":
+            self._mm(self.bot[0][0])            # validates the attribute
+        key = "wgrad_" + self.matmul_precision
+        if key not in buf:
+            buf[key] = self._build_wplans(buf, self.matmul_precision)
+        return buf[key]
+
+    def _build_wplans(self, buf, precision):
+        """(whole, split) for _wplans.  split: (bottom plan, top plan), each with scratch of its own and the layers' parameters
+        set, where the step takes the two sub-networks' weight gradients apart -- None otherwise.  whole: all layers in one call;
+        in fp32 on the scratch the layers' backward calls use (lin_work), in bf16 on scratch of its own and therefore only where
+        the step has no split plans (None otherwise)."""
+        xs, dzs, layers, B, split = buf["wgrad_args"]
+        gw = [self.gW[l] for l in layers]
+        gb = [self.gb[l] for l in layers]
+        kw = {} if precision == "fp32" else {"precision": precision}       # (fp32: the calls stay what they were, as _mm)
+
+        def plan(lo, hi, work=None):
+            ls = layers[lo:hi]
+            if work is None:
+                work = ops.mlp_wgrad_work(B, [l.out_features for l in ls], [self.W[l].shape[1] for l in ls], self.dev, **kw)
+            return ops.WgradPlan(xs[lo:hi], dzs[lo:hi], gw[lo:hi], gb[lo:hi], work, **kw)
+
+        fp32 = precision == "fp32"
+        whole = plan(0, len(layers), buf["lin_work"] if fp32 else None) if fp32 or not split else None
+        if not split:
+            return whole, None
+        nb = len(self.bot)
+        parts = (plan(0, nb), plan(nb, len(layers)))
+        # one rank: nothing sits between a sub-network's weight gradients and its SGD step, so the step rides in the
+        # gradients' reduction pass (cdlrm_mlp_wgrad_sgd) -- one launch less per sub-network and step
+        parts[0].set_params([self.W[l] for l in layers[:nb]], [l.bias.data for l in layers[:nb]])
+        parts[1].set_params([self.W[l] for l in layers[nb:]], [l.bias.data for l in layers[nb:]])
+        return whole, parts
 
     def _buffers(self, B):
         if B in self._bufs:
@@ -1176,22 +1189,11 @@ class TrainEngine:
         x0 = torch.empty(B, self.W[layers[0]].shape[1], dtype=f32, device=dev)   # stand-in: re-pointed at X every step
         xs = [x0] + b["bot_y"] + [b["R"]] + b["top_y"][:-1]
         dzs = b["bot_dy"] + [b["dfeat"][:, 0, :]] + b["top_dy"]
-        b["wgrad"] = ops.WgradPlan(xs, dzs, [self.gW[l] for l in layers], [self.gb[l] for l in layers], b["lin_work"])
-        b["wgrad_args"] = (xs, dzs, layers, B, dev)       # for the bf16 plans (_wplans)
         # long local batches: the top MLP's weight gradients run on their own stream beside the interaction backward
-        # and the bottom MLP's backward -- (bottom plan, top plan), each with its own scratch
-        b["wgrad_split"] = None
-        if self.defer_top or (S.is_hip(dev) and B >= self.split_wgrad_min):
-            nb = len(self.bot)
-            gw = [self.gW[l] for l in layers]
-            gb = [self.gb[l] for l in layers]
-            wk = lambda ls: ops.mlp_wgrad_work(B, [l.out_features for l in ls], [self.W[l].shape[1] for l in ls], dev)
-            b["wgrad_split"] = (ops.WgradPlan(xs[:nb], dzs[:nb], gw[:nb], gb[:nb], wk(layers[:nb])),
-                                ops.WgradPlan(xs[nb:], dzs[nb:], gw[nb:], gb[nb:], wk(layers[nb:])))
-            # one rank: nothing sits between a sub-network's weight gradients and its SGD step, so the step rides in the
-            # gradients' reduction pass (cdlrm_mlp_wgrad_sgd) -- one launch less per sub-network and step
-            b["wgrad_split"][0].set_params([self.W[l] for l in layers[:nb]], [l.bias.data for l in layers[:nb]])
-            b["wgrad_split"][1].set_params([self.W[l] for l in layers[nb:]], [l.bias.data for l in layers[nb:]])
+        # and the bottom MLP's backward -- (bottom plan, top plan) instead of one plan of all layers
+        split = bool(self.defer_top or (S.is_hip(dev) and B >= self.split_wgrad_min))
+        b["wgrad_args"] = (xs, dzs, layers, B, split)
+        b["wgrad_fp32"] = self._build_wplans(b, "fp32")
         self._bufs[B] = b
         return b
 

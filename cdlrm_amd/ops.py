@@ -641,8 +641,6 @@ def _wgrad_work_bytes(M: int, Ns, Ks, precision: str) -> int:
     n = len(Ns)
     NA = C.c_int32 * n
     N, K = NA(*[int(x) for x in Ns]), NA(*[int(x) for x in Ks])
-    if precision == "fp32":
-        return int(_lib.lib().cdlrm_mlp_wgrad_work_bytes(n, int(M), N, K))
     return int(_lib.lib().cdlrm_mlp_wgrad_work_bytes_ex(n, int(M), N, K, PRECISIONS[precision]))
 
 
@@ -704,23 +702,14 @@ class WgradPlan:
 def mlp_wgrad(plan: WgradPlan, stream=None, lr: Optional[float] = None):
     """dW[i] = dZ[i]^T X[i], db[i] = column sums of dZ[i] for every layer of the plan (one grouped launch at small M).
     lr given (and plan.set_params called): W[i] -= lr * dW[i], b[i] -= lr * db[i] in the same launches."""
-    if plan.precision != "fp32":
-        flags = PRECISIONS[plan.precision]
-        if lr is None:
-            check(_lib.lib().cdlrm_mlp_wgrad_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.M, plan.N,
-                                                plan.K, flags, plan.work.data_ptr(), stream_ptr(stream)))
-        else:
-            check(_lib.lib().cdlrm_mlp_wgrad_sgd_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
-                                                    plan.P_b, float(lr), plan.M, plan.N, plan.K, flags, plan.work.data_ptr(),
-                                                    stream_ptr(stream)))
-        return
+    flags = PRECISIONS[plan.precision]          # 0: exactly cdlrm_mlp_wgrad / cdlrm_mlp_wgrad_sgd
     if lr is None:
-        check(_lib.lib().cdlrm_mlp_wgrad(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.M, plan.N,
-                                         plan.K, plan.work.data_ptr(), stream_ptr(stream)))
+        check(_lib.lib().cdlrm_mlp_wgrad_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.M, plan.N,
+                                            plan.K, flags, plan.work.data_ptr(), stream_ptr(stream)))
     else:
-        check(_lib.lib().cdlrm_mlp_wgrad_sgd(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
-                                             plan.P_b, float(lr), plan.M, plan.N, plan.K, plan.work.data_ptr(),
-                                             stream_ptr(stream)))
+        check(_lib.lib().cdlrm_mlp_wgrad_sgd_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
+                                                plan.P_b, float(lr), plan.M, plan.N, plan.K, flags, plan.work.data_ptr(),
+                                                stream_ptr(stream)))
 
 
 def mlp_wgrad_route(plan: WgradPlan, n_cu: int = 256, precision: Optional[str] = None) -> list:

@@ -889,6 +889,27 @@ def test_mlp_wgrad_with_fused_sgd_step(ops, M):
             assert torch.equal(dbs[i], gb[i])
             ops.sgd_step(b0[i], dbs[i], lr)
             assert torch.equal(b0[i], bs[i]), i
+    # ops.mlp_wgrad goes through the flags-word entry points; the plain exports called directly give the same bits
+    from cdlrm_amd import _lib
+    st = ops.stream_ptr(None)
+    W1, b1 = [w.clone() for w in Ws], [None if b is None else b.clone() for b in bs]
+    ops.mlp_wgrad(plan, lr=lr)                           # (a second step, from the parameters after the first)
+    want = [t.clone() for t in dWs + [b for b in dbs if b is not None] + Ws + [b for b in bs if b is not None]]
+    for t in dWs + [b for b in dbs if b is not None]:
+        t.fill_(float("nan"))
+    p = plan
+    _lib.check(_lib.lib().cdlrm_mlp_wgrad(p.n, p.X, p.ld_x, p.dZ, p.ld_dz, p.dW, p.db, p.M, p.N, p.K, p.work.data_ptr(), st))
+    for t, w in zip(dWs + [b for b in dbs if b is not None], want):
+        assert torch.equal(t, w)
+    for w, w1 in zip(Ws, W1):
+        w.copy_(w1)
+    for b, b_1 in zip(bs, b1):
+        if b is not None:
+            b.copy_(b_1)
+    _lib.check(_lib.lib().cdlrm_mlp_wgrad_sgd(p.n, p.X, p.ld_x, p.dZ, p.ld_dz, p.dW, p.db, p.P_w, p.P_b, lr, p.M, p.N, p.K,
+                                              p.work.data_ptr(), st))
+    for t, w in zip(dWs + [b for b in dbs if b is not None] + Ws + [b for b in bs if b is not None], want):
+        assert torch.equal(t, w)
 
 
 def test_qr_embedding_bag_golden(ops, golden):
