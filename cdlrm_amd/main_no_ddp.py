@@ -132,7 +132,7 @@ def ProcessArgs(argv=None):
     parser.add_argument("--day-file-loader", type=str, default="host", choices=["host", "device"],
                         help="--data-generation=dataset: `host` = the reference's per-batch host loader; `device` = the raw rows "
                              "of a whole look-ahead window are uploaded ahead and cut into batches on the GPU "
-                             "(data_loader_terabyte.DeviceDayLoader)")
+                             "(data_loader_terabyte.DeviceDayLoader; with --mlperf-bin-loader: BinLoader / DeviceBinLoader)")
     parser.add_argument("--device-rng", action="store_true", default=False,
                         help="way choice by counter-based Philox on the GPU (perf mode; not bit-comparable with the "
                              "reference's torch-CPU Categorical draw)")
@@ -701,7 +701,40 @@ def main(argv=None):
         sys.exit("ERROR: --data-generation=%s is not supported (dataset | criteo-synthetic | random | synthetic)"
                  % args.data_generation)
     train_ld = test_ld = None
-    if args.data_generation == "dataset":
+    if args.data_generation == "dataset" and args.mlperf_bin_loader:
+        # the binary files of the reference's MLPerf path (dlrm_data_pytorch.py:391-439): <processed-data-file minus its
+        # extension>_train.bin / _test.bin, table sizes from <raw>_fea_count.npz.  The reference reaches this branch only with
+        # --large-batch --memory-map --data-set=terabyte and starts its ETL when a file is missing; here the flag alone chooses
+        # it and a missing file ends the run.  The training loader leaves the short last batch out, as the day-file path
+        # does (a step's batch is sliced across ranks); --mlperf-bin-shuffle applies to it alone.
+        from .data_loader_terabyte import BinLoader, CriteoBinDataset, DeviceBinLoader
+        lstr = args.processed_data_file.split("/")
+        d_path = "/".join(lstr[0:-1] + [lstr[-1].split(".")[0]])
+        train_file, test_file, counts_file = d_path + "_train.bin", d_path + "_test.bin", args.raw_data_file + "_fea_count.npz"
+        for f in (train_file, test_file, counts_file):
+            if not os.path.isfile(f):
+                sys.exit("ERROR: --mlperf-bin-loader: %s does not exist (the Criteo pre-processing that writes it is not part "
+                         "of this program)" % f)
+        tb = args.test_mini_batch_size if args.test_mini_batch_size > 0 else args.mini_batch_size
+        try:
+            train_data = CriteoBinDataset(train_file, counts_file, args.mini_batch_size, args.max_ind_range)
+            test_data = CriteoBinDataset(test_file, counts_file, tb, args.max_ind_range)
+        except ValueError as e:
+            sys.exit("ERROR: " + str(e))
+        args.arch_embedding_size = "-".join(str(int(c)) for c in train_data.counts)
+        # every rank draws the permutation itself: at world > 1 from a generator of its own, so that all of them draw the same
+        gen = torch.Generator().manual_seed(args.numpy_rand_seed) if args.mlperf_bin_shuffle and args.world_size > 1 else None
+        if args.day_file_loader == "device":
+            train_ld = DeviceBinLoader(train_data, args.mlperf_bin_shuffle, True, gen, window=args.lookahead)
+            test_ld = DeviceBinLoader(test_data, window=16)
+        else:
+            train_ld = BinLoader(train_data, args.mlperf_bin_shuffle, True, gen)
+            test_ld = BinLoader(test_data)
+        if rank == 0:
+            print("MLPerf binary loader: %s (%s) reads %s, %d batches of %d%s; test: %s" % (
+                type(train_ld).__name__, args.day_file_loader, train_file, len(train_ld), args.mini_batch_size,
+                ", shuffled" if args.mlperf_bin_shuffle else "", test_file), flush=True)
+    elif args.data_generation == "dataset":
         # the pre-processed day files of the reference's terabyte path (dlrm_data_pytorch.py:440-492): table sizes
         # from <raw>_fea_count.npz (:180-181), batches from <raw>_<day>_reordered.npz
         from .data_loader_terabyte import DataLoader, DeviceDayLoader
@@ -769,7 +802,7 @@ def main(argv=None):
     launch.check_world(args.world_size)
     if args.data_generation == "dataset" and args.day_file_loader == "device":
         train_ld.device = test_ld.device = dev
-        if rank == 0:
+        if rank == 0 and not args.mlperf_bin_loader:
             print("Day-file loader: device (windows of %d batches cut on the GPU, one window uploaded ahead)" % train_ld.window,
                   flush=True)
     from . import synth

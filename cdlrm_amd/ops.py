@@ -863,6 +863,34 @@ def dayfile_window(x_int: torch.Tensor, x_cat: torch.Tensor, y: torch.Tensor, ma
                                           X.data_ptr(), lS_i.data_ptr(), pitch, col0, T.data_ptr(), stream_ptr(stream)))
 
 
+def binfile_tile() -> int:
+    """Samples per workgroup of `binfile_window`'s kernel."""
+    return int(_lib.lib().cdlrm_binfile_tile())
+
+
+def binfile_window(rec: torch.Tensor, n_dense: int, max_ind_range: int, X: torch.Tensor, lS_i: torch.Tensor, T: torch.Tensor,
+                   col0: int = 0, stream=None) -> None:
+    """n records of the MLPerf binary Criteo file on the device (rec int32 [n, 1 + n_dense + n_cat], a record =
+    [y | dense | categorical]) -> samples [col0, col0 + n) of a window, with `dayfile_window`'s outputs and rules
+    (include/cdlrm_hip.h: cdlrm_binfile_window)."""
+    for t, name in ((rec, "rec"), (X, "X"), (lS_i, "lS_i"), (T, "T")):
+        _require_cuda(t, name)
+    assert rec.dtype == torch.int32 and X.dtype == torch.float32 and T.dtype == torch.float32 and lS_i.dtype == torch.int64
+    assert rec.dim() == 2 and X.dim() == 2 and lS_i.dim() == 2
+    assert rec.is_contiguous() and X.is_contiguous() and T.is_contiguous()
+    n, nd = rec.shape[0], int(n_dense)
+    nc = rec.shape[1] - 1 - nd
+    col0 = int(col0)
+    assert nd >= 1 and nc >= 1 and X.shape[1] == nd and lS_i.shape[0] == nc
+    assert col0 >= 0 and col0 + n <= X.shape[0] and col0 + n <= T.numel() and col0 + n <= lS_i.shape[1], \
+        "samples [%d, %d) do not fit the window buffers" % (col0, col0 + n)
+    assert lS_i.stride(1) == 1 or lS_i.shape[1] == 1
+    pitch = lS_i.stride(0) if nc > 1 else lS_i.shape[1]
+    assert pitch >= lS_i.shape[1]
+    check(_lib.lib().cdlrm_binfile_window(rec.data_ptr(), n, nd, nc, int(max_ind_range), X.data_ptr(), lS_i.data_ptr(), pitch,
+                                          col0, T.data_ptr(), stream_ptr(stream)))
+
+
 def mark_rows(ctx: CacheCtx, slots: torch.Tensor, touched: torch.Tensor, stream=None):
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[0] == ctx.T
     check(_lib.lib().cdlrm_mark_rows(ctx.handle, slots.data_ptr(), slots.shape[1], touched.data_ptr(),

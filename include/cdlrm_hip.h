@@ -643,6 +643,20 @@ int cdlrm_dayfile_window(const int32_t* x_int, const int32_t* x_cat, const int32
 /* samples per workgroup of cdlrm_dayfile_window (tests probe its edges; tools size their grids by it) */
 int cdlrm_dayfile_tile(void);
 
+/* ---- MLPerf binary Criteo records cut on the device (data_loader_terabyte.DeviceBinLoader) ------------------------------
+ * Replaces, for n records of the binary file that lie in HBM as the file stores them (rec int32 [n, 1 + n_dense + n_cat],
+ * a record = [y | n_dense | n_cat], data_loader_terabyte.py:238-275), CriteoBinDataset.__getitem__'s host transform
+ * (data_loader_terabyte.py:225-235 -> _transform_features, :68-87) and the trainer's per-step uploads of its result
+ * (main_no_ddp.py:388-391).  Outputs and their meaning are cdlrm_dayfile_window's, word for word, with
+ * x_int[i, :] = rec[i, 1 : 1 + n_dense], x_cat[i, :] = rec[i, 1 + n_dense :], y[i] = rec[i, 0]: the same log in double
+ * rounded once, the same floor-mod, cells outside columns [col0, col0 + n) not written, n_cat <= 60; in addition a tile of
+ * 256 whole records must fit the LDS (1 + n_dense + n_cat <= 159).  rec needs 4-byte alignment only.  Not a tape entry
+ * point: it never runs on the training queue. */
+int cdlrm_binfile_window(const int32_t* rec, int64_t n, int32_t n_dense, int32_t n_cat, int64_t max_ind_range, float* X,
+                         int64_t* lS_i, int64_t lS_i_pitch, int64_t col0, float* T, void* stream);
+/* samples per workgroup of cdlrm_binfile_window */
+int cdlrm_binfile_tile(void);
+
 /* ---- launch tapes -------------------------------------------------------------------------------------------------
  * A training step's call sequence (this library's entry points + event records / stream waits), recorded once per control
  * path by the host and re-issued by ONE call per step (the reference issues the same ops from Python every iteration,
