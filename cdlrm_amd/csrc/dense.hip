@@ -127,8 +127,9 @@ static int linear_fwd(const float* X, int64_t ld_x, const float* W, const float*
                       int32_t K, int32_t act, void* stream, const GemmRec* rec) {
     CDLRM_REQUIRE(X && W && Y && M >= 0 && N >= 1 && K >= 1 && ld_x >= K && ld_y >= N, "bad argument");
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint riding on the activation code
-    const int bf16 = (act & CDLRM_GEMM_BF16) != 0;         // the opt-in bf16 matrix-core mode (gemm_bf16.h)
-    act &= ~(CDLRM_GEMM_ALONE | CDLRM_GEMM_BF16);
+    const int bf16 = bf16_planes(act);                     // the opt-in bf16 / bf16x3 matrix-core modes (gemm_bf16.h): 1 / 2 planes
+    act &= ~(CDLRM_GEMM_ALONE | BF16_MODES);
+    CDLRM_REQUIRE(bf16 >= 0, "CDLRM_GEMM_BF16 and CDLRM_GEMM_BF16X3 exclude each other");
     CDLRM_REQUIRE(act >= 0 && act <= 2, "bad activation code");
     if (M == 0) return 0;
     if (!rec) CDLRM_CLEAR_STALE();
@@ -136,7 +137,7 @@ static int linear_fwd(const float* X, int64_t ld_x, const float* W, const float*
         GemmArgs g = gemm_args();
         g.A = X; g.lda = ld_x; g.B = W; g.ldb = K; g.C = Y; g.ldc = ld_y; g.slab = 0;
         g.M = M; g.N = N; g.K = K; g.bias = bias; g.act = act;
-        return launch_gemm_bf16<true, true>(g, (hipStream_t)stream, rec);
+        return launch_gemm_bf16<true, true>(g, bf16, (hipStream_t)stream, rec);
     }
     // (Round 6, measured and removed: this layer on the matrix cores -- a wave owning 16 rows x 256 columns, the weights as
     //  16x16x4 fragments in registers, ascending k, bit-identical -- 10.9 us alone against 8.6 for the register kernel below at
@@ -375,8 +376,10 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
                       float* dX, int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N, int32_t K, int32_t act,
                       int32_t x_act, void* work, void* stream, const GemmRec* rec) {
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint for the dgrad GEMM, riding on the activation code
-    const int bf16 = (act & CDLRM_GEMM_BF16) != 0 && bf16_layer_ok(N, K);     // both GEMMs of the layer in bf16 (gemm_bf16.h)
-    act &= ~(CDLRM_GEMM_ALONE | CDLRM_GEMM_BF16);
+    const int planes = bf16_planes(act);
+    const int bf16 = bf16_layer_ok(N, K) ? planes : 0;     // both GEMMs of the layer in bf16 / bf16x3 (gemm_bf16.h): 1 / 2 planes
+    act &= ~(CDLRM_GEMM_ALONE | BF16_MODES);
+    CDLRM_REQUIRE(planes >= 0, "CDLRM_GEMM_BF16 and CDLRM_GEMM_BF16X3 exclude each other");
     CDLRM_REQUIRE(X && W && dY && work && M >= 1 && N >= 1 && K >= 1, "bad argument");
     CDLRM_REQUIRE(dW || !db, "db without dW (the bias gradient is a by-product of the weight-gradient GEMM)");
     CDLRM_REQUIRE(act == 0 || Y, "activation backward needs Y");
@@ -395,7 +398,7 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
         g.vecB = aligned16(W) && K % 4 == 0;
         g.mask = X; g.ldmask = ld_x; g.mask_act = x_act;
         g.alone = alone;
-        int rc = bf16 ? launch_gemm_bf16<true, false>(g, s, rec) : launch_gemm<true, false>(g, 1, s, rec);
+        int rc = bf16 ? launch_gemm_bf16<true, false>(g, bf16, s, rec) : launch_gemm<true, false>(g, 1, s, rec);
         if (rc) return rc;
     }
     // dW[N,K] = dZ[M,N]^T X[M,K], split over M into slabs summed in slab order; the first column panel of the
@@ -426,8 +429,8 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
         }
         int rc = 0;
         if (!bf16) rc = launch_gemm<false, false>(g, zs, s, rec ? rec + 1 : nullptr);
-        else if (rec) gemm_record(rec + 1, CDLRM_ROUTE_BF16, 1, 1, 0, 0, zs, g.vecA, g.vecB, 0);
-        else rc = launch_wgrad_bf16(&g, 1, g.vecA, g.vecB, s);
+        else if (rec) gemm_record(rec + 1, bf16_family(bf16), 1, 1, 0, 0, zs, g.vecA, g.vecB, 0);
+        else rc = launch_wgrad_bf16(&g, 1, g.vecA, g.vecB, bf16, s);
         if (rc) return rc;
         if (zs > 1 && !rec)     // one launch sums the dW slabs and the bias-gradient partials
             hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)(r.gxa + cdiv(r.countB, 64))), dim3(256), 0, s, r.partA, r.countA, zs,
@@ -443,7 +446,7 @@ extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, co
     CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
     // a completion event waiting for this call (cdlrm_event_attach_next) rides on the dgrad GEMM when that is the call's only
     // launch (the training step's use); with several launches it is recorded behind the last one
-    if ((act & ~(CDLRM_GEMM_ALONE | CDLRM_GEMM_BF16)) != 0 || dW || !dX) stop_scope.hold((hipStream_t)stream);
+    if ((act & ~(CDLRM_GEMM_ALONE | BF16_MODES)) != 0 || dW || !dX) stop_scope.hold((hipStream_t)stream);
     return linear_bwd(X, ld_x, W, Y, ld_y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, stream, nullptr);
     // (stop_scope records an event no launch carried)
 }
@@ -473,7 +476,7 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
 //   long batches:
 //     WG_SPLIT   per layer one split-M GEMM (launch_gemm picks the kernel: tiled, or LDS-free for degenerate shapes) into the
 //                layer's own slabs, then ONE grouped reduction of all layers
-//   flags & CDLRM_GEMM_BF16 (gemm_bf16.h), any batch:
+//   flags & CDLRM_GEMM_BF16 or CDLRM_GEMM_BF16X3 (gemm_bf16.h; the same layout, one or two operand planes), any batch:
 //     WG_BF16    the layers the shape rule admits (bf16_layer_ok) as one grouped bf16 launch on 64x64 tiles with one slab length
 //                (bf16_wgrad_kchunk), then one grouped reduction of their slabs.  The other layers (the 13-wide input, the 1-wide
 //                head) keep the family AND slab count they have in the all-fp32 call of the same layer list, run in front, and
@@ -498,6 +501,7 @@ struct WgradLayer {
 };
 struct WgradLayout {
     std::vector<WgradLayer> L;      // one per layer, in the caller's order
+    int planes = 0;                 // bf16_planes(flags): 1 bf16, 2 bf16x3
     int n_bf = 0;                   // layers of the bf16 group
     int bf_vecA = 1, bf_vecB = 1;   // ... which runs one kernel variant: 16-byte loads where every member allows them
     uint64_t high = 0;              // bytes of `work` the call writes: the end of the last block carved
@@ -508,6 +512,8 @@ struct WgradLayout {
 static void wgrad_layout(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K, int32_t flags, const float* const* X,
                          const int64_t* ld_x, const float* const* dZ, const int64_t* ld_dz, WgradLayout& p) {
     const bool shortb = M <= WGRAD_DIRECT_MAX_M;
+    const bool bf = (flags & BF16_MODES) != 0;
+    p.planes = bf16_planes(flags);
     p.L.resize((size_t)(n_layers > 0 ? n_layers : 0));
     // families; the tiles that set the slab counts
     int64_t tiles = 0, bf_tiles = 0;
@@ -519,7 +525,7 @@ static void wgrad_layout(int32_t n_layers, int64_t M, const int32_t* N, const in
         const bool tiled = l.vecA && l.vecB && M >= 256;
         // (a layer that leaves for the bf16 group still counts: the slab count of the fp32 layers beside it is that of the all-fp32 call)
         if (shortb && tiled) tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
-        if ((flags & CDLRM_GEMM_BF16) && bf16_layer_ok(N[i], K[i])) {
+        if (bf && bf16_layer_ok(N[i], K[i])) {
             l.family = WG_BF16;
             p.n_bf++;
             bf_tiles += cdiv(N[i], 64) * cdiv(K[i], 64);
@@ -554,11 +560,11 @@ static void wgrad_layout(int32_t n_layers, int64_t M, const int32_t* N, const in
     // split rule's cap for every layer (tiled or not), long batches cdlrm_linear_bwd_work_bytes per layer (wgrad_splits slabs
     // where the layout may need fewer, 256 bytes of slack each), 256 bytes in front.  In a bf16 call it is also where the bf16
     // group's slabs start; a call without fp32 layers reserves nothing for them.
-    uint64_t fp_reserve = (flags & CDLRM_GEMM_BF16) && !any_fp ? 0 : 256;
+    uint64_t fp_reserve = bf && !any_fp ? 0 : 256;
     uint64_t cs;
     // blocks in `work`, in launch order
     for (int f = 0; f < WG_FAMILIES; ++f) {
-        if (f == WG_BF16 && (flags & CDLRM_GEMM_BF16)) p.high = fp_reserve;     // (the fp32 layers own the front part, used or not)
+        if (f == WG_BF16 && bf) p.high = fp_reserve;     // (the fp32 layers own the front part, used or not)
         for (int i = 0; i < n_layers; ++i) {
             WgradLayer& l = p.L[i];
             if (l.family != f) continue;
@@ -587,15 +593,15 @@ static void wgrad_layout(int32_t n_layers, int64_t M, const int32_t* N, const in
             }
         }
     }
-    if (flags & CDLRM_GEMM_BF16) p.reserve = p.high + 256;
+    if (bf) p.reserve = p.high + 256;
     else p.reserve = fp_reserve;
 }
 
 extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes_ex(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K,
                                                   int32_t flags) {
-    if (!N || !K) return 0;
+    if (!N || !K || bf16_planes(flags) < 0) return 0;
     WgradLayout p;
-    wgrad_layout(n_layers, M, N, K, flags & CDLRM_GEMM_BF16, nullptr, nullptr, nullptr, nullptr, p);
+    wgrad_layout(n_layers, M, N, K, flags & BF16_MODES, nullptr, nullptr, nullptr, nullptr, p);
     return p.reserve;
 }
 
@@ -636,7 +642,8 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
                          const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
                          const int32_t* K, int32_t flags, void* work, void* stream, float* const* P_w, float* const* P_b, float lr,
                          cdlrm_gemm_route* rout, int n_cu) {
-    CDLRM_REQUIRE((flags & ~CDLRM_GEMM_BF16) == 0, "bad flags");
+    CDLRM_REQUIRE((flags & ~BF16_MODES) == 0, "bad flags");
+    CDLRM_REQUIRE(bf16_planes(flags) >= 0, "CDLRM_GEMM_BF16 and CDLRM_GEMM_BF16X3 exclude each other");
     CDLRM_REQUIRE(n_layers >= 0 && (n_layers == 0 || (X && ld_x && dZ && ld_dz && dW && db && N && K)) && M >= 1,
                   "bad argument");
     for (int i = 0; i < n_layers; ++i)
@@ -660,7 +667,7 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
             const WgradLayer& l = p.L[i];
             if (l.family == WG_TILED) route_set(&rout[i], CDLRM_ROUTE_GEMM, 1, 1, 0, 0, l.zs, 1, 1, 0);
             else if (l.family == WG_DIRECT) route_set(&rout[i], CDLRM_ROUTE_DIRECT, 0, 0, 0, 0, l.zs, l.vecA, l.vecB, 0);
-            else if (l.family == WG_BF16) route_set(&rout[i], CDLRM_ROUTE_BF16, 1, 1, 0, 0, l.zs, p.bf_vecA, p.bf_vecB, 0);
+            else if (l.family == WG_BF16) route_set(&rout[i], bf16_family(p.planes), 1, 1, 0, 0, l.zs, p.bf_vecA, p.bf_vecB, 0);
             else {      // the kernel and its tile are launch_gemm's choice
                 const GemmRec rec = {&rout[i], n_cu};
                 (void)launch_gemm<false, false>(problem(i), l.zs, s, &rec);
@@ -750,7 +757,7 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
     if (p.n_bf == 0) return 0;
     probs.clear();
     stage(WG_BF16);
-    int rc = launch_wgrad_bf16(probs.data(), (int)probs.size(), p.bf_vecA, p.bf_vecB, s);
+    int rc = launch_wgrad_bf16(probs.data(), (int)probs.size(), p.bf_vecA, p.bf_vecB, p.planes, s);
     if (rc) return rc;
     return finish(true);
 }

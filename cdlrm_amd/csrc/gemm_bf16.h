@@ -21,6 +21,17 @@
 //   happens in the write pass).
 // Rows past the matrix edge are clamped to valid addresses (their products land in outputs that are never stored), contraction
 // indices past the split's end are zero-filled at LDS-write time -- the K tails (479, 480 not a multiple of 64) included.
+//
+// PL = 2: the opt-in `CDLRM_GEMM_BF16X3` mode, the same kernels with two bf16 PLANES per operand:
+//
+//   x ~ h + l,   h = bf16(x),   l = bf16(x - float(h))   (the subtraction is exact in fp32; l = 0 where h is not finite)
+//   C[m,n] = sum_k  al*bh + ah*bl + ah*bh                 (al*bl, ~2^-16 of the product, is dropped)
+//
+// Loads, staging registers, K tails and epilogue are those of PL = 1; b16_store writes a hi image and, ROWS * B16_KP elements
+// behind it, a lo image of the same pitch (two planes = the LDS bytes of one fp32 image), and each 16-deep step issues three
+// MFMAs per accumulator -- lo*hi, hi*lo, hi*hi, the small terms first -- into the one fp32 accumulator.  |x - h - l| <= 2^-16 |x|,
+// so a product is off by ~3 * 2^-16 of its magnitude at most: near fp32, not fp32.  Tiles: 64x64 and 64x128 only (a 128x128
+// tile's four images are 73.7 KB, past the 64 KB a workgroup may declare statically).
 #pragma once
 #include "gemm.h"
 
@@ -35,6 +46,14 @@ typedef float f32x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned b16_pack(float lo, float hi) {
     const b16x2 v = __builtin_convertvector((f32x2v){lo, hi}, b16x2);
     return __builtin_bit_cast(unsigned, v);
+}
+
+// the two planes of a pair: hi = the plain cast, lo = the cast of the (exact) remainder, 0 where hi is Inf or NaN -- a NaN or an
+// overflow then lives in the hi plane alone and reaches the outputs of its own row / column only
+__device__ __forceinline__ void b16_split(float x0, float x1, unsigned& hi, unsigned& lo) {
+    hi = b16_pack(x0, x1);
+    const float r0 = x0 - __uint_as_float(hi << 16), r1 = x1 - __uint_as_float(hi & 0xffff0000u);
+    lo = b16_pack((hi & 0x7f80u) != 0x7f80u ? r0 : 0.f, (hi & 0x7f800000u) != 0x7f800000u ? r1 : 0.f);
 }
 
 // float4s one thread holds for one operand tile of ROWS rows x 64 contraction indices (both staging forms: ROWS / 16)
@@ -86,9 +105,11 @@ __device__ __forceinline__ void b16_load(const float* __restrict__ P, int64_t ld
     }
 }
 
-// convert + write one staged tile into its bf16 LDS image, zero-filling contraction indices >= kmax
-template <bool KC, int ROWS>
+// convert + write one staged tile into its bf16 LDS image (PL = 2: the hi image at S, the lo image ROWS * B16_KP behind it),
+// zero-filling contraction indices >= kmax
+template <bool KC, int ROWS, int PL>
 __device__ __forceinline__ void b16_store(unsigned short* __restrict__ S, const B16Stage<ROWS>& st, int64_t k0, int64_t kmax) {
+    unsigned short* __restrict__ SL = (PL == 2) ? S + ROWS * B16_KP : S;     // PL = 1: the one image only, SL unused
     if (KC) {
 #pragma unroll
         for (int i = 0; i < ROWS / 32; ++i) {
@@ -99,7 +120,14 @@ __device__ __forceinline__ void b16_store(unsigned short* __restrict__ S, const 
 #pragma unroll
             for (int u = 0; u < 8; ++u) e[u] = (k0 + c + u < kmax) ? e[u] : 0.f;     // selects, not branches
             uint4 w;
-            w.x = b16_pack(e[0], e[1]); w.y = b16_pack(e[2], e[3]); w.z = b16_pack(e[4], e[5]); w.w = b16_pack(e[6], e[7]);
+            if (PL == 2) {
+                uint4 wl;
+                b16_split(e[0], e[1], w.x, wl.x); b16_split(e[2], e[3], w.y, wl.y);
+                b16_split(e[4], e[5], w.z, wl.z); b16_split(e[6], e[7], w.w, wl.w);
+                *reinterpret_cast<uint4*>(SL + r * B16_KP + c) = wl;
+            } else {
+                w.x = b16_pack(e[0], e[1]); w.y = b16_pack(e[2], e[3]); w.z = b16_pack(e[4], e[5]); w.w = b16_pack(e[6], e[7]);
+            }
             *reinterpret_cast<uint4*>(S + r * B16_KP + c) = w;
         }
     } else {
@@ -115,10 +143,22 @@ __device__ __forceinline__ void b16_store(unsigned short* __restrict__ S, const 
                 x[u].x = ok ? x[u].x : 0.f; x[u].y = ok ? x[u].y : 0.f; x[u].z = ok ? x[u].z : 0.f; x[u].w = ok ? x[u].w : 0.f;
             }
             uint2 w0, w1, w2, w3;       // row r + q: its 4 consecutive contraction indices 4 kg .. 4 kg + 3
-            w0.x = b16_pack(x[0].x, x[1].x); w0.y = b16_pack(x[2].x, x[3].x);
-            w1.x = b16_pack(x[0].y, x[1].y); w1.y = b16_pack(x[2].y, x[3].y);
-            w2.x = b16_pack(x[0].z, x[1].z); w2.y = b16_pack(x[2].z, x[3].z);
-            w3.x = b16_pack(x[0].w, x[1].w); w3.y = b16_pack(x[2].w, x[3].w);
+            if (PL == 2) {
+                uint2 l0, l1, l2, l3;
+                b16_split(x[0].x, x[1].x, w0.x, l0.x); b16_split(x[2].x, x[3].x, w0.y, l0.y);
+                b16_split(x[0].y, x[1].y, w1.x, l1.x); b16_split(x[2].y, x[3].y, w1.y, l1.y);
+                b16_split(x[0].z, x[1].z, w2.x, l2.x); b16_split(x[2].z, x[3].z, w2.y, l2.y);
+                b16_split(x[0].w, x[1].w, w3.x, l3.x); b16_split(x[2].w, x[3].w, w3.y, l3.y);
+                *reinterpret_cast<uint2*>(SL + (r + 0) * B16_KP + 4 * kg) = l0;
+                *reinterpret_cast<uint2*>(SL + (r + 1) * B16_KP + 4 * kg) = l1;
+                *reinterpret_cast<uint2*>(SL + (r + 2) * B16_KP + 4 * kg) = l2;
+                *reinterpret_cast<uint2*>(SL + (r + 3) * B16_KP + 4 * kg) = l3;
+            } else {
+                w0.x = b16_pack(x[0].x, x[1].x); w0.y = b16_pack(x[2].x, x[3].x);
+                w1.x = b16_pack(x[0].y, x[1].y); w1.y = b16_pack(x[2].y, x[3].y);
+                w2.x = b16_pack(x[0].z, x[1].z); w2.y = b16_pack(x[2].z, x[3].z);
+                w3.x = b16_pack(x[0].w, x[1].w); w3.y = b16_pack(x[2].w, x[3].w);
+            }
             *reinterpret_cast<uint2*>(S + (r + 0) * B16_KP + 4 * kg) = w0;
             *reinterpret_cast<uint2*>(S + (r + 1) * B16_KP + 4 * kg) = w1;
             *reinterpret_cast<uint2*>(S + (r + 2) * B16_KP + 4 * kg) = w2;
@@ -127,7 +167,8 @@ __device__ __forceinline__ void b16_store(unsigned short* __restrict__ S, const 
     }
 }
 
-template <bool A_KC, bool B_KC, int TM, int TN, bool VA, bool VB>
+// As / Bs: PL images of BM / BN rows each
+template <bool A_KC, bool B_KC, int TM, int TN, bool VA, bool VB, int PL>
 __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& g, unsigned bx, unsigned by, unsigned bz,
                                                unsigned short* __restrict__ As, unsigned short* __restrict__ Bs) {
     constexpr int BM = 64 * TM, BN = 64 * TN;
@@ -155,8 +196,8 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& g, unsigned bx, u
     const int lr = lane & 31, lh = lane >> 5;
     for (int64_t k0 = kbeg; k0 < kend; k0 += B16_BK) {
         __syncthreads();
-        b16_store<A_KC, BM>(As, ra, k0, kend);
-        b16_store<B_KC, BN>(Bs, rb, k0, kend);
+        b16_store<A_KC, BM, PL>(As, ra, k0, kend);
+        b16_store<B_KC, BN, PL>(Bs, rb, k0, kend);
         __syncthreads();
         if (!A_KC && do_colsum) {       // wave-uniform; no loads inside
 #pragma unroll
@@ -175,21 +216,30 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& g, unsigned bx, u
         b16_load<B_KC, BN, VB>(g.B, g.ldb, n0, g.N, k0 + B16_BK, kend, rb);
 #pragma unroll
         for (int s = 0; s < B16_BK / 16; ++s) {
-            b16x8 a[TM], b[TN];
+            b16x8 a[PL][TM], b[PL][TN];          // [0] hi, [1] lo
 #pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int r = wm * (32 * TM) + i * 32 + lr;
-                a[i] = __builtin_bit_cast(b16x8, *reinterpret_cast<const uint4*>(As + r * B16_KP + 16 * s + 8 * lh));
+            for (int p = 0; p < PL; ++p) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const int r = p * BM + wm * (32 * TM) + i * 32 + lr;
+                    a[p][i] = __builtin_bit_cast(b16x8, *reinterpret_cast<const uint4*>(As + r * B16_KP + 16 * s + 8 * lh));
+                }
+#pragma unroll
+                for (int j = 0; j < TN; ++j) {
+                    const int c = p * BN + wn * (32 * TN) + j * 32 + lr;
+                    b[p][j] = __builtin_bit_cast(b16x8, *reinterpret_cast<const uint4*>(Bs + c * B16_KP + 16 * s + 8 * lh));
+                }
             }
+            // PL = 2: lo*hi, hi*lo, then hi*hi; each pass over all accumulators, so that consecutive MFMAs are independent
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int c = wn * (32 * TN) + j * 32 + lr;
-                b[j] = __builtin_bit_cast(b16x8, *reinterpret_cast<const uint4*>(Bs + c * B16_KP + 16 * s + 8 * lh));
+            for (int t = (PL == 2 ? 0 : 2); t < 3; ++t) {
+                const int pa = t == 0 ? PL - 1 : 0, pb = t == 1 ? PL - 1 : 0;
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[pa][i], b[pb][j], acc[i][j], 0, 0, 0);
             }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     }
     if (!A_KC && do_colsum) {
@@ -231,21 +281,22 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmArgs& g, unsigned bx, u
         }
 }
 
-template <bool A_KC, bool B_KC, int TM, int TN, bool VA, bool VB>
+template <bool A_KC, bool B_KC, int TM, int TN, bool VA, bool VB, int PL>
 __global__ void __launch_bounds__(256) k_gemm_bf16(GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) unsigned short As[64 * TM * B16_KP];
-    __shared__ __attribute__((aligned(16))) unsigned short Bs[64 * TN * B16_KP];
+    static_assert(PL * 64 * (TM + TN) * B16_KP * 2 <= 65536, "static LDS of a workgroup");
+    __shared__ __attribute__((aligned(16))) unsigned short As[PL * 64 * TM * B16_KP];
+    __shared__ __attribute__((aligned(16))) unsigned short Bs[PL * 64 * TN * B16_KP];
     const unsigned nwg = gridDim.x * gridDim.y * gridDim.z;
     const unsigned wgid = xcd_remap((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, nwg);
-    gemm_bf16_body<A_KC, B_KC, TM, TN, VA, VB>(g, wgid % gridDim.x, (wgid / gridDim.x) % gridDim.y,
-                                               wgid / (gridDim.x * gridDim.y), As, Bs);
+    gemm_bf16_body<A_KC, B_KC, TM, TN, VA, VB, PL>(g, wgid % gridDim.x, (wgid / gridDim.x) % gridDim.y,
+                                                   wgid / (gridDim.x * gridDim.y), As, Bs);
 }
 
 // grouped launch of 64x64-tile problems (the weight gradients of several layers), each with its own contraction split
-template <bool VA, bool VB>
+template <bool VA, bool VB, int PL>
 __global__ void __launch_bounds__(256) k_gemm_bf16_group(GemmGroup grp) {
-    __shared__ __attribute__((aligned(16))) unsigned short As[64 * B16_KP];
-    __shared__ __attribute__((aligned(16))) unsigned short Bs[64 * B16_KP];
+    __shared__ __attribute__((aligned(16))) unsigned short As[PL * 64 * B16_KP];
+    __shared__ __attribute__((aligned(16))) unsigned short Bs[PL * 64 * B16_KP];
     const unsigned wgid = xcd_remap(blockIdx.x, gridDim.x);
     int p = 0;
 #pragma unroll
@@ -254,7 +305,7 @@ __global__ void __launch_bounds__(256) k_gemm_bf16_group(GemmGroup grp) {
     const GemmArgs& g = grp.g[p];
     const unsigned local = wgid - grp.first[p];
     const unsigned gx = (unsigned)((g.N + 63) / 64), gy = (unsigned)((g.M + 63) / 64);
-    gemm_bf16_body<false, false, 1, 1, VA, VB>(g, local % gx, (local / gx) % gy, local / (gx * gy), As, Bs);
+    gemm_bf16_body<false, false, 1, 1, VA, VB, PL>(g, local % gx, (local / gx) % gy, local / (gx * gy), As, Bs);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -262,6 +313,14 @@ __global__ void __launch_bounds__(256) k_gemm_bf16_group(GemmGroup grp) {
 // The shape rule of the mode (layer terms: N outputs, K inputs): every GEMM of a layer with K >= 32 and N >= 32 -- never M, so
 // results do not depend on the batch size.  The 13-wide first layer and the 1-wide head stay on their fp32 routes.
 static inline bool bf16_layer_ok(int64_t N, int64_t K) { return N >= 32 && K >= 32; }
+
+// The mode bits of a flags word -> operand planes: 0 fp32, 1 CDLRM_GEMM_BF16, 2 CDLRM_GEMM_BF16X3, -1 both (an error)
+#define BF16_MODES (CDLRM_GEMM_BF16 | CDLRM_GEMM_BF16X3)
+static inline int bf16_planes(int32_t flags) {
+    const int32_t m = flags & BF16_MODES;
+    return m == 0 ? 0 : m == CDLRM_GEMM_BF16 ? 1 : m == CDLRM_GEMM_BF16X3 ? 2 : -1;
+}
+static inline int bf16_family(int planes) { return planes == 2 ? CDLRM_ROUTE_BF16X3 : CDLRM_ROUTE_BF16; }
 
 // 16-byte loads legal for one operand: rows 16-byte aligned, and >= 4 elements along the loaded direction
 template <bool KC>
@@ -272,10 +331,11 @@ static inline bool bf16_vec(const float* P, int64_t ld, int64_t rows, int64_t kd
 
 // tile of an un-split forward / dgrad: the largest of 128x128, 64x128, 64x64 whose grid keeps >= 4 workgroups per CU (the
 // loads, not the MFMAs, set the pace here: more workgroups in flight hide more of their latency).  (128x64 is never picked: its
-// grid is never larger than 64x128's.)
-static inline void bf16_pick_tile(int64_t M, int64_t N, int* tm, int* tn) {
+// grid is never larger than 64x128's.)  Two planes: the same rule over 64x128 and 64x64 (55.3 and 36.9 KB of LDS: two and four
+// workgroups per CU; 128x128 would need 73.7 KB, more than a workgroup may declare statically).
+static inline void bf16_pick_tile(int64_t M, int64_t N, int planes, int* tm, int* tn) {
     const int cand[3][2] = {{2, 2}, {1, 2}, {1, 1}};
-    for (int c = 0; c < 3; ++c) {
+    for (int c = planes == 2 ? 1 : 0; c < 3; ++c) {
         if (cdiv(M, 64 * cand[c][0]) * cdiv(N, 64 * cand[c][1]) >= 2 * GEMM_MIN_BLOCKS || c == 2) {
             *tm = cand[c][0]; *tn = cand[c][1];
             return;
@@ -283,32 +343,35 @@ static inline void bf16_pick_tile(int64_t M, int64_t N, int* tm, int* tn) {
     }
 }
 
-template <bool A_KC, bool B_KC, int TM, int TN>
+template <bool A_KC, bool B_KC, int TM, int TN, int PL>
 static void launch_gemm_bf16_v(const GemmArgs& g, dim3 grid, hipStream_t s) {
-    if (g.vecA && g.vecB) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, true, true>), grid, dim3(256), 0, s, g);
-    else if (g.vecA) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, true, false>), grid, dim3(256), 0, s, g);
-    else if (g.vecB) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, false, true>), grid, dim3(256), 0, s, g);
-    else CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, false, false>), grid, dim3(256), 0, s, g);
+    if (g.vecA && g.vecB) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, true, true, PL>), grid, dim3(256), 0, s, g);
+    else if (g.vecA) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, true, false, PL>), grid, dim3(256), 0, s, g);
+    else if (g.vecB) CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, false, true, PL>), grid, dim3(256), 0, s, g);
+    else CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, false, false, PL>), grid, dim3(256), 0, s, g);
 }
 
-// An un-split forward (A_KC, B_KC) or dgrad (A_KC, !B_KC) in bf16.  g.vecA / g.vecB are recomputed here from the operands.
-// rec != nullptr: record the route, launch nothing.
+// An un-split forward (A_KC, B_KC) or dgrad (A_KC, !B_KC) in bf16 (planes 1) or bf16x3 (planes 2).  g.vecA / g.vecB are
+// recomputed here from the operands.  rec != nullptr: record the route, launch nothing.
 template <bool A_KC, bool B_KC>
-static int launch_gemm_bf16(GemmArgs g, hipStream_t s, const GemmRec* rec) {
+static int launch_gemm_bf16(GemmArgs g, int planes, hipStream_t s, const GemmRec* rec) {
     static_assert(A_KC, "forward / dgrad layouts only; the weight gradient goes through launch_wgrad_bf16");
     g.vecA = bf16_vec<true>(g.A, g.lda, g.M, g.K);
     g.vecB = bf16_vec<B_KC>(g.B, g.ldb, g.N, g.K);
     g.kchunk = g.K;
     int tm, tn;
-    bf16_pick_tile(g.M, g.N, &tm, &tn);
+    bf16_pick_tile(g.M, g.N, planes, &tm, &tn);
     if (rec) {
-        gemm_record(rec, CDLRM_ROUTE_BF16, tm, tn, 0, 0, 1, g.vecA, g.vecB, 0);
+        gemm_record(rec, bf16_family(planes), tm, tn, 0, 0, 1, g.vecA, g.vecB, 0);
         return 0;
     }
     dim3 grid((unsigned)cdiv(g.N, 64 * tn), (unsigned)cdiv(g.M, 64 * tm), 1);
-    if (tm == 2 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 2, 2>(g, grid, s);
-    else if (tm == 1 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 1, 2>(g, grid, s);
-    else launch_gemm_bf16_v<A_KC, B_KC, 1, 1>(g, grid, s);
+    if (planes == 2) {
+        if (tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 1, 2, 2>(g, grid, s);
+        else launch_gemm_bf16_v<A_KC, B_KC, 1, 1, 2>(g, grid, s);
+    } else if (tm == 2 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 2, 2, 1>(g, grid, s);
+    else if (tm == 1 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 1, 2, 1>(g, grid, s);
+    else launch_gemm_bf16_v<A_KC, B_KC, 1, 1, 1>(g, grid, s);
     CDLRM_LAUNCH_CHECK();
     return 0;
 }
@@ -325,7 +388,15 @@ static inline int64_t bf16_wgrad_kchunk(int64_t M, int64_t tiles, int64_t max_sp
 }
 
 // weight-gradient problems (dW = dZ^T X layout: both operands contraction-strided) as grouped launches of <= GEMM_GROUP_MAX
-static inline int launch_wgrad_bf16(const GemmArgs* probs, int n, int va, int vb, hipStream_t s) {
+template <int PL>
+static inline void launch_wgrad_bf16_v(const GemmGroup& grp, unsigned blocks, int va, int vb, hipStream_t s) {
+    if (va && vb) CDLRM_LAUNCH_EV((k_gemm_bf16_group<true, true, PL>), dim3(blocks), dim3(256), 0, s, grp);
+    else if (va) CDLRM_LAUNCH_EV((k_gemm_bf16_group<true, false, PL>), dim3(blocks), dim3(256), 0, s, grp);
+    else if (vb) CDLRM_LAUNCH_EV((k_gemm_bf16_group<false, true, PL>), dim3(blocks), dim3(256), 0, s, grp);
+    else CDLRM_LAUNCH_EV((k_gemm_bf16_group<false, false, PL>), dim3(blocks), dim3(256), 0, s, grp);
+}
+
+static inline int launch_wgrad_bf16(const GemmArgs* probs, int n, int va, int vb, int planes, hipStream_t s) {
     for (int q0 = 0; q0 < n; q0 += GEMM_GROUP_MAX) {
         GemmGroup grp;
         memset(&grp, 0, sizeof(grp));
@@ -337,10 +408,8 @@ static inline int launch_wgrad_bf16(const GemmArgs* probs, int n, int va, int vb
             grp.n++;
         }
         grp.first[grp.n] = blocks;
-        if (va && vb) CDLRM_LAUNCH_EV((k_gemm_bf16_group<true, true>), dim3(blocks), dim3(256), 0, s, grp);
-        else if (va) CDLRM_LAUNCH_EV((k_gemm_bf16_group<true, false>), dim3(blocks), dim3(256), 0, s, grp);
-        else if (vb) CDLRM_LAUNCH_EV((k_gemm_bf16_group<false, true>), dim3(blocks), dim3(256), 0, s, grp);
-        else CDLRM_LAUNCH_EV((k_gemm_bf16_group<false, false>), dim3(blocks), dim3(256), 0, s, grp);
+        if (planes == 2) launch_wgrad_bf16_v<2>(grp, blocks, va, vb, s);
+        else launch_wgrad_bf16_v<1>(grp, blocks, va, vb, s);
     }
     CDLRM_LAUNCH_CHECK();
     return 0;

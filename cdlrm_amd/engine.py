@@ -824,8 +824,9 @@ class TrainEngine:
         the identity, so the result must equal the one-rank fast path bit for bit (tests/test_rccl_one_rank.py).
         matmul_precision: "fp32" (default: the reference's arithmetic) or "bf16" -- every MLP layer with K >= 32 and N >= 32
         runs its forward, dgrad and weight-gradient GEMMs on the bf16 matrix cores (operands rounded once to bf16 inside the
-        kernels, fp32 accumulation, storage and epilogues: DESIGN.md section 4, "bf16 mode").  A plain attribute: set it
-        between steps and the next step / evaluate() follows it."""
+        kernels, fp32 accumulation, storage and epilogues: DESIGN.md section 4, "bf16 mode") -- or "bf16x3": the same layers
+        with every operand split into two bf16 values and three exact products per product, near-fp32 results (DESIGN.md
+        section 4.2).  A plain attribute: set it between steps and the next step / evaluate() follows it."""
         self.cg, self.dlrm, self.host = cache_group, dlrm, host_tables
         self.ctx = cache_group.ctx
         self.dev = cache_group.weight.device
@@ -1103,15 +1104,19 @@ class TrainEngine:
 
     def _mm(self, l) -> dict:
         """The extra keyword of layer l's linear_fwd / linear_bwd calls: {} in fp32 mode (the calls stay what they were),
-        {"bf16": True} in bf16 mode for a layer the shape rule admits (ops.bf16_eligible)."""
+        {"bf16": True} in bf16 mode and {"precision": "bf16x3"} in bf16x3 mode for a layer the shape rule admits
+        (ops.bf16_eligible)."""
         if self.matmul_precision == "fp32":
             return {}
-        assert self.matmul_precision == "bf16", "matmul_precision: 'fp32' or 'bf16', not %r" % (self.matmul_precision,)
-        return {"bf16": True} if ops.bf16_eligible(l.out_features, self.W[l].shape[1]) else {}
+        assert self.matmul_precision in ("bf16", "bf16x3"), \
+            "matmul_precision: 'fp32', 'bf16' or 'bf16x3', not %r" % (self.matmul_precision,)
+        if not ops.bf16_eligible(l.out_features, self.W[l].shape[1]):
+            return {}
+        return {"bf16": True} if self.matmul_precision == "bf16" else {"precision": self.matmul_precision}
 
     def _wplans(self, buf):
         """(whole-network plan, (bottom plan, top plan) or None) of the weight gradients at the current matmul precision: the
-        fp32 plans of _buffers, or bf16 plans built on first use."""
+        fp32 plans of _buffers, or bf16 / bf16x3 plans built on first use."""
         if self.matmul_precision != "fp32":
             self._mm(self.bot[0][0])            # validates the attribute
         key = "wgrad_" + self.matmul_precision
@@ -1122,7 +1127,7 @@ class TrainEngine:
     def _build_wplans(self, buf, precision):
         """(whole, split) for _wplans.  split: (bottom plan, top plan), each with scratch of its own and the layers' parameters
         set, where the step takes the two sub-networks' weight gradients apart -- None otherwise.  whole: all layers in one call;
-        in fp32 on the scratch the layers' backward calls use (lin_work), in bf16 on scratch of its own and therefore only where
+        in fp32 on the scratch the layers' backward calls use (lin_work), in bf16 / bf16x3 on scratch of its own and so only where
         the step has no split plans (None otherwise)."""
         xs, dzs, layers, B, split = buf["wgrad_args"]
         gw = [self.gW[l] for l in layers]

@@ -49,7 +49,7 @@ def ProcessArgs(argv=None):
     parser.add_argument("--loss-function", type=str, default="mse")  # or bce or wbce
     # opt-in bf16 matrix-core mode of the MLP GEMMs (K >= 32 and N >= 32 layers; fp32 storage and accumulation): TrainEngine's
     # matmul_precision.  fp32 is the reference's arithmetic.
-    parser.add_argument("--matmul-precision", type=str, default="fp32", choices=["fp32", "bf16"])
+    parser.add_argument("--matmul-precision", type=str, default="fp32", choices=["fp32", "bf16", "bf16x3"])
     parser.add_argument("--loss-weights", type=str, default="1.0-1.0")
     parser.add_argument("--loss-threshold", type=float, default=0.0)
     parser.add_argument("--round-targets", type=bool, default=False)

@@ -556,28 +556,32 @@ ACT = {"none": 0, "relu": 1, "sigmoid": 2}
 
 GEMM_ALONE = 0x100        # include/cdlrm_hip.h: CDLRM_GEMM_ALONE
 GEMM_BF16 = 0x200         # include/cdlrm_hip.h: CDLRM_GEMM_BF16
-PRECISIONS = {"fp32": 0, "bf16": GEMM_BF16}
+GEMM_BF16X3 = 0x400       # include/cdlrm_hip.h: CDLRM_GEMM_BF16X3
+PRECISIONS = {"fp32": 0, "bf16": GEMM_BF16, "bf16x3": GEMM_BF16X3}
 
 
 def bf16_eligible(N: int, K: int) -> bool:
-    """The shape rule of the bf16 mode (CDLRM_GEMM_BF16): a layer with N outputs and K inputs runs its GEMMs in bf16 when
-    K >= 32 and N >= 32; other layers keep their fp32 routes."""
+    """The shape rule of the bf16 and bf16x3 modes (CDLRM_GEMM_BF16 / CDLRM_GEMM_BF16X3): a layer with N outputs and K inputs
+    runs its GEMMs in the mode when K >= 32 and N >= 32; other layers keep their fp32 routes."""
     return int(N) >= 32 and int(K) >= 32
 
 
-def _flags(alone: bool = False, bf16: bool = False) -> int:
-    return (GEMM_ALONE if alone else 0) | (GEMM_BF16 if bf16 else 0)
+def _flags(alone: bool = False, bf16: bool = False, precision: Optional[str] = None) -> int:
+    assert precision is None or not bf16, "bf16= and precision= are two spellings of one choice: pass one"
+    return (GEMM_ALONE if alone else 0) | (GEMM_BF16 if bf16 else 0) | (PRECISIONS[precision] if precision else 0)
 
 
 def linear_fwd(X: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor], Y: torch.Tensor, act: int, stream=None,
-               alone: bool = False, bf16: bool = False):
+               alone: bool = False, bf16: bool = False, precision: Optional[str] = None):
     """alone: no other GEMM runs beside this launch (scheduling hint, CDLRM_GEMM_ALONE).  bf16: the opt-in bf16 matrix-core
-    mode (CDLRM_GEMM_BF16: X and W rounded once to bf16 inside the kernel, fp32 accumulation; eligible shapes only)."""
+    mode (CDLRM_GEMM_BF16: X and W rounded once to bf16 inside the kernel, fp32 accumulation; eligible shapes only).
+    precision: a key of PRECISIONS instead of bf16= ("bf16" is bf16=True; "bf16x3": CDLRM_GEMM_BF16X3, X and W split into two
+    bf16 planes each, three exact products per product, near-fp32 results)."""
     M, K = X.shape
     N = W.shape[0]
     assert W.shape[1] == K and W.is_contiguous() and X.stride(1) == 1 and Y.stride(1) == 1
     check(_lib.lib().cdlrm_linear_fwd(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(b), Y.data_ptr(), Y.stride(0), M, N,
-                                      K, act | _flags(alone, bf16), stream_ptr(stream)))
+                                      K, act | _flags(alone, bf16, precision), stream_ptr(stream)))
 
 
 def linear_bwd_work(M: int, N: int, K: int, device) -> torch.Tensor:
@@ -586,20 +590,20 @@ def linear_bwd_work(M: int, N: int, K: int, device) -> torch.Tensor:
 
 
 def linear_bwd(X, W, Y, dY, dX, dW, db, act: int, work: torch.Tensor, stream=None, x_act: int = 0, alone: bool = False,
-               bf16: bool = False):
+               bf16: bool = False, precision: Optional[str] = None):
     """act: this layer's activation, applied backward to dY in place (0: dY already is the pre-activation
     gradient).  x_act: the activation that produced X; dX then leaves as the layer below's pre-activation gradient.
-    bf16: as linear_fwd (dgrad operands dZ and W, weight-gradient operands dZ and X)."""
+    bf16, precision: as linear_fwd (dgrad operands dZ and W, weight-gradient operands dZ and X)."""
     M, K = X.shape
     N = W.shape[0]
     check(_lib.lib().cdlrm_linear_bwd(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(Y), 0 if Y is None else Y.stride(0),
                                       dY.data_ptr(), dY.stride(0), ptr(dX), 0 if dX is None else dX.stride(0),
-                                      ptr(dW), ptr(db), M, N, K, act | _flags(alone, bf16), int(x_act), work.data_ptr(),
+                                      ptr(dW), ptr(db), M, N, K, act | _flags(alone, bf16, precision), int(x_act), work.data_ptr(),
                                       stream_ptr(stream)))
 
 
 ROUTE_FAMILIES = {0: None, 1: "smallk_rows", 2: "smallk", 3: "direct", 4: "staged", 5: "gemm2", 6: "gemm3", 7: "gemm",
-                  8: "bf16"}
+                  8: "bf16", 9: "bf16x3"}
 
 
 def _route(r: _lib.GemmRoute) -> Optional[dict]:
@@ -610,7 +614,8 @@ def _route(r: _lib.GemmRoute) -> Optional[dict]:
                 fast=r.fast)
 
 
-def linear_fwd_route(X, W, b, Y, act: int, alone: bool = False, n_cu: int = 256, bf16: bool = False) -> dict:
+def linear_fwd_route(X, W, b, Y, act: int, alone: bool = False, n_cu: int = 256, bf16: bool = False,
+                     precision: Optional[str] = None) -> dict:
     """The kernel linear_fwd(X, W, b, Y, act, alone=alone) launches, from the same decision code, without launching it:
     family (ROUTE_FAMILIES), tile (tm, tn), direct mode / aligned, splits, vec_a / vec_b, fast (the full-tile epilogue).
     X, W, b, Y: tensors or anything with .shape, .stride(0) and .data_ptr() -- addresses are looked at for their alignment
@@ -619,12 +624,12 @@ def linear_fwd_route(X, W, b, Y, act: int, alone: bool = False, n_cu: int = 256,
     N = W.shape[0]
     out = _lib.GemmRoute()
     check(_lib.raw().cdlrm_linear_fwd_route(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(b), Y.data_ptr(), Y.stride(0), M, N, K,
-                                            act | _flags(alone, bf16), None, int(n_cu), C.byref(out)))
+                                            act | _flags(alone, bf16, precision), None, int(n_cu), C.byref(out)))
     return _route(out)
 
 
 def linear_bwd_route(X, W, Y, dY, dX, dW, db, act: int, x_act: int = 0, alone: bool = False, n_cu: int = 256,
-                     bf16: bool = False):
+                     bf16: bool = False, precision: Optional[str] = None):
     """(dgrad, wgrad): the kernels linear_bwd with the same arguments launches for dX and for dW / db (None where it launches
     none), as linear_fwd_route."""
     M, K = X.shape
@@ -632,7 +637,7 @@ def linear_bwd_route(X, W, Y, dY, dX, dW, db, act: int, x_act: int = 0, alone: b
     out = (_lib.GemmRoute * 2)()
     check(_lib.raw().cdlrm_linear_bwd_route(X.data_ptr(), X.stride(0), W.data_ptr(), ptr(Y), 0 if Y is None else Y.stride(0),
                                             dY.data_ptr(), dY.stride(0), ptr(dX), 0 if dX is None else dX.stride(0), ptr(dW),
-                                            ptr(db), M, N, K, act | _flags(alone, bf16), int(x_act), 256, None,
+                                            ptr(db), M, N, K, act | _flags(alone, bf16, precision), int(x_act), 256, None,
                                             int(n_cu), out))
     return _route(out[0]), _route(out[1])
 
@@ -652,8 +657,8 @@ def mlp_wgrad_work(M: int, Ns: Sequence[int], Ks: Sequence[int], device, precisi
 
 class WgradPlan:
     """Host-side argument block of cdlrm_mlp_wgrad for a fixed set of layers and buffers (built once per batch shape;
-    `set_x` re-points one layer's input, e.g. the dense features of the current batch).  precision: "fp32", or "bf16" for
-    the opt-in bf16 mode of the eligible layers (K >= 32 and N >= 32; work from mlp_wgrad_work(..., precision="bf16"))."""
+    `set_x` re-points one layer's input, e.g. the dense features of the current batch).  precision: "fp32", or "bf16" /
+    "bf16x3" for the opt-in modes of the eligible layers (K >= 32 and N >= 32; work from mlp_wgrad_work(..., precision=...))."""
 
     def __init__(self, Xs, dZs, dWs, dbs, work: torch.Tensor, precision: str = "fp32"):
         import ctypes as C

@@ -463,6 +463,15 @@ int cdlrm_gather_interact_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, int64_t 
  * on its way into LDS, products are exact, accumulation is fp32 in a fixed order.  Storage, bias, activations, act' masks, bias
  * gradients, slab reductions and SGD steps stay fp32.  Other layers take their fp32 route as without the flag. */
 #define CDLRM_GEMM_BF16 0x200
+/* CDLRM_GEMM_BF16X3, usable wherever CDLRM_GEMM_BF16 is (never both in one call: an error): the opt-in split-operand mode,
+ * "near fp32" on the bf16 matrix cores.  Same layers, same kernels, same fp32 storage and epilogues; each operand element x is
+ * split into two bf16 values, h = bf16(x) and l = bf16(x - h) (round-to-nearest-even; l = 0 where h is Inf or NaN), and a product
+ * a * b is computed as al*bh + ah*bl + ah*bh -- three exact products, accumulated in fp32 in a fixed order; al*bl is dropped.
+ * |x - h - l| <= 2^-16 |x|, so a result differs from the exact one by about 3 * 2^-16 * (|A| |B|) at most plus the fp32
+ * accumulation error of 3 K terms: several times the error of an fp32 GEMM, ~1/500 of CDLRM_GEMM_BF16's.  A non-finite operand
+ * element makes the outputs of its own row / column non-finite and no others; a NaN may stand where fp32 arithmetic gives an Inf
+ * (Inf * l with l = 0). */
+#define CDLRM_GEMM_BF16X3 0x400
 int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y,
                      int64_t ld_y, int64_t M, int32_t N, int32_t K, int32_t act, void* stream);
 /* Backward of the same layer.  act != 0: dY is the gradient w.r.t. the layer's OUTPUT and is overwritten
@@ -490,6 +499,7 @@ int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, const float* 
 #define CDLRM_ROUTE_GEMM3 6         /* k_gemm3: the wide kernel, (32 tm) x (32 tn) tiles, one workgroup per CU */
 #define CDLRM_ROUTE_GEMM 7          /* k_gemm: register-staged, (64 tm) x (64 tn) tiles */
 #define CDLRM_ROUTE_BF16 8          /* k_gemm_bf16 / k_gemm_bf16_group (CDLRM_GEMM_BF16): bf16 MFMA, (64 tm) x (64 tn) tiles */
+#define CDLRM_ROUTE_BF16X3 9        /* the same kernels with two operand planes (CDLRM_GEMM_BF16X3): 64x64 or 64x128 tiles */
 typedef struct cdlrm_gemm_route {
     int32_t family;         /* CDLRM_ROUTE_* */
     int32_t tm, tn;         /* tile: k_gemm / k_gemm2 in units of 64 rows / columns, k_gemm3 IM / JN in units of 32 */
@@ -531,10 +541,11 @@ int cdlrm_mlp_wgrad_sgd(int32_t n_layers, const float* const* X, const int64_t* 
                         const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W, float* const* b,
                         float lr, int64_t M, const int32_t* N, const int32_t* K, void* work, void* stream);
 
-/* The same three calls with a flags word (0 or CDLRM_GEMM_BF16).  flags = 0: exactly cdlrm_mlp_wgrad_work_bytes /
+/* The same three calls with a flags word (0, CDLRM_GEMM_BF16 or CDLRM_GEMM_BF16X3).  flags = 0: exactly cdlrm_mlp_wgrad_work_bytes /
  * cdlrm_mlp_wgrad / cdlrm_mlp_wgrad_sgd.  CDLRM_GEMM_BF16: the layers with K[i] >= 32 and N[i] >= 32 run in bf16 (one grouped
  * launch, split-M slabs, the same fixed-order slab reduction with the SGD step inside), the others on their fp32 plan; work is
- * sized by cdlrm_mlp_wgrad_work_bytes_ex with the same flags. */
+ * sized by cdlrm_mlp_wgrad_work_bytes_ex with the same flags.  CDLRM_GEMM_BF16X3: the same plan and the same work size with
+ * the split operands. */
 uint64_t cdlrm_mlp_wgrad_work_bytes_ex(int32_t n_layers, int64_t M, const int32_t* N, const int32_t* K, int32_t flags);
 int cdlrm_mlp_wgrad_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
                        const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
