@@ -56,6 +56,10 @@ class EmbBwdRoute(C.Structure):
                 ("once_off", c_i64), ("apply_keys_off", c_i64)]
 
 
+class InteractRoute(C.Structure):
+    _fields_ = [("family", c_i32), ("d4", c_i32), ("ns", c_i32), ("reserved", c_i32), ("grid", c_i64), ("lds_bytes", c_i64)]
+
+
 # name -> (restype, argtypes); every symbol include/cdlrm_hip.h declares
 PROTOTYPES = {
     "cdlrm_abi_version": (C.c_int, []),
@@ -114,6 +118,7 @@ PROTOTYPES = {
     "cdlrm_gather_interact_fwd": (C.c_int, [vp, vp, c_i64, vp, c_i64, c_i64, c_i32, vp, c_i64, vp]),
     "cdlrm_gather_interact_bwd": (C.c_int, [vp, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, c_i32, c_i32, vp, vp]),
     "cdlrm_gather_interact_bwd_sgd": (C.c_int, [vp, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, c_i32, c_i32, vp, vp, c_i64, c_f32, vp]),
+    "cdlrm_interact_route": (C.c_int, [c_i32, c_i64, c_i32, c_i32, c_i32, c_i64, c_i32, C.POINTER(InteractRoute)]),
     "cdlrm_linear_fwd": (C.c_int, [vp, c_i64, vp, vp, vp, c_i64, c_i64, c_i32, c_i32, c_i32, vp]),
     "cdlrm_linear_bwd_work_bytes": (c_u64, [c_i64, c_i32, c_i32]),
     "cdlrm_linear_bwd": (C.c_int, [vp, c_i64, vp, vp, c_i64, vp, c_i64, vp, c_i64, vp, vp, c_i64, c_i32, c_i32,

@@ -133,15 +133,6 @@ __global__ void __launch_bounds__(BINFILE_TILE) k_binfile_window(const int32_t* 
 
 extern "C" int cdlrm_binfile_tile(void) { return BINFILE_TILE; }
 
-template <typename K>
-static int binfile_set_lds(K kernel, size_t lds, size_t* cached) {
-    if (lds > *cached) {
-        CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *cached = lds;
-    }
-    return 0;
-}
-
 extern "C" int cdlrm_binfile_window(const int32_t* rec, int64_t n, int32_t n_dense, int32_t n_cat, int64_t max_ind_range, float* X,
                                     int64_t* lS_i, int64_t lS_i_pitch, int64_t col0, float* T, void* stream) {
     CDLRM_REQUIRE(n >= 0 && col0 >= 0 && lS_i_pitch >= col0 + n, "the piece must lie inside the window rectangle's row");
@@ -154,12 +145,12 @@ extern "C" int cdlrm_binfile_window(const int32_t* rec, int64_t n, int32_t n_den
     CDLRM_REQUIRE(((uintptr_t)rec & 3) == 0 && ((uintptr_t)X & 3) == 0 && ((uintptr_t)T & 3) == 0 && ((uintptr_t)lS_i & 7) == 0,
                   "misaligned buffer");
     const dim3 grid((unsigned)cdiv(n, BINFILE_TILE)), block(BINFILE_TILE);
-    static size_t attr_any = 64 * 1024;         // what a kernel may ask for without the attribute
     if (n_dense == 13 && n_cat == 26) {         // (41 KiB)
         hipLaunchKernelGGL((k_binfile_window<13, 26>), grid, block, lds, (hipStream_t)stream, rec, n, 13, 26, max_ind_range, X, lS_i,
                            lS_i_pitch, col0, T);
     } else {
-        const int rc = binfile_set_lds(k_binfile_window<0, 0>, lds, &attr_any);
+        // (64 KiB: what a kernel may ask for without the attribute)
+        const int rc = cdlrm_grant_dynamic_lds<k_binfile_window<0, 0>, 64 * 1024>(lds);
         if (rc) return rc;
         hipLaunchKernelGGL((k_binfile_window<0, 0>), grid, block, lds, (hipStream_t)stream, rec, n, (int)n_dense, (int)n_cat,
                            max_ind_range, X, lS_i, lS_i_pitch, col0, T);

@@ -6,7 +6,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <atomic>
+#include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/cdlrm_hip.h"
@@ -76,6 +79,25 @@ void cdlrm_set_error(const char* fmt, ...);
 #define CDLRM_HIDDEN_DATA __attribute__((visibility("hidden")))
 #define CDLRM_LAUNCH_CHECK() CDLRM_HIP_CHECK(hipGetLastError())
 
+// A launch with more dynamic LDS than the kernel has been granted so far raises hipFuncAttributeMaxDynamicSharedMemorySize first.
+// One record per kernel instantiation (the statics of this template's instantiation), starting at Granted0 -- what the kernel may
+// ask for without the attribute, where the caller knows it.  The native tape's lanes call the library from several host
+// threads: the record is a relaxed atomic (the common case is one load), and a raise is made under a lock so that two first
+// launches cannot leave the smaller value behind.
+template <auto Kernel, size_t Granted0 = 0>
+static int cdlrm_grant_dynamic_lds(size_t lds) {
+    static std::atomic<size_t> granted{Granted0};
+    static std::mutex raising;
+    if (lds > granted.load(std::memory_order_relaxed)) {
+        std::lock_guard<std::mutex> lock(raising);
+        if (lds > granted.load(std::memory_order_relaxed)) {
+            CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            granted.store(lds, std::memory_order_relaxed);
+        }
+    }
+    return 0;
+}
+
 // Development switches (cdlrm_debug_set, tools/ab_step.py --attr debug:<key>): A/B a kernel path against the one it replaced
 // on ONE box in ONE process -- box-to-box spread is larger than most single-kernel gains.  All zero in production.
 //   0: 13-wide forward on the LDS-tiled kernel   1: workgroups per CU of the embedding backward's chunk kernel (0: 12, -1: one per
@@ -90,8 +112,7 @@ void cdlrm_set_error(const char* fmt, ...);
 //      (sixteen for a lone head) in flight instead of one head x four (eight): bit-identical.
 //      -DCDLRM_DEV builds ONLY (timing experiments that SKIP work; the shipped library refuses them): 1 = no embedding
 //      update, 2 = no slot sort
-//   7: bits: 1 = the epilogues before round 5 (operands fetched behind, not ahead of, their use); 2 = the fused gather +
-//      interaction forward on ONE slab slice (before round 6's double buffering) -- both bit-identical to the default
+//   7: bits: 1 = the epilogues before round 5 (operands fetched behind, not ahead of, their use) -- bit-identical to the default
 // No key makes the shipped library skip work: a number measured with any of them set is a number for the same arithmetic.
 extern CDLRM_HIDDEN_DATA int g_cdlrm_debug[8];
 

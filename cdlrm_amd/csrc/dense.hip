@@ -807,13 +807,30 @@ extern "C" int cdlrm_mlp_wgrad_route(int32_t n_layers, const float* const* X, co
 // =================================================================================================
 __device__ __forceinline__ int pair_base(int i, int itself) { return itself ? i * (i + 1) / 2 : i * (i - 1) / 2; }
 
+// ---- LDS footprints of the interaction kernels, floats per wave (a workgroup is four waves, each with a slice of its own) ----
+// Written down ONCE: the kernels carve their slices with these and interact_plan() sizes the launch's dynamic LDS from them.
+// Generic pair (any D): the feature tile [32][D + 1] + 32; the backward stages the pair gradients (padded to 4) behind it.
+__host__ __device__ constexpr int ia_generic_tile(int D) { return 32 * (D + 1) + 32; }
+__host__ __device__ constexpr int ia_generic_bwd_floats(int D, int npairs) { return ia_generic_tile(D) + ((npairs + 3) & ~3); }
+// Pipelined kernels (D = 4 D4 in 32 / 64 / 128 / 256).  A whole-row tile is [32][D + 4], a column slab's slice [32][D / NS + 4];
+// a staged dR row is the dense part + up to 32 * 33 / 2 pair gradients, a staged output row that + the pad word.
+__host__ __device__ constexpr int ia_row_tile(int D4) { return 32 * (4 * D4 + 4); }
+__host__ __device__ constexpr int ia_slab_slice(int D4, int NS) { return 32 * (4 * D4 / NS + 4); }
+__host__ __device__ constexpr int ia_grad_row(int D4) { return 4 * D4 + 528; }
+__host__ __device__ constexpr int ia_out_row(int D4) { return 4 * D4 + 532; }
+__host__ __device__ constexpr int ia_fwd_p_floats(int D4) { return ia_row_tile(D4); }
+__host__ __device__ constexpr int ia_bwd_p_floats(int D4) { return ia_row_tile(D4) + ia_grad_row(D4); }
+__host__ __device__ constexpr int ia_fwd_s_slices(int D4, int NS, bool DB) { return (DB ? 2 : 1) * ia_slab_slice(D4, NS); }
+__host__ __device__ constexpr int ia_fwd_s_floats(int D4, int NS, bool DB) { return ia_fwd_s_slices(D4, NS, DB) + ia_out_row(D4); }
+__host__ __device__ constexpr int ia_bwd_s_floats(int D4, int NS) { return ia_slab_slice(D4, NS) + ia_grad_row(D4); }
+
 __global__ void __launch_bounds__(256) k_interact_fwd(const float* __restrict__ feat, int64_t B, int F, int D, int itself,
                                                       float* __restrict__ R, int64_t ld_r) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ldt = D + 1;
-    float* Ts = smem + wave * (32 * ldt + 32);
-    for (int e = lane; e < 32 * ldt + 32; e += 64) Ts[e] = 0.f;
+    float* Ts = smem + wave * ia_generic_tile(D);
+    for (int e = lane; e < ia_generic_tile(D); e += 64) Ts[e] = 0.f;
     const int D4 = D >> 2;
     const int64_t nb = cdiv_dev(B, 4);
     for (int64_t blk = blockIdx.x; blk < nb; blk += gridDim.x) {
@@ -857,10 +874,9 @@ __global__ void __launch_bounds__(256) k_interact_bwd(const float* __restrict__ 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ldt = D + 1;
     const int npairs = pair_base(F, itself);
-    const int per_wave = 32 * ldt + 32 + ((npairs + 3) & ~3);
-    float* Ts = smem + wave * per_wave;
-    float* Gs = Ts + 32 * ldt + 32;
-    for (int e = lane; e < 32 * ldt + 32; e += 64) Ts[e] = 0.f;
+    float* Ts = smem + wave * ia_generic_bwd_floats(D, npairs);
+    float* Gs = Ts + ia_generic_tile(D);
+    for (int e = lane; e < ia_generic_tile(D); e += 64) Ts[e] = 0.f;
     const int D4 = D >> 2;
     const int off = itself ? 1 : 0;
     const int64_t nb = cdiv_dev(B, 4);
@@ -972,7 +988,8 @@ __global__ void __launch_bounds__(256) k_interact_fwd_p(const float* __restrict_
     constexpr int D = 4 * D4, PITCH = D + 4;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* Ts = smem + wave * (32 * PITCH);
+    static_assert(32 * PITCH == ia_row_tile(D4), "the tile the kernel walks is the tile the launch is sized for");
+    float* Ts = smem + wave * ia_fwd_p_floats(D4);
     for (int e = lane; e < 32 * PITCH; e += 64) Ts[e] = 0.f;        // rows F..31 stay zero
     const int FD4 = F * D4;
     const int64_t nw = (int64_t)gridDim.x * 4;
@@ -1082,12 +1099,12 @@ template <int D4, int NS, bool G, bool DB = false>
 __global__ void __launch_bounds__(256) k_interact_fwd_s(const float* __restrict__ feat, IaGather ga, int64_t B, int F,
                                                         int itself, float* __restrict__ R, int64_t ld_r) {
     constexpr int D = 4 * D4, CS = D4 / NS, DS = 4 * CS, PITCH = DS + 4, NR = CS / 2;
-    constexpr int OSW = D + 532;                    // output staging row: D + up to 528 pairs + the pad word
-    constexpr int TSW = (DB ? 2 : 1) * 32 * PITCH;  // slab slice(s) of a wave
+    constexpr int TSW = ia_fwd_s_slices(D4, NS, DB);    // slab slice(s) of a wave; behind them the output staging row (ia_out_row)
+    static_assert(32 * PITCH == ia_slab_slice(D4, NS), "the slice the kernel walks is the slice the launch is sized for");
     static_assert(!DB || (NS % 2 == 0 && DS / 16 >= 1), "double buffering alternates two slices over an even number of slabs");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* Ts = smem + wave * (TSW + OSW);
+    float* Ts = smem + wave * ia_fwd_s_floats(D4, NS, DB);
     float* Os = Ts + TSW;
     const int64_t nw = (int64_t)gridDim.x * 4;
     int64_t b = (int64_t)blockIdx.x * 4 + wave;
@@ -1294,12 +1311,13 @@ __global__ void __launch_bounds__(256) k_interact_bwd_p(const float* __restrict_
                                                         int64_t ld_r, int64_t B, int F, int itself, int x_act,
                                                         float* __restrict__ dfeat) {
     constexpr int D = 4 * D4, PITCH = D + 4;
-    constexpr int GMAX = D + 528;               // dense part + up to 32*33/2 pair gradients
+    constexpr int GMAX = ia_grad_row(D4);       // dense part + up to 32*33/2 pair gradients
     constexpr int NG = (GMAX / 4 + 63) / 64;
+    static_assert(32 * PITCH == ia_row_tile(D4), "the tile the kernel walks is the tile the launch is sized for");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 31, lk = lane >> 5;
-    float* Ts = smem + wave * (32 * PITCH + GMAX);
+    float* Ts = smem + wave * ia_bwd_p_floats(D4);
     float* Gs = Ts + 32 * PITCH;
     for (int e = lane; e < 32 * PITCH; e += 64) Ts[e] = 0.f;
     const int FD4 = F * D4;
@@ -1385,13 +1403,14 @@ __global__ void __launch_bounds__(256, (G && D4 <= 32) ? 2 : 1) k_interact_bwd_s
                                                         const float* __restrict__ dR, int64_t ld_r, int64_t B, int F,
                                                         int itself, int x_act, float* __restrict__ dfeat) {
     constexpr int D = 4 * D4, CS = D4 / NS, DS = 4 * CS, PITCH = DS + 4, NR = CS / 2;
-    constexpr int GMAX = D + 528;               // dense part + up to 32*33/2 pair gradients
+    constexpr int GMAX = ia_grad_row(D4);       // dense part + up to 32*33/2 pair gradients
     constexpr int NG = (GMAX / 4 + 63) / 64;
     static_assert(DS % 32 == 0, "a slab is a whole number of 32-column MFMA blocks");
+    static_assert(32 * PITCH == ia_slab_slice(D4, NS), "the slice the kernel walks is the slice the launch is sized for");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 31, lk = lane >> 5;
-    float* Ts = smem + wave * (32 * PITCH + GMAX);
+    float* Ts = smem + wave * ia_bwd_s_floats(D4, NS);
     float* Gs = Ts + 32 * PITCH;
     float* Os = Gs + D;                         // [16][32] output staging: the pair part of the dR row, dead once S is built
     const int off = itself ? 1 : 0;
@@ -1545,12 +1564,123 @@ __global__ void __launch_bounds__(256, (G && D4 <= 32) ? 2 : 1) k_interact_bwd_s
     for (b += nw; b < B; b += nw) one(b);
 }
 
-template <typename K>
-static int interact_set_lds(K kernel, size_t lds, size_t* cached) {
-    if (lds > *cached) {
-        CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        *cached = lds;
+// ---- the host side of the interaction: one plan, five entry points ------------------------------------------------------
+// What a call launches -- kernel family, grid, dynamic LDS -- is a pure function of its shape, its row pitch and the alignment
+// of its operands.  interact_plan() is that function; the entry points check their arguments and launch what it says,
+// cdlrm_interact_route() reports it.
+enum { IA_FWD = CDLRM_IA_OP_FWD, IA_BWD = CDLRM_IA_OP_BWD, IA_GATHER_FWD = CDLRM_IA_OP_GATHER_FWD,
+       IA_GATHER_BWD = CDLRM_IA_OP_GATHER_BWD, IA_GATHER_BWD_SGD = CDLRM_IA_OP_GATHER_BWD_SGD };
+
+struct IaPlan {
+    int family;         // CDLRM_IA_*; 0: no kernel takes the shape (the gather ops outside their shapes)
+    int d4, ns;         // D / 4; column slabs per sample (slab families: slabs of 32 columns)
+    int64_t grid;       // workgroups of 256 lanes: a wave per sample, striding
+    size_t lds;         // dynamic LDS bytes of the launch
+};
+
+// the fused forward is double-buffered wherever a sample is more than one slab (D = 32: nothing to alternate)
+constexpr bool ia_gather_fwd_db(int d4) { return d4 > 8; }
+
+// aligned_r: R (forward) / dR (backward) is 16-byte aligned; aligned_dfeat: dfeat is.  The gather ops REQUIRE whole-float4
+// rows (their entry points refuse anything else), so for them the two are not looked at.
+static IaPlan interact_plan(int op, int64_t B, int F, int D, int itself, int64_t ld_r, bool aligned_r, bool aligned_dfeat) {
+    IaPlan p{};
+    const int npairs = itself ? F * (F + 1) / 2 : F * (F - 1) / 2, width = D + npairs;
+    const bool piped = D == 32 || D == 64 || D == 128 || D == 256;      // the software-pipelined kernels' widths
+    const bool gather = op >= IA_GATHER_FWD;
+    if (gather && !(piped && F > 16 && F <= 32)) return p;
+    // whole-float4 rows of R / dR: the row pitch holds the last (padded) word
+    const bool vec = gather || (ld_r % 4 == 0 && aligned_r && ld_r >= ((width + 3) & ~3));
+    const int d4 = D / 4, ns = d4 / 8;
+    int floats;         // per wave
+    int64_t cap;        // workgroups (256 CUs)
+    p.d4 = d4;
+    if (op == IA_GATHER_FWD) {
+        // ONE workgroup per CU, a wave walks 8 samples of a c3 batch: in the step 23.6 us against 25.2 on two and 26.5 on three
+        // (bench.py --debug 4=<n>; stand-alone 27.4 / 27.2 / 27.2).  Two samples' rows in flight per wave (a second register set,
+        // the loop unrolled by two) measured SLOWER in the step, twice: 25.1 us as hipcc compiled it (its wait counts at the joins
+        // of the unrolled loop wait for part of the younger sample's rows at every slab), and 25.7 against 24.0 us on one box
+        // with every vector-memory instruction issued from inline asm and ONE counted wait per sample (exact: vmcnt(19) in front
+        // of the address arithmetic, nothing else; bit-identical once the 16-byte stores had wait states behind them -- the
+        // compiler reuses a store's data registers at once when it does not know the statement is a store).  More rows in flight
+        // do not help: a c3 launch is 1024 waves x 8 samples, 2.9 us per sample against 2.3 us at c5 (64 samples per wave, 0.89
+        // of 8 TB/s) -- the difference is ramp, and neither variant shortens it.  Both removed.
+        // (slabs of 256 or 512 B instead of 128 -- NS = 2, 1 at D = 128 -- measured the same in the step and 24.6-25.8 / 26.6-28.3
+        //  against 27.2 us stand-alone; the variants were removed)
+        const bool db = ia_gather_fwd_db(d4);
+        p.family = db ? CDLRM_IA_SLAB_DB : CDLRM_IA_SLAB;
+        p.ns = ns;
+        floats = ia_fwd_s_floats(d4, ns, db);
+        cap = 256 * (g_cdlrm_debug[4] > 0 ? g_cdlrm_debug[4] : 1);
+    } else if (gather) {
+        p.family = CDLRM_IA_SLAB;
+        p.ns = ns;
+        floats = ia_bwd_s_floats(d4, ns);
+        cap = 256 * (g_cdlrm_debug[5] > 0 ? g_cdlrm_debug[5] : (D == 256 ? 1 : 2));
+    } else if (op == IA_FWD && piped && vec) {
+        // column-slab kernel, slabs of 32 columns, ONE workgroup per CU (each wave streams 8 samples at B = 8192).  Measured at
+        // B = 8192, F = 27, D = 128 (tools/interact_ablate.hip): 22.6 us against 29.3 for the whole-row staging kernel at two
+        // workgroups per CU (26.9 at one); 2 / 4 / 8 slabs at one workgroup per CU 23.3 / 22.6 / 23.3, at two 24.7 / 24.2 / 24.3,
+        // at three to five 26.6-27.5 -- the finer-grained pipeline, not occupancy, is what pays
+        p.family = CDLRM_IA_SLAB;
+        p.ns = ns;
+        floats = ia_fwd_s_floats(d4, ns, false);
+        cap = 256;
+    } else if (op == IA_FWD && piped) {
+        // output rows that cannot leave as float4 words (pitch or alignment): whole-row staging, scalar stores
+        p.family = CDLRM_IA_ROW;
+        floats = ia_fwd_p_floats(d4);
+        cap = 512;              // 2 workgroups per CU (LDS), each wave streams ~4 samples
+    } else if (op == IA_FWD) {
+        p.family = CDLRM_IA_GENERIC;
+        floats = ia_generic_tile(D);
+        cap = 2048;
+    } else if (piped && vec && F > 16 && aligned_dfeat) {
+        // column-slab kernel, slabs of 32 columns, two workgroups per CU.  Measured at B = 8192, F = 27, D = 128
+        // (tools/interact_ablate.hip): 41.2 us against 49.1 for the whole-row staging kernel; 4 slabs on 256 / 512 / 768 workgroups
+        // 45.6 / 41.2 / 44.2, 2 slabs 46.7 / 51.8 / 54.2
+        // (D = 256: 336 registers per lane, one wave per SIMD -- one workgroup per CU is all that fits: 96.7 us against 102.2)
+        p.family = CDLRM_IA_SLAB;
+        p.ns = ns;
+        floats = ia_bwd_s_floats(d4, ns);
+        cap = D == 256 ? 256 : 512;
+    } else if (piped && D != 256 && vec) {
+        // F <= 16 (or an unaligned dfeat): whole-row staging, the accumulators stored straight from their lanes
+        p.family = CDLRM_IA_ROW;
+        floats = ia_bwd_p_floats(d4);
+        cap = 512;
+    } else {
+        p.family = CDLRM_IA_GENERIC;
+        floats = ia_generic_bwd_floats(D, npairs);
+        cap = 2048;
     }
+    p.grid = cdiv(B, 4) < cap ? cdiv(B, 4) : cap;
+    p.lds = (size_t)4 * floats * sizeof(float);
+    return p;
+}
+
+// run-time D4 of the pipelined kernels -> compile-time: fn(std::integral_constant<int, D4>{})
+template <typename Fn>
+static int ia_with_d4(int d4, Fn&& fn) {
+    switch (d4) {
+        case 8: return fn(std::integral_constant<int, 8>{});
+        case 16: return fn(std::integral_constant<int, 16>{});
+        case 32: return fn(std::integral_constant<int, 32>{});
+        case 64: return fn(std::integral_constant<int, 64>{});
+    }
+    cdlrm_set_error("interaction: no pipelined kernel at D = %d", 4 * d4);
+    return CDLRM_EINVAL;
+}
+
+// carry: an attached completion event (CdlrmStopScope of the entry point) rides on the launch as its stop event
+template <auto Kernel, typename... Args>
+static int ia_launch(const IaPlan& p, void* stream, bool carry, Args... args) {
+    const int rc = cdlrm_grant_dynamic_lds<Kernel>(p.lds);
+    if (rc) return rc;
+    const dim3 grid((unsigned)p.grid), block(256);
+    if (carry) CDLRM_LAUNCH_EV(Kernel, grid, block, p.lds, (hipStream_t)stream, args...);
+    else hipLaunchKernelGGL(Kernel, grid, block, p.lds, (hipStream_t)stream, args...);
+    CDLRM_LAUNCH_CHECK();
     return 0;
 }
 
@@ -1559,64 +1689,17 @@ extern "C" int cdlrm_interact_fwd(const float* feat, int64_t B, int32_t F, int32
     CDLRM_REQUIRE(feat && R && F >= 1 && F <= 32 && D >= 4 && D % 4 == 0 && D <= 512, "unsupported shape (F<=32, D%4==0)");
     CDLRM_REQUIRE(aligned16(feat) && ld_r >= D + (itself ? F * (F + 1) / 2 : F * (F - 1) / 2), "alignment / ld_r");
     if (B == 0) return 0;
-    if (D == 32 || D == 64 || D == 128 || D == 256) {
-        const int width_p = D + (itself ? F * (F + 1) / 2 : F * (F - 1) / 2);
-        // whole-float4 output rows: the row pitch holds the last (padded) word
-        const bool vec_out_p = ld_r % 4 == 0 && aligned16(R) && ld_r >= ((width_p + 3) & ~3);
-        int64_t gp = cdiv(B, 4);
-        if (vec_out_p) {
-            // column-slab kernel, slabs of 32 columns, ONE workgroup per CU (each wave streams 8 samples at B = 8192).  Measured at
-            // B = 8192, F = 27, D = 128 (tools/interact_ablate.hip): 22.6 us against 29.3 for the whole-row staging kernel at two
-            // workgroups per CU (26.9 at one); 2 / 4 / 8 slabs at one workgroup per CU 23.3 / 22.6 / 23.3, at two 24.7 / 24.2 / 24.3,
-            // at three to five 26.6-27.5 -- the finer-grained pipeline, not occupancy, is what pays
-            const size_t lds_s = (size_t)4 * (32 * 36 + D + 532) * sizeof(float);
-            if (gp > 256) gp = 256;
-            static size_t s32 = 0, s64 = 0, s128 = 0, s256 = 0;
-#define IFWD_S(D4_, A_)                                                                                               \
-    do {                                                                                                              \
-        int rc = interact_set_lds(k_interact_fwd_s<D4_, D4_ / 8, false>, lds_s, &A_);                                 \
-        if (rc) return rc;                                                                                            \
-        hipLaunchKernelGGL((k_interact_fwd_s<D4_, D4_ / 8, false>), dim3((unsigned)gp), dim3(256), lds_s,             \
-                           (hipStream_t)stream, feat, IaGather{}, B, F, itself, R, ld_r);                             \
-    } while (0)
-            if (D == 32) IFWD_S(8, s32);
-            else if (D == 64) IFWD_S(16, s64);
-            else if (D == 128) IFWD_S(32, s128);
-            else IFWD_S(64, s256);
-#undef IFWD_S
-            CDLRM_LAUNCH_CHECK();
-            return 0;
-        }
-        // output rows that cannot leave as float4 words (pitch or alignment): whole-row staging, scalar stores
-        const size_t ldsp = (size_t)4 * 32 * (D + 4) * sizeof(float);
-        if (gp > 512) gp = 512;             // 2 workgroups per CU (LDS), each wave streams ~4 samples
-        static size_t a32 = 0, a64 = 0, a128 = 0, a256 = 0;
-#define IFWD(D4_, A_)                                                                                          \
-    do {                                                                                                       \
-        int rc = interact_set_lds(k_interact_fwd_p<D4_>, ldsp, &A_);                                           \
-        if (rc) return rc;                                                                                     \
-        hipLaunchKernelGGL((k_interact_fwd_p<D4_>), dim3((unsigned)gp), dim3(256), ldsp, (hipStream_t)stream,  \
-                           feat, B, F, itself, R, ld_r);                                                       \
-    } while (0)
-        if (D == 32) IFWD(8, a32);
-        else if (D == 64) IFWD(16, a64);
-        else if (D == 128) IFWD(32, a128);
-        else IFWD(64, a256);
-#undef IFWD
-        CDLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lds = (size_t)4 * (32 * (D + 1) + 32) * sizeof(float);
-    static size_t attr = 0;
-    if (lds > attr) {
-        CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)k_interact_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
-    int64_t gx = cdiv(B, 4);
-    if (gx > 2048) gx = 2048;
-    hipLaunchKernelGGL(k_interact_fwd, dim3((unsigned)gx), dim3(256), lds, (hipStream_t)stream, feat, B, F, D, itself, R, ld_r);
-    CDLRM_LAUNCH_CHECK();
-    return 0;
+    const IaPlan p = interact_plan(IA_FWD, B, F, D, itself, ld_r, aligned16(R), false);
+    if (p.family == CDLRM_IA_SLAB)
+        return ia_with_d4(p.d4, [&](auto d4) {
+            constexpr int D4 = decltype(d4)::value;
+            return ia_launch<k_interact_fwd_s<D4, D4 / 8, false>>(p, stream, false, feat, IaGather{}, B, F, itself, R, ld_r);
+        });
+    if (p.family == CDLRM_IA_ROW)
+        return ia_with_d4(p.d4, [&](auto d4) {
+            return ia_launch<k_interact_fwd_p<decltype(d4)::value>>(p, stream, false, feat, B, F, itself, R, ld_r);
+        });
+    return ia_launch<k_interact_fwd>(p, stream, false, feat, B, F, D, itself, R, ld_r);
 }
 
 extern "C" int cdlrm_interact_bwd(const float* feat, const float* dR, int64_t ld_r, int64_t B, int32_t F, int32_t D,
@@ -1625,79 +1708,50 @@ extern "C" int cdlrm_interact_bwd(const float* feat, const float* dR, int64_t ld
     CDLRM_REQUIRE(feat && dR && dfeat && F >= 1 && F <= 32 && D >= 4 && D % 4 == 0 && D <= 512, "unsupported shape");
     CDLRM_REQUIRE(aligned16(feat), "alignment");
     if (B == 0) return 0;
-    const int npairs = itself ? F * (F + 1) / 2 : F * (F - 1) / 2;
-    const bool vec_in = ld_r % 4 == 0 && aligned16(dR) && ld_r >= ((D + npairs + 3) & ~3);
-    if ((D == 32 || D == 64 || D == 128 || D == 256) && vec_in && F > 16 && aligned16(dfeat)) {
-        // column-slab kernel, slabs of 32 columns, two workgroups per CU.  Measured at B = 8192, F = 27, D = 128
-        // (tools/interact_ablate.hip): 41.2 us against 49.1 for the whole-row staging kernel; 4 slabs on 256 / 512 / 768 workgroups
-        // 45.6 / 41.2 / 44.2, 2 slabs 46.7 / 51.8 / 54.2
-        const size_t lds_s = (size_t)4 * (32 * 36 + D + 528) * sizeof(float);
-        int64_t gp = cdiv(B, 4);
-        // (D = 256: 336 registers per lane, one wave per SIMD -- one workgroup per CU is all that fits: 96.7 us against 102.2)
-        const int64_t gmax = D == 256 ? 256 : 512;
-        if (gp > gmax) gp = gmax;
-        static size_t s32 = 0, s64 = 0, s128 = 0, s256 = 0;
-#define IBWD_S(D4_, A_)                                                                                               \
-    do {                                                                                                              \
-        int rc = interact_set_lds(k_interact_bwd_s<D4_, D4_ / 8, false>, lds_s, &A_);                                 \
-        if (rc) return rc;                                                                                            \
-        CDLRM_LAUNCH_EV((k_interact_bwd_s<D4_, D4_ / 8, false>), dim3((unsigned)gp), dim3(256), lds_s,                \
-                        (hipStream_t)stream, feat, IaGather{}, dR, ld_r, B, F, itself, x_act, dfeat);                 \
-    } while (0)
-        if (D == 32) IBWD_S(8, s32);
-        else if (D == 64) IBWD_S(16, s64);
-        else if (D == 128) IBWD_S(32, s128);
-        else IBWD_S(64, s256);
-#undef IBWD_S
-        CDLRM_LAUNCH_CHECK();
-        return 0;
+    const IaPlan p = interact_plan(IA_BWD, B, F, D, itself, ld_r, aligned16(dR), aligned16(dfeat));
+    if (p.family == CDLRM_IA_SLAB)
+        return ia_with_d4(p.d4, [&](auto d4) {
+            constexpr int D4 = decltype(d4)::value;
+            return ia_launch<k_interact_bwd_s<D4, D4 / 8, false>>(p, stream, true, feat, IaGather{}, dR, ld_r, B, F, itself, x_act,
+                                                                  dfeat);
+        });
+    if (p.family == CDLRM_IA_ROW)
+        return ia_with_d4(p.d4, [&](auto d4) {
+            constexpr int D4 = decltype(d4)::value;
+            if constexpr (D4 <= 32)     // (the plan has no whole-row backward at D = 256)
+                return ia_launch<k_interact_bwd_p<D4>>(p, stream, true, feat, dR, ld_r, B, F, itself, x_act, dfeat);
+            else
+                return (int)CDLRM_EINVAL;
+        });
+    CDLRM_REQUIRE(p.lds <= 160 * 1024, "LDS budget");
+    return ia_launch<k_interact_bwd>(p, stream, false, feat, dR, ld_r, B, F, D, itself, x_act, dfeat);
+}
+
+extern "C" int cdlrm_interact_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r,
+                                    int32_t aligned, struct cdlrm_interact_route* out) {
+    CDLRM_REQUIRE(out && op >= IA_FWD && op <= IA_GATHER_BWD_SGD && B >= 0, "bad argument");
+    CDLRM_REQUIRE(F >= 1 && F <= 32 && D >= 4 && D % 4 == 0 && D <= 512, "unsupported shape (F<=32, D%4==0)");
+    const int width = D + (itself ? F * (F + 1) / 2 : F * (F - 1) / 2);
+    const IaPlan p = interact_plan(op, B, F, D, itself, ld_r, aligned & 1, aligned & 2);
+    // what the entry point of `op` refuses
+    if (op == IA_FWD) CDLRM_REQUIRE(ld_r >= width, "alignment / ld_r");
+    if (op == IA_BWD && p.family == CDLRM_IA_GENERIC) CDLRM_REQUIRE(p.lds <= 160 * 1024, "LDS budget");
+    if (op >= IA_GATHER_FWD) {
+        CDLRM_REQUIRE(p.family, "unsupported shape (D in 32/64/128/256, 16 < T + 1 <= 32)");
+        CDLRM_REQUIRE(ld_r % 4 == 0 && (aligned & 1) && ld_r >= ((width + 3) & ~3) && (op == IA_GATHER_FWD || (aligned & 2)),
+                      "whole-float4 output / gradient rows");
     }
-    if ((D == 32 || D == 64 || D == 128) && vec_in) {
-        // F <= 16 (or an unaligned dfeat): whole-row staging, the accumulators stored straight from their lanes
-        const size_t ldsp = (size_t)4 * (32 * (D + 4) + D + 528) * sizeof(float);
-        int64_t gp = cdiv(B, 4);
-        if (gp > 512) gp = 512;
-        static size_t b32 = 0, b64 = 0, b128 = 0;
-#define IBWD(D4_, A_)                                                                                          \
-    do {                                                                                                       \
-        int rc = interact_set_lds(k_interact_bwd_p<D4_>, ldsp, &A_);                                           \
-        if (rc) return rc;                                                                                     \
-        CDLRM_LAUNCH_EV((k_interact_bwd_p<D4_>), dim3((unsigned)gp), dim3(256), ldsp, (hipStream_t)stream,     \
-                        feat, dR, ld_r, B, F, itself, x_act, dfeat);                                           \
-    } while (0)
-        if (D == 32) IBWD(8, b32);
-        else if (D == 64) IBWD(16, b64);
-        else IBWD(32, b128);
-#undef IBWD
-        CDLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lds = (size_t)4 * (32 * (D + 1) + 32 + ((npairs + 3) & ~3)) * sizeof(float);
-    CDLRM_REQUIRE(lds <= 160 * 1024, "LDS budget");
-    static size_t attr = 0;
-    if (lds > attr) {
-        CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)k_interact_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = lds;
-    }
-    int64_t gx = cdiv(B, 4);
-    if (gx > 2048) gx = 2048;
-    hipLaunchKernelGGL(k_interact_bwd, dim3((unsigned)gx), dim3(256), lds, (hipStream_t)stream, feat, dR, ld_r, B, F, D,
-                       itself, x_act, dfeat);
-    CDLRM_LAUNCH_CHECK();
+    out->family = p.family; out->d4 = p.d4; out->ns = p.ns; out->reserved = 0;
+    out->grid = p.grid; out->lds_bytes = (int64_t)p.lds;
     return 0;
 }
 
 // ---- fused gather + interaction (Criteo layout: one index per bag, so a bag's sum-pool is its cache row) ------------------
 // cached EmbeddingBag forward (model_no_ddp.py:200-203) + interact_features "dot" (:272-293) in one launch, and the
 // interaction backward reading the same rows again: the [B, T, D] block between the two operators is never written or read.
-// Shapes the column-slab kernels take: D in {32, 64, 128, 256}, 16 < F = T + 1 <= 32, float4 output / gradient rows.
-static bool gather_interact_shape_ok(const cdlrm_ctx* ctx) {
-    const int D = ctx->D, F = ctx->T + 1;
-    return (D == 32 || D == 64 || D == 128 || D == 256) && F > 16 && F <= 32;
-}
-
+// Shapes the column-slab kernels take (interact_plan): D in {32, 64, 128, 256}, 16 < F = T + 1 <= 32, float4 output / gradient rows.
 extern "C" int cdlrm_gather_interact_supported(cdlrm_ctx* ctx) {
-    return ctx && gather_interact_shape_ok(ctx) ? 1 : 0;
+    return ctx && interact_plan(IA_GATHER_FWD, 1, ctx->T + 1, ctx->D, 0, 0, true, true).family ? 1 : 0;
 }
 
 extern "C" int cdlrm_gather_interact_fwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
@@ -1706,8 +1760,9 @@ extern "C" int cdlrm_gather_interact_fwd(cdlrm_ctx* ctx, const int32_t* slots, i
     CDLRM_CLEAR_STALE();
     CDLRM_REQUIRE(ctx && slots && x && R, "null argument");
     CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
-    CDLRM_REQUIRE(gather_interact_shape_ok(ctx), "unsupported shape (D in 32/64/128/256, 16 < T + 1 <= 32): gather + interaction as two calls");
     const int D = ctx->D, F = ctx->T + 1;
+    const IaPlan p = interact_plan(IA_GATHER_FWD, B, F, D, itself, ld_r, aligned16(R), false);
+    CDLRM_REQUIRE(p.family, "unsupported shape (D in 32/64/128/256, 16 < T + 1 <= 32): gather + interaction as two calls");
     const int width = D + (itself ? F * (F + 1) / 2 : F * (F - 1) / 2);
     CDLRM_REQUIRE(n >= B && (int64_t)ctx->T * n < INT32_MAX && aligned16(x) && ld_x % 4 == 0 && ld_x >= D,
                   "slot pitch / dense-feature rows");
@@ -1721,46 +1776,16 @@ extern "C" int cdlrm_gather_interact_fwd(cdlrm_ctx* ctx, const int32_t* slots, i
     hipEvent_t se = cdlrm_take_stop_event((hipStream_t)stream);
     if (!ev1 && se) { ev1 = se; se = nullptr; }
     IaGather ga{ctx->d_tab, reinterpret_cast<const v4f*>(ctx->weight), slots, n, ld_x / 4};
-    const size_t lds_s = (size_t)4 * (32 * 36 + D + 532) * sizeof(float);
-    int64_t gp = cdiv(B, 4);
-    // ONE workgroup per CU, a wave walks 8 samples of a c3 batch: in the step 23.6 us against 25.2 on two and 26.5 on three
-    // (bench.py --debug 4=<n>; stand-alone 27.4 / 27.2 / 27.2).  Two samples' rows in flight per wave (a second register set,
-    // the loop unrolled by two) measured SLOWER in the step, twice: 25.1 us as hipcc compiled it (its wait counts at the joins
-    // of the unrolled loop wait for part of the younger sample's rows at every slab), and 25.7 against 24.0 us on one box
-    // with every vector-memory instruction issued from inline asm and ONE counted wait per sample (exact: vmcnt(19) in front
-    // of the address arithmetic, nothing else; bit-identical once the 16-byte stores had wait states behind them -- the
-    // compiler reuses a store's data registers at once when it does not know the statement is a store).  More rows in flight
-    // do not help: a c3 launch is 1024 waves x 8 samples, 2.9 us per sample against 2.3 us at c5 (64 samples per wave, 0.89
-    // of 8 TB/s) -- the difference is ramp, and neither variant shortens it.  Both removed
-    const int per_cu = g_cdlrm_debug[4] > 0 ? g_cdlrm_debug[4] : 1;
-    if (gp > 256 * per_cu) gp = 256 * per_cu;
-    static size_t s32 = 0, s64 = 0, s128 = 0, s256 = 0;
-#define GIFWD(D4_, A_)                                                                                                \
-    do {                                                                                                              \
-        int rc = interact_set_lds(k_interact_fwd_s<D4_, D4_ / 8, true>, lds_s, &A_);                                  \
-        if (rc) return rc;                                                                                            \
-        hipExtLaunchKernelGGL((k_interact_fwd_s<D4_, D4_ / 8, true>), dim3((unsigned)gp), dim3(256), lds_s,           \
-                              (hipStream_t)stream, ev0, ev1, 0, x, ga, B, F, itself, R, ld_r);                        \
-    } while (0)
-    // (slabs of 256 or 512 B instead of 128 -- NS = 2, 1 at D = 128 -- measured the same in the step and 24.6-25.8 / 26.6-28.3 against
-    //  27.2 us stand-alone; the variants were removed)
-    // the double-buffered form (round 6; cdlrm_debug_set(7, 2): the single-slice form, for A/Bs -- bit-identical)
-    static size_t d64 = 0, d128 = 0, d256 = 0;
-    const size_t lds_d = (size_t)4 * (2 * 32 * 36 + D + 532) * sizeof(float);
-#define GIFWD_DB(D4_, A_)                                                                                             \
-    do {                                                                                                              \
-        int rc = interact_set_lds(k_interact_fwd_s<D4_, D4_ / 8, true, true>, lds_d, &A_);                            \
-        if (rc) return rc;                                                                                            \
-        hipExtLaunchKernelGGL((k_interact_fwd_s<D4_, D4_ / 8, true, true>), dim3((unsigned)gp), dim3(256), lds_d,     \
-                              (hipStream_t)stream, ev0, ev1, 0, x, ga, B, F, itself, R, ld_r);                        \
-    } while (0)
-    const bool db = !(g_cdlrm_debug[7] & 2);
-    if (D == 32) GIFWD(8, s32);                    // (one slab per sample: nothing to alternate)
-    else if (D == 64) { if (db) GIFWD_DB(16, d64); else GIFWD(16, s64); }
-    else if (D == 128) { if (db) GIFWD_DB(32, d128); else GIFWD(32, s128); }
-    else { if (db) GIFWD_DB(64, d256); else GIFWD(64, s256); }
-#undef GIFWD_DB
-#undef GIFWD
+    const int rc = ia_with_d4(p.d4, [&](auto d4) {
+        constexpr int D4 = decltype(d4)::value;
+        constexpr auto kernel = k_interact_fwd_s<D4, D4 / 8, true, ia_gather_fwd_db(D4)>;
+        const int rc = cdlrm_grant_dynamic_lds<kernel>(p.lds);
+        if (rc) return rc;
+        hipExtLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3(256), p.lds, (hipStream_t)stream, ev0, ev1, 0, x, ga, B, F,
+                              itself, R, ld_r);
+        return 0;
+    });
+    if (rc) return rc;
     if (se) CDLRM_HIP_CHECK(hipEventRecord(se, (hipStream_t)stream));
     CDLRM_LAUNCH_CHECK();
     return 0;
@@ -1772,40 +1797,21 @@ static int cdlrm_gather_interact_bwd_core(cdlrm_ctx* ctx, const int32_t* slots, 
     CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
     CDLRM_REQUIRE(ctx && slots && x && dR && dfeat, "null argument");
     CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
-    CDLRM_REQUIRE(gather_interact_shape_ok(ctx), "unsupported shape (D in 32/64/128/256, 16 < T + 1 <= 32): cdlrm_interact_bwd on a gathered block");
     const int D = ctx->D, F = ctx->T + 1;
+    const IaPlan p = interact_plan(once ? IA_GATHER_BWD_SGD : IA_GATHER_BWD, B, F, D, itself, ld_r, aligned16(dR), aligned16(dfeat));
+    CDLRM_REQUIRE(p.family, "unsupported shape (D in 32/64/128/256, 16 < T + 1 <= 32): cdlrm_interact_bwd on a gathered block");
     const int npairs = itself ? F * (F + 1) / 2 : F * (F - 1) / 2;
     CDLRM_REQUIRE(n >= B && (int64_t)ctx->T * n < INT32_MAX && aligned16(x) && ld_x % 4 == 0 && ld_x >= D,
                   "slot pitch / dense-feature rows");
     CDLRM_REQUIRE(ld_r % 4 == 0 && aligned16(dR) && ld_r >= ((D + npairs + 3) & ~3) && aligned16(dfeat), "whole-float4 gradient rows");
     if (B == 0) return 0;
     IaGather ga{ctx->d_tab, reinterpret_cast<const v4f*>(ctx->weight), slots, n, ld_x / 4, once, ld_once, lr};
-    const size_t lds_s = (size_t)4 * (32 * 36 + D + 528) * sizeof(float);
-    int64_t gp = cdiv(B, 4);
-    const int per_cu = g_cdlrm_debug[5] > 0 ? g_cdlrm_debug[5] : (D == 256 ? 1 : 2);
-    if (gp > 256 * per_cu) gp = 256 * per_cu;
-    static size_t s32 = 0, s64 = 0, s128 = 0, s256 = 0, o32 = 0, o64 = 0, o128 = 0, o256 = 0;
-#define GIBWD(D4_, A_, ONCE_)                                                                                         \
-    do {                                                                                                              \
-        int rc = interact_set_lds(k_interact_bwd_s<D4_, D4_ / 8, true, ONCE_>, lds_s, &A_);                           \
-        if (rc) return rc;                                                                                            \
-        CDLRM_LAUNCH_EV((k_interact_bwd_s<D4_, D4_ / 8, true, ONCE_>), dim3((unsigned)gp), dim3(256), lds_s,          \
-                        (hipStream_t)stream, x, ga, dR, ld_r, B, F, itself, x_act, dfeat);                            \
-    } while (0)
-    if (once) {
-        if (D == 32) GIBWD(8, o32, true);
-        else if (D == 64) GIBWD(16, o64, true);
-        else if (D == 128) GIBWD(32, o128, true);
-        else GIBWD(64, o256, true);
-    } else {
-        if (D == 32) GIBWD(8, s32, false);
-        else if (D == 64) GIBWD(16, s64, false);
-        else if (D == 128) GIBWD(32, s128, false);
-        else GIBWD(64, s256, false);
-    }
-#undef GIBWD
-    CDLRM_LAUNCH_CHECK();
-    return 0;
+    return ia_with_d4(p.d4, [&](auto d4) {
+        constexpr int D4 = decltype(d4)::value;
+        if (once)
+            return ia_launch<k_interact_bwd_s<D4, D4 / 8, true, true>>(p, stream, true, x, ga, dR, ld_r, B, F, itself, x_act, dfeat);
+        return ia_launch<k_interact_bwd_s<D4, D4 / 8, true, false>>(p, stream, true, x, ga, dR, ld_r, B, F, itself, x_act, dfeat);
+    });
 }
 
 extern "C" int cdlrm_gather_interact_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,

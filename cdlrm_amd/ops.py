@@ -551,6 +551,22 @@ def gather_interact_bwd_sgd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor,
                                                    dfeat.data_ptr(), int(once), int(ld_once), float(lr), stream_ptr(stream)))
 
 
+IA_OPS = {"fwd": 0, "bwd": 1, "gather_fwd": 2, "gather_bwd": 3, "gather_bwd_sgd": 4}
+IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db"}
+
+
+def interact_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, aligned_r: bool = True,
+                   aligned_dfeat: bool = True) -> dict:
+    """The kernel one interaction call launches, from the same decision code, without launching it: op of IA_OPS on B samples
+    of F features (T + 1 for the gather ops) of D columns, ld_r the row pitch of R (forward) / dR (backward), aligned_r /
+    aligned_dfeat whether R / dR and dfeat are 16-byte aligned.  family (IA_FAMILIES), d4, ns, grid (under the current
+    cdlrm_debug_set values) and lds_bytes; a shape the call refuses raises its error.  No device is touched."""
+    out = _lib.InteractRoute()
+    check(_lib.raw().cdlrm_interact_route(IA_OPS[op], int(B), int(F), int(D), int(bool(itself)), int(ld_r),
+                                          int(bool(aligned_r)) | int(bool(aligned_dfeat)) << 1, C.byref(out)))
+    return {"family": IA_FAMILIES[out.family], "d4": out.d4, "ns": out.ns, "grid": out.grid, "lds_bytes": out.lds_bytes}
+
+
 ACT = {"none": 0, "relu": 1, "sigmoid": 2}
 
 

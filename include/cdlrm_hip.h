@@ -450,6 +450,30 @@ int cdlrm_gather_interact_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, c
 int cdlrm_gather_interact_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
                                   const float* dR, int64_t ld_r, int64_t B, int32_t itself, int32_t x_act, float* dfeat,
                                   const uint8_t* once, int64_t ld_once, float lr, void* stream);
+/* Which kernel an interaction call launches (cdlrm_interact_route below). */
+#define CDLRM_IA_GENERIC 1      /* k_interact_fwd / k_interact_bwd: any D, a barrier per sample */
+#define CDLRM_IA_ROW 2          /* k_interact_fwd_p / _bwd_p<d4>: software-pipelined, the sample's whole rows staged */
+#define CDLRM_IA_SLAB 3         /* k_interact_fwd_s / _bwd_s<d4, ns, gather>: column slabs of D / ns columns */
+#define CDLRM_IA_SLAB_DB 4      /* k_interact_fwd_s<d4, ns, true, true>: the slab slice double-buffered */
+#define CDLRM_IA_OP_FWD 0               /* cdlrm_interact_fwd */
+#define CDLRM_IA_OP_BWD 1               /* cdlrm_interact_bwd */
+#define CDLRM_IA_OP_GATHER_FWD 2        /* cdlrm_gather_interact_fwd */
+#define CDLRM_IA_OP_GATHER_BWD 3        /* cdlrm_gather_interact_bwd */
+#define CDLRM_IA_OP_GATHER_BWD_SGD 4    /* cdlrm_gather_interact_bwd_sgd */
+struct cdlrm_interact_route {   /* (a struct tag: the query below has the name) */
+    int32_t family;             /* CDLRM_IA_* */
+    int32_t d4;                 /* D / 4 (the template argument of the ROW / SLAB kernels) */
+    int32_t ns;                 /* column slabs per sample (SLAB families), else 0 */
+    int32_t reserved;
+    int64_t grid;               /* workgroups of 256 lanes, under the current cdlrm_debug_set values (keys 4 and 5) */
+    int64_t lds_bytes;          /* dynamic LDS of the launch */
+};
+/* The plan of one interaction call without the launch: op CDLRM_IA_OP_*, the call's B, F (= T + 1 for the gather ops), D,
+ * itself and row pitch of R (forward) / dR (backward); aligned: bit 0 = R / dR is 16-byte aligned, bit 1 = dfeat is.  The answer
+ * comes out of the same decision code the launching calls run; a shape the entry point refuses is refused here with its
+ * error.  No device is touched. */
+int cdlrm_interact_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r, int32_t aligned,
+                         struct cdlrm_interact_route* out);
 /* Linear + activation (create_mlp, model_no_ddp.py:244-270): Y = act(X W^T + b).
  * X [M, K] ld_x, W [N, K] row-major (nn.Linear.weight), Y [M, N] ld_y. act: 0 none, 1 ReLU, 2 sigmoid. */
 /* CDLRM_GEMM_ALONE, or-ed into `act` of cdlrm_linear_fwd / cdlrm_linear_bwd: the caller's promise that no other GEMM runs beside

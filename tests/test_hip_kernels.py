@@ -535,15 +535,23 @@ def test_fused_activation_backward_chain(ops, M):
     np.testing.assert_allclose(dfeat[:, 0].cpu().numpy(), pre0.grad.float().numpy(), **tol)
 
 
-@pytest.mark.parametrize("B,F,D,itself,pad", [(3000, 27, 128, 0, 1), (2049, 9, 32, 1, 3), (700, 32, 64, 0, 0),
-                                               (5000, 27, 128, 1, 2), (33, 27, 256, 0, 1), (257, 4, 16, 0, 0),
-                                               (1, 27, 128, 0, 1),
-                                               # slab kernels with several samples per wave at the other widths; a row pitch
-                                               # that is no multiple of 4 (whole-row forward, generic backward)
-                                               (2100, 27, 256, 1, 3), (4100, 20, 32, 0, 2), (300, 27, 128, 0, 0)])
+# (B, F, D, itself, pad): the kernels the row is here for, "<family> <d4>" of the forward and of the backward
+INTERACT_ROWS = {
+    (3000, 27, 128, 0, 1): ("slab 32", "slab 32"), (2049, 9, 32, 1, 3): ("slab 8", "row 8"), (700, 32, 64, 0, 0): ("slab 16", "slab 16"),
+    (5000, 27, 128, 1, 2): ("slab 32", "slab 32"), (33, 27, 256, 0, 1): ("slab 64", "slab 64"), (257, 4, 16, 0, 0): ("generic 4", "generic 4"),
+    (1, 27, 128, 0, 1): ("slab 32", "slab 32"),
+    # slab kernels with several samples per wave at the other widths; a row pitch that is no multiple of 4
+    (2100, 27, 256, 1, 3): ("row 64", "generic 64"), (4100, 20, 32, 0, 2): ("slab 8", "slab 8"), (300, 27, 128, 0, 0): ("row 32", "generic 32"),
+    # the whole-row kernels at the remaining widths; 2100: a wave of a grid capped at 512 workgroups walks a second sample
+    (2100, 9, 64, 0, 0): ("slab 16", "row 16"), (2100, 12, 128, 1, 2): ("slab 32", "row 32"),
+    (2100, 27, 32, 0, 0): ("row 8", "generic 8"), (2100, 20, 64, 1, 1): ("row 16", "generic 16")}
+
+
+@pytest.mark.parametrize("B,F,D,itself,pad", list(INTERACT_ROWS))
 def test_interaction_kernels_vs_torch(ops, B, F, D, itself, pad):
     """Pairwise-dot interaction forward/backward (software-pipelined kernels for D = 32/64/128/256, generic otherwise)
-    against torch autograd on the oracle's interact_features; R/dR with a padded row pitch as the engine uses."""
+    against torch autograd on the oracle's interact_features; R/dR with a padded row pitch as the engine uses.  Each row runs
+    the kernels it names (ops.interact_route on the call's own arguments)."""
     rng = np.random.RandomState(B + F + D)
     feat = torch.from_numpy(rng.randn(B, F, D).astype(np.float32))
     npairs = F * (F + 1) // 2 if itself else F * (F - 1) // 2
@@ -554,12 +562,17 @@ def test_interaction_kernels_vs_torch(ops, B, F, D, itself, pad):
     ref.backward(G[:, :D + npairs].double())
     fd = feat.to(DEV)
     R = torch.full((B, width), 7.0, device=DEV)
+    r = ops.interact_route("fwd", B, F, D, bool(itself), R.stride(0), R.data_ptr() % 16 == 0)
+    assert "%s %d" % (r["family"], r["d4"]) == INTERACT_ROWS[B, F, D, itself, pad][0]
     ops.interact_fwd(fd, bool(itself), R)
     np.testing.assert_allclose(R[:, :D + npairs].cpu().numpy(), ref.detach().float().numpy(), rtol=2e-5, atol=2e-5)
     padc = R[:, D + npairs:]                                # pad columns: untouched, or zero (whole-float4 output rows)
     assert bool(((padc == 7.0) | (padc == 0.0)).all())
     dfeat = torch.empty_like(fd)
-    ops.interact_bwd(fd, G.to(DEV), bool(itself), dfeat)
+    Gd = G.to(DEV)
+    r = ops.interact_route("bwd", B, F, D, bool(itself), Gd.stride(0), Gd.data_ptr() % 16 == 0, dfeat.data_ptr() % 16 == 0)
+    assert "%s %d" % (r["family"], r["d4"]) == INTERACT_ROWS[B, F, D, itself, pad][1]
+    ops.interact_bwd(fd, Gd, bool(itself), dfeat)
     np.testing.assert_allclose(dfeat.cpu().numpy(), f.grad.float().numpy(), rtol=2e-5, atol=2e-4)
 
 
