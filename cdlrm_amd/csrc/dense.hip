@@ -7,7 +7,6 @@
 #include "gemm_wide.h"
 #include "gemm_bf16.h"
 
-
 // Linear forward with a short contraction (K <= 32: the first bottom layer reads the 13 dense features).  An MFMA
 // tile would be mostly padding -- the small-batch GEMM spends 13 us at M = 1024 fetching clamped indices for 13.6 MFLOP --
 // so this one runs on the vector ALU: a workgroup owns 32 rows x 128 columns, X tile and transposed W tile in LDS,
@@ -122,76 +121,62 @@ __global__ void __launch_bounds__(256) k_linear_smallk_rows(const float* __restr
     }
 }
 
-// rec != nullptr: the route query (cdlrm_linear_fwd_route) -- every decision below is taken, its outcome recorded, nothing launched
-static int linear_fwd(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y, int64_t M, int32_t N,
-                      int32_t K, int32_t act, void* stream, const GemmRec* rec) {
+// Rows per workgroup of k_linear_smallk_rows: ~512-1024 workgroups at the c3 batch; short batches get 8 rows per workgroup -- a
+// wave's 52 weight loads are then amortised over two rows only, but 32 rows left 64 workgroups for 256 CUs at M = 1024 and the
+// kernel took 10.3 us in the per-rank step, against 6.6 for the LDS-tiled one.
+static inline int smallk_rows_per_wg(int64_t M) { return M >= 32768 ? 128 : M >= 4096 ? 32 : 8; }
+
+// the forward problem g (A = X, B = W with pitch K, C = Y) on the vector-ALU kernel the plan names
+static void launch_linear_smallk(const GemmPlan& p, const GemmArgs& g, hipStream_t s) {
+    if (p.r.family == CDLRM_ROUTE_SMALLK_ROWS)
+        hipLaunchKernelGGL((k_linear_smallk_rows<13>), p.grid, dim3(256), 0, s, g.A, g.lda, g.B, g.bias, g.C, g.ldc, g.M, g.N,
+                           smallk_rows_per_wg(g.M), g.act);
+    else
+        hipLaunchKernelGGL(k_linear_smallk, p.grid, dim3(256), 0, s, g.A, g.lda, g.B, g.bias, g.C, g.ldc, g.M, g.N, (int)g.K, g.act);
+}
+
+#include "gemm_plan.h"      // gemm_plan / gemm_launch: behind every kernel they choose between
+
+// Check the arguments of cdlrm_linear_fwd, build its problem g and plan it for n_cu compute units.  M == 0: no launch (the plan's
+// family stays CDLRM_ROUTE_NONE).
+static int linear_fwd_plan(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y, int64_t M,
+                           int32_t N, int32_t K, int32_t act, int n_cu, GemmArgs& g, GemmPlan& p) {
     CDLRM_REQUIRE(X && W && Y && M >= 0 && N >= 1 && K >= 1 && ld_x >= K && ld_y >= N, "bad argument");
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint riding on the activation code
-    const int bf16 = bf16_planes(act);                     // the opt-in bf16 / bf16x3 matrix-core modes (gemm_bf16.h): 1 / 2 planes
+    const int planes = bf16_planes(act);                   // the opt-in bf16 / bf16x3 matrix-core modes (gemm_bf16.h): 1 / 2 planes
     act &= ~(CDLRM_GEMM_ALONE | BF16_MODES);
-    CDLRM_REQUIRE(bf16 >= 0, "CDLRM_GEMM_BF16 and CDLRM_GEMM_BF16X3 exclude each other");
+    CDLRM_REQUIRE(planes >= 0, "CDLRM_GEMM_BF16 and CDLRM_GEMM_BF16X3 exclude each other");
     CDLRM_REQUIRE(act >= 0 && act <= 2, "bad activation code");
+    memset(&p, 0, sizeof(p));
     if (M == 0) return 0;
-    if (!rec) CDLRM_CLEAR_STALE();
-    if (bf16 && bf16_layer_ok(N, K)) {
-        GemmArgs g = gemm_args();
-        g.A = X; g.lda = ld_x; g.B = W; g.ldb = K; g.C = Y; g.ldc = ld_y; g.slab = 0;
-        g.M = M; g.N = N; g.K = K; g.bias = bias; g.act = act;
-        return launch_gemm_bf16<true, true>(g, bf16, (hipStream_t)stream, rec);
-    }
-    // (Round 6, measured and removed: this layer on the matrix cores -- a wave owning 16 rows x 256 columns, the weights as
-    //  16x16x4 fragments in registers, ascending k, bit-identical -- 10.9 us alone against 8.6 for the register kernel below at
-    //  M = 8192 (64 scattered 4-byte weight loads per lane for 64 MFMAs), 0.5542 against 0.5519 ms per c3 step.)
-    if (K == 13 && N % 256 == 0 && ld_y % 4 == 0 && aligned16(Y) && (!bias || aligned16(bias)) && M >= 256 &&
-        !g_cdlrm_debug[0]) {
-        // Rows per workgroup: ~512-1024 workgroups at the c3 batch; short batches get 8 rows per workgroup -- a wave's 52
-        // weight loads are then amortised over two rows only, but 32 rows left 64 workgroups for 256 CUs at M = 1024 and the
-        // kernel took 10.3 us in the per-rank step, against 6.6 for the LDS-tiled one.
-        const int rpw = M >= 32768 ? 128 : M >= 4096 ? 32 : 8;
-        const int64_t blocks = cdiv(M, rpw) * (N >> 8);
-        if (blocks <= 0x7fffffff) {
-            if (rec) {
-                gemm_record(rec, CDLRM_ROUTE_SMALLK_ROWS, 0, 0, 0, 0, 1, 0, 0, 0);
-                return 0;
-            }
-            hipLaunchKernelGGL((k_linear_smallk_rows<13>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, X, ld_x, W,
-                               bias, Y, ld_y, M, (int)N, rpw, (int)act);
-            CDLRM_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (K <= SK_KMAX && N % 4 == 0 && ld_y % 4 == 0 && aligned16(Y) && cdiv(M, 32) <= 65535) {
-        if (rec) {
-            gemm_record(rec, CDLRM_ROUTE_SMALLK, 0, 0, 0, 0, 1, 0, 0, 0);
-            return 0;
-        }
-        dim3 grid((unsigned)cdiv(N, 128), (unsigned)cdiv(M, 32));
-        hipLaunchKernelGGL(k_linear_smallk, grid, dim3(256), 0, (hipStream_t)stream, X, ld_x, W, bias, Y, ld_y, M, (int)N,
-                           (int)K, (int)act);
-        CDLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    GemmArgs g = gemm_args();
+    g = gemm_args();
     g.A = X; g.lda = ld_x; g.B = W; g.ldb = K; g.C = Y; g.ldc = ld_y; g.slab = 0;
     g.M = M; g.N = N; g.K = K; g.kchunk = K; g.bias = bias; g.act = act;
     g.vecA = aligned16(X) && ld_x % 4 == 0 && K % 4 == 0;
     g.vecB = aligned16(W) && K % 4 == 0;
     g.alone = alone;
-    return launch_gemm<true, true>(g, 1, (hipStream_t)stream, rec);
+    p = gemm_plan<true, true>(g, 1, planes, n_cu);
+    return 0;
 }
 
 extern "C" int cdlrm_linear_fwd(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y,
                                 int64_t M, int32_t N, int32_t K, int32_t act, void* stream) {
-    return linear_fwd(X, ld_x, W, bias, Y, ld_y, M, N, K, act, stream, nullptr);
+    GemmArgs g; GemmPlan p;
+    const int rc = linear_fwd_plan(X, ld_x, W, bias, Y, ld_y, M, N, K, act, gemm_device_cus(), g, p);
+    if (rc || p.r.family == CDLRM_ROUTE_NONE) return rc;
+    CDLRM_CLEAR_STALE();
+    return gemm_launch<true, true>(p, g, (hipStream_t)stream);
 }
 
 extern "C" int cdlrm_linear_fwd_route(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y, int64_t ld_y,
                                       int64_t M, int32_t N, int32_t K, int32_t act, void* stream, int32_t n_cu,
                                       cdlrm_gemm_route* out) {
     CDLRM_REQUIRE(out && n_cu >= 1, "bad argument");
+    GemmArgs g; GemmPlan p;
     memset(out, 0, sizeof(*out));
-    const GemmRec rec = {out, n_cu};
-    return linear_fwd(X, ld_x, W, bias, Y, ld_y, M, N, K, act, stream, &rec);
+    const int rc = linear_fwd_plan(X, ld_x, W, bias, Y, ld_y, M, N, K, act, n_cu, g, p);
+    if (rc == 0) *out = p.r;
+    return rc;
 }
 
 // ---- backward helpers -----------------------------------------------------------------------------
@@ -325,7 +310,7 @@ static inline uint64_t r256(uint64_t bytes) { return (bytes + 255) & ~(uint64_t)
 // slab count of ONE layer at a long batch (cdlrm_linear_bwd, and every fp32 layer of cdlrm_mlp_wgrad* above WGRAD_DIRECT_MAX_M)
 static int wgrad_splits(int64_t M, int N, int K) {
     if (M <= WGRAD_DIRECT_MAX_M) return 1;
-    const int64_t tiles = cdiv(N, 64) * cdiv(K, 64);    // the 64x64 tile launch_gemm picks for these shapes
+    const int64_t tiles = cdiv(N, 64) * cdiv(K, 64);    // the 64x64 tile gemm_plan picks for these shapes
     const int64_t target = 1024;        // measured at c3: 512 -> 0.687 ms/step, 1024 -> 0.668, 2048 the same
     int64_t s = cdiv(target, tiles);                  // aim at ~4 workgroups of 64x64 per CU (2 of 128x64)
     const int64_t smax = cdiv(M, 8 * GBK);
@@ -371,10 +356,15 @@ extern "C" uint64_t cdlrm_linear_bwd_work_bytes(int64_t M, int32_t N, int32_t K)
     return wgrad_carve(0, wgrad_splits(M, N, K), N, K, &cs) + 256;
 }
 
-// rec != nullptr: the route query (cdlrm_linear_bwd_route): rec[0] the dgrad, rec[1] the weight gradient; nothing launched
-static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float* Y, int64_t ld_y, float* dY, int64_t ld_dy,
-                      float* dX, int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N, int32_t K, int32_t act,
-                      int32_t x_act, void* work, void* stream, const GemmRec* rec) {
+// What cdlrm_linear_bwd launches behind the activation backward: the dgrad GEMM (dX asked for; else its plan's family stays
+// CDLRM_ROUTE_NONE), the weight-gradient GEMM and the reduction of its pw.r.splits > 1 slabs (dW asked for)
+struct LinearBwdPlan { GemmArgs gx, gw; GemmPlan px, pw; ReduceJob red; };
+
+// Check the arguments of cdlrm_linear_bwd (act: without its flag bits on return), build its problems and plan them for n_cu
+// compute units.
+static int linear_bwd_plan(const float* X, int64_t ld_x, const float* W, const float* Y, float* dY, int64_t ld_dy, float* dX,
+                           int64_t ld_dx, float* dW, float* db, int64_t M, int32_t N, int32_t K, int32_t& act, int32_t x_act,
+                           void* work, int n_cu, LinearBwdPlan& o) {
     const int alone = (act & CDLRM_GEMM_ALONE) != 0;       // scheduling hint for the dgrad GEMM, riding on the activation code
     const int planes = bf16_planes(act);
     const int bf16 = bf16_layer_ok(N, K) ? planes : 0;     // both GEMMs of the layer in bf16 / bf16x3 (gemm_bf16.h): 1 / 2 planes
@@ -385,58 +375,38 @@ static int linear_bwd(const float* X, int64_t ld_x, const float* W, const float*
     CDLRM_REQUIRE(act == 0 || Y, "activation backward needs Y");
     CDLRM_REQUIRE(act >= 0 && act <= 2 && x_act >= 0 && x_act <= 2, "bad activation code");
     CDLRM_REQUIRE(((uintptr_t)work & 255) == 0, "work must be 256-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    if (act != 0 && !rec) {     // dZ = dY * act'(Y) in place
-        const int64_t nb = cdiv(M * N, 256), blocks = nb < 2048 ? nb : 2048;
-        hipLaunchKernelGGL(k_act_grad, dim3((unsigned)blocks), dim3(256), 0, s, Y, ld_y, dY, ld_dy, M, N, act);
-    }
+    memset(&o, 0, sizeof(o));
     if (dX) {   // dX[M,K] = dZ[M,N] W[N,K]  (* act'(X) when X is the activation output of the layer below)
-        GemmArgs g = gemm_args();
+        GemmArgs& g = o.gx = gemm_args();
         g.A = dY; g.lda = ld_dy; g.B = W; g.ldb = K; g.C = dX; g.ldc = ld_dx; g.slab = 0;
         g.M = M; g.N = K; g.K = N; g.kchunk = N; g.bias = nullptr; g.act = 0;
         g.vecA = aligned16(dY) && ld_dy % 4 == 0 && N % 4 == 0;
         g.vecB = aligned16(W) && K % 4 == 0;
         g.mask = X; g.ldmask = ld_x; g.mask_act = x_act;
         g.alone = alone;
-        int rc = bf16 ? launch_gemm_bf16<true, false>(g, bf16, s, rec) : launch_gemm<true, false>(g, 1, s, rec);
-        if (rc) return rc;
+        o.px = gemm_plan<true, false>(g, 1, bf16, n_cu);
     }
     // dW[N,K] = dZ[M,N]^T X[M,K], split over M into slabs summed in slab order; the first column panel of the
     // same GEMM sums dZ over the batch (bias gradient).  bf16: the same split-M slabs (at most `splits` of them: the work size
     // does not change) and the same slab reduction.
     if (dW) {
         const int splits = wgrad_splits(M, N, K);
-        GemmArgs g = gemm_args();
+        GemmArgs& g = o.gw = gemm_args();
         g.A = dY; g.lda = ld_dy; g.B = X; g.ldb = ld_x; g.C = dW; g.ldc = K; g.colsum = db;
         g.slab = (int64_t)N * K;
         g.M = N; g.N = K; g.K = M;
-        if (bf16) {
-            g.kchunk = bf16_wgrad_kchunk(M, cdiv(N, 64) * cdiv(K, 64), splits);
-            g.vecA = bf16_vec<false>(dY, ld_dy, N, M);
-            g.vecB = bf16_vec<false>(X, ld_x, K, M);
-        } else {
-            g.kchunk = cdiv(cdiv(M, splits), GBK) * GBK;
-            g.vecA = aligned16(dY) && ld_dy % 4 == 0 && N % 4 == 0;
-            g.vecB = aligned16(X) && ld_x % 4 == 0 && K % 4 == 0;
-        }
+        g.kchunk = bf16 ? bf16_wgrad_kchunk(M, cdiv(N, 64) * cdiv(K, 64), splits) : cdiv(cdiv(M, splits), GBK) * GBK;
+        g.vecA = aligned16(dY) && ld_dy % 4 == 0 && N % 4 == 0;
+        g.vecB = aligned16(X) && ld_x % 4 == 0 && K % 4 == 0;
         const int zs = (int)cdiv(M, g.kchunk);      // <= splits
-        ReduceJob r{};
         if (zs > 1) {
             uint64_t cs;
             wgrad_carve(0, zs, N, K, &cs);
             // (one layer alone on the queue: a reduction up to 2048 workgroups wide)
-            r = wgrad_slabbed(g, work, 0, cs, zs, reduce_gxa(g.slab, 256, 2048), dW, db, nullptr, nullptr, 0.f);
+            o.red = wgrad_slabbed(g, work, 0, cs, zs, reduce_gxa(g.slab, 256, 2048), dW, db, nullptr, nullptr, 0.f);
         }
-        int rc = 0;
-        if (!bf16) rc = launch_gemm<false, false>(g, zs, s, rec ? rec + 1 : nullptr);
-        else if (rec) gemm_record(rec + 1, bf16_family(bf16), 1, 1, 0, 0, zs, g.vecA, g.vecB, 0);
-        else rc = launch_wgrad_bf16(&g, 1, g.vecA, g.vecB, bf16, s);
-        if (rc) return rc;
-        if (zs > 1 && !rec)     // one launch sums the dW slabs and the bias-gradient partials
-            hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)(r.gxa + cdiv(r.countB, 64))), dim3(256), 0, s, r.partA, r.countA, zs,
-                               dW, r.gxa, r.partB, r.countB, zs, db);
+        o.pw = gemm_plan<false, false>(g, zs, bf16, n_cu);
     }
-    if (!rec) CDLRM_LAUNCH_CHECK();
     return 0;
 }
 
@@ -447,7 +417,22 @@ extern "C" int cdlrm_linear_bwd(const float* X, int64_t ld_x, const float* W, co
     // a completion event waiting for this call (cdlrm_event_attach_next) rides on the dgrad GEMM when that is the call's only
     // launch (the training step's use); with several launches it is recorded behind the last one
     if ((act & ~(CDLRM_GEMM_ALONE | BF16_MODES)) != 0 || dW || !dX) stop_scope.hold((hipStream_t)stream);
-    return linear_bwd(X, ld_x, W, Y, ld_y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, stream, nullptr);
+    hipStream_t s = (hipStream_t)stream;
+    LinearBwdPlan o;
+    int rc = linear_bwd_plan(X, ld_x, W, Y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, gemm_device_cus(), o);
+    if (rc) return rc;
+    if (act != 0) {     // dZ = dY * act'(Y) in place
+        const int64_t nb = cdiv(M * N, 256), blocks = nb < 2048 ? nb : 2048;
+        hipLaunchKernelGGL(k_act_grad, dim3((unsigned)blocks), dim3(256), 0, s, Y, ld_y, dY, ld_dy, M, N, act);
+    }
+    if (dX && (rc = gemm_launch<true, false>(o.px, o.gx, s))) return rc;
+    if (dW && (rc = gemm_launch<false, false>(o.pw, o.gw, s))) return rc;
+    const ReduceJob& r = o.red;
+    if (o.pw.r.splits > 1)      // one launch sums the dW slabs and the bias-gradient partials
+        hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)(r.gxa + cdiv(r.countB, 64))), dim3(256), 0, s, r.partA, r.countA, r.splits,
+                           dW, r.gxa, r.partB, r.countB, r.splits, db);
+    CDLRM_LAUNCH_CHECK();
+    return 0;
     // (stop_scope records an event no launch carried)
 }
 
@@ -456,9 +441,11 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
                                       int32_t K, int32_t act, int32_t x_act, void* work, void* stream, int32_t n_cu,
                                       cdlrm_gemm_route* out) {
     CDLRM_REQUIRE(out && n_cu >= 1, "bad argument");
+    LinearBwdPlan o;
     memset(out, 0, 2 * sizeof(*out));
-    const GemmRec rec[2] = {{out, n_cu}, {out + 1, n_cu}};
-    return linear_bwd(X, ld_x, W, Y, ld_y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, stream, rec);
+    const int rc = linear_bwd_plan(X, ld_x, W, Y, dY, ld_dy, dX, ld_dx, dW, db, M, N, K, act, x_act, work, n_cu, o);
+    if (rc == 0) { out[0] = o.px.r; out[1] = o.pw.r; }
+    return rc;
 }
 
 // ---- cdlrm_mlp_wgrad*: the weight (and bias) gradients of SEVERAL layers at once ------------------------------------------------
@@ -474,7 +461,7 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
 //                combination allows (launch_wgrad_mixed)
 //     one slab count for all of them, then ONE grouped reduction
 //   long batches:
-//     WG_SPLIT   per layer one split-M GEMM (launch_gemm picks the kernel: tiled, or LDS-free for degenerate shapes) into the
+//     WG_SPLIT   per layer one split-M GEMM (gemm_plan picks the kernel: tiled, or LDS-free for degenerate shapes) into the
 //                layer's own slabs, then ONE grouped reduction of all layers
 //   flags & CDLRM_GEMM_BF16 or CDLRM_GEMM_BF16X3 (gemm_bf16.h; the same layout, one or two operand planes), any batch:
 //     WG_BF16    the layers the shape rule admits (bf16_layer_ok) as one grouped bf16 launch on 64x64 tiles with one slab length
@@ -629,12 +616,6 @@ static void launch_reduce_jobs(const std::vector<ReduceJob>& jobs, hipStream_t s
     }
 }
 
-static inline void route_set(cdlrm_gemm_route* out, int family, int tm, int tn, int mode, int aligned, int splits, int va, int vb,
-                             int fast) {
-    const GemmRec rec = {out, 0};
-    gemm_record(&rec, family, tm, tn, mode, aligned, splits, va, vb, fast);
-}
-
 // All of cdlrm_mlp_wgrad*: build the layout, then either translate it into routes (rout: the route query, one entry per layer,
 // nothing launched, no pointer read) or walk it and launch.  P_w / P_b (both or neither): the layers' parameters, stepped by
 // -lr * gradient in the reduction pass (layers whose gradient needs no reduction: one elementwise launch behind it).
@@ -665,12 +646,14 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
     if (rout) {
         for (int i = 0; i < n_layers; ++i) {
             const WgradLayer& l = p.L[i];
-            if (l.family == WG_TILED) route_set(&rout[i], CDLRM_ROUTE_GEMM, 1, 1, 0, 0, l.zs, 1, 1, 0);
-            else if (l.family == WG_DIRECT) route_set(&rout[i], CDLRM_ROUTE_DIRECT, 0, 0, 0, 0, l.zs, l.vecA, l.vecB, 0);
-            else if (l.family == WG_BF16) route_set(&rout[i], bf16_family(p.planes), 1, 1, 0, 0, l.zs, p.bf_vecA, p.bf_vecB, 0);
-            else {      // the kernel and its tile are launch_gemm's choice
-                const GemmRec rec = {&rout[i], n_cu};
-                (void)launch_gemm<false, false>(problem(i), l.zs, s, &rec);
+            cdlrm_gemm_route& r = rout[i];
+            r.splits = l.zs;
+            if (l.family == WG_TILED) { r.family = CDLRM_ROUTE_GEMM; r.tm = r.tn = r.vec_a = r.vec_b = 1; }
+            else if (l.family == WG_DIRECT) { r.family = CDLRM_ROUTE_DIRECT; r.vec_a = l.vecA; r.vec_b = l.vecB; }
+            else if (l.family == WG_BF16) { r.family = bf16_family(p.planes); r.tm = r.tn = 1; r.vec_a = p.bf_vecA; r.vec_b = p.bf_vecB; }
+            else {      // the kernel and its tile are gemm_plan's choice, as in the launch below
+                GemmArgs g = problem(i);
+                r = gemm_plan<false, false>(g, l.zs, 0, n_cu).r;
             }
         }
         return 0;
@@ -747,7 +730,9 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
             size_t q = 0;
             for (int i = 0; i < n_layers; ++i) {
                 if (p.L[i].family != WG_SPLIT) continue;
-                int rc = launch_gemm<false, false>(probs[q++], p.L[i].zs, s);
+                GemmArgs& g = probs[q++];
+                const GemmPlan gp = gemm_plan<false, false>(g, p.L[i].zs, 0, gemm_device_cus());
+                int rc = gemm_launch<false, false>(gp, g, s);
                 if (rc) return rc;
             }
         }

@@ -40,18 +40,17 @@ struct GemmArgs {
                                               // kernel of gemm_wide.h wants a whole CU: 96 KB of LDS, one wave per SIMD)
 };
 
-// "Record, don't launch" (cdlrm_linear_fwd_route / _bwd_route): the launch functions below take an optional GemmRec and then
-// write what they chose into *out instead of launching -- the route and the launch come out of the same decisions.  n_cu: the
-// compute-unit count the wide kernel's rule is evaluated for (the launching path asks the device).
-struct GemmRec {
-    cdlrm_gemm_route* out;
-    int n_cu;
+// What one GEMM launch is: the kernel family and variant as the route queries report them (cdlrm_gemm_route), plus the grid and
+// the dynamic LDS bytes of the launch.  gemm_plan (gemm_plan.h) fills it in, gemm_launch launches from it, the route queries
+// copy `r` out: one value, read by both.
+struct GemmPlan {
+    cdlrm_gemm_route r;
+    dim3 grid;
+    unsigned lds;
 };
-static inline void gemm_record(const GemmRec* rec, int family, int tm, int tn, int mode, int aligned, int splits, int va,
-                               int vb, int fast) {
-    cdlrm_gemm_route& r = *rec->out;
-    r.family = family; r.tm = tm; r.tn = tn; r.mode = mode; r.aligned = aligned; r.splits = splits;
-    r.vec_a = va; r.vec_b = vb; r.fast = fast;
+// the grid of a kernel on bm x bn output tiles, the contraction cut into `splits` slabs
+static inline dim3 gemm_grid(const GemmArgs& g, int bm, int bn, int splits) {
+    return dim3((unsigned)cdiv(g.N, bn), (unsigned)cdiv(g.M, bm), (unsigned)splits);
 }
 
 static inline GemmArgs gemm_args() {
@@ -820,45 +819,34 @@ static void launch_gemm_staged(const GemmArgs& g, dim3 grid, int mode, hipStream
     else CDLRM_LAUNCH_EV((k_gemm_staged<A_KC, B_KC, 0>), grid, dim3(256), ST_LDS_BYTES, s, g);
 }
 
+// Which of the 32x32-tile kernels takes a problem: the staged one (16-byte loads throughout), else the LDS-free one with the
+// aligned loader or the generic one; and its mode.  klen: the length of a contraction slab (kchunk <= 0 or >= K: un-split).
+struct DirectVariant { bool staged, aligned; int mode; int64_t klen; };
 template <bool A_KC, bool B_KC>
-static void launch_gemm_direct(GemmArgs g, int splits, hipStream_t s, const GemmRec* rec = nullptr) {
-    g.vecC = aligned16(g.C) && g.ldc % 4 == 0 && g.slab % 4 == 0;
-    const bool va = A_KC && g.vecA, vb = B_KC && g.vecB;     // only contraction-contiguous operands use 16-B loads
-    dim3 grid((unsigned)cdiv(g.N, 32), (unsigned)cdiv(g.M, 32), (unsigned)splits);
-    const int64_t klen = g.kchunk < g.K ? g.kchunk : g.K;
+static inline DirectVariant direct_variant(const GemmArgs& g) {
+    const int64_t klen = g.kchunk > 0 && g.kchunk < g.K ? g.kchunk : g.K;
     const bool al = direct_aligned<A_KC, B_KC>(g, klen);
-    const int mode = direct_mode(klen, al);
-    const bool st = direct_staged<A_KC, B_KC>(g, klen);
-    if (rec) {
-        // direct_prefetch's launch-wide conditions (a thread also needs its float4 inside the matrix)
-        const int pre = g.fastep && g.vecC && (g.bias == nullptr || aligned16(g.bias)) &&
-                        (g.mask_act == 0 || (aligned16(g.mask) && g.ldmask % 4 == 0));
-        // the kernel launched below: staged (16-byte loads throughout), the aligned loader (16-byte loads on the
-        // contraction-contiguous operands), the generic one (va / vb)
-        gemm_record(rec, st ? CDLRM_ROUTE_STAGED : CDLRM_ROUTE_DIRECT, 0, 0, mode, st || al, splits, st ? 1 : al ? A_KC : va,
-                    st ? 1 : al ? B_KC : vb, pre);
-        return;
-    }
-    if (st) {
-        launch_gemm_staged<A_KC, B_KC>(g, grid, mode, s);
-        return;
-    }
-    if (al) {
-        if (mode == 2) hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, A_KC, B_KC, 2, true>), grid, dim3(256), 0, s, g);
-        else if (mode == 1) hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, A_KC, B_KC, 1, true>), grid, dim3(256), 0, s, g);
-        else hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, A_KC, B_KC, 0, true>), grid, dim3(256), 0, s, g);
-        return;
-    }
-#define CDLRM_DIRECT(VA_, VB_)                                                                              \
-    do {                                                                                                    \
-        if (mode == 2) hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, VA_, VB_, 2, false>), grid, dim3(256), 0, s, g);      \
-        else if (mode == 1) hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, VA_, VB_, 1, false>), grid, dim3(256), 0, s, g); \
-        else hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, VA_, VB_, 0, false>), grid, dim3(256), 0, s, g);                \
+    return {direct_staged<A_KC, B_KC>(g, klen), al, direct_mode(klen, al), klen};
+}
+// 16-byte stores legal for the short-batch kernels (GemmArgs.vecC)
+static inline int direct_vec_c(const GemmArgs& g) { return aligned16(g.C) && g.ldc % 4 == 0 && g.slab % 4 == 0; }
+
+// the LDS-free kernel of a plan of family CDLRM_ROUTE_DIRECT: the aligned loader, or the generic one with the plan's 16-byte
+// flags (only contraction-contiguous operands use 16-byte loads)
+template <bool A_KC, bool B_KC>
+static void launch_gemm_direct(const GemmPlan& p, const GemmArgs& g, hipStream_t s) {
+    const int mode = p.r.mode;
+#define CDLRM_DIRECT(VA_, VB_, AL_)                                                                           \
+    do {                                                                                                      \
+        if (mode == 2) hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, VA_, VB_, 2, AL_>), p.grid, dim3(256), 0, s, g);      \
+        else if (mode == 1) hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, VA_, VB_, 1, AL_>), p.grid, dim3(256), 0, s, g); \
+        else hipLaunchKernelGGL((k_gemm_direct<A_KC, B_KC, VA_, VB_, 0, AL_>), p.grid, dim3(256), 0, s, g);                \
     } while (0)
-    if (va && vb) CDLRM_DIRECT(A_KC, B_KC);
-    else if (va) CDLRM_DIRECT(A_KC, false);
-    else if (vb) CDLRM_DIRECT(false, B_KC);
-    else CDLRM_DIRECT(false, false);
+    if (p.r.aligned) CDLRM_DIRECT(A_KC, B_KC, true);
+    else if (p.r.vec_a && p.r.vec_b) CDLRM_DIRECT(A_KC, B_KC, false);
+    else if (p.r.vec_a) CDLRM_DIRECT(A_KC, false, false);
+    else if (p.r.vec_b) CDLRM_DIRECT(false, B_KC, false);
+    else CDLRM_DIRECT(false, false, false);
 #undef CDLRM_DIRECT
 }
 
@@ -903,18 +891,15 @@ static inline int launch_wgrad_mixed(const GemmArgs* direct, int nd, const GemmG
     int mode = -1;
     bool al = false;
     for (int i = 0; i < nd; ++i) {
-        const int64_t kc = direct[i].kchunk > 0 && direct[i].kchunk < direct[i].K ? direct[i].kchunk : direct[i].K;
-        GemmArgs pg = direct[i];
-        pg.kchunk = kc;
-        const bool a = direct_aligned<false, false>(pg, kc);
-        if (direct_staged<false, false>(pg, kc)) return 0;
-        const int m = direct_mode(kc, a);
-        if (i > 0 && (m != mode || a != al)) return 0;         // one variant of the LDS-free body per launch
-        mode = m; al = a;
+        const DirectVariant v = direct_variant<false, false>(direct[i]);
+        if (v.staged) return 0;
+        if (i > 0 && (v.mode != mode || v.aligned != al)) return 0;         // one variant of the LDS-free body per launch
+        mode = v.mode; al = v.aligned;
         dgrp.first[i] = blocks;
-        dgrp.g[i] = pg;
-        dgrp.g[i].vecC = aligned16(pg.C) && pg.ldc % 4 == 0 && pg.slab % 4 == 0;
-        blocks += (unsigned)(cdiv(pg.M, 32) * cdiv(pg.N, 32) * cdiv(pg.K, kc));
+        dgrp.g[i] = direct[i];
+        dgrp.g[i].kchunk = v.klen;
+        dgrp.g[i].vecC = direct_vec_c(direct[i]);
+        blocks += (unsigned)(cdiv(direct[i].M, 32) * cdiv(direct[i].N, 32) * cdiv(direct[i].K, v.klen));
     }
     dgrp.n = nd;
     dgrp.first[nd] = blocks;
@@ -929,7 +914,9 @@ static inline int launch_wgrad_mixed(const GemmArgs* direct, int nd, const GemmG
     return 1;
 }
 
-// up to GEMM_GROUP_MAX un-split problems of the weight-gradient layout (both operands contraction-strided) per launch
+// Problems of the weight-gradient layout (both operands contraction-strided) on the 32x32-tile kernels, up to GEMM_GROUP_MAX per
+// launch.  kchunk < K: the contraction is cut into slabs (C + z*slab, colsum + z*M), summed by the caller.  A launch runs one
+// kernel variant (direct_variant); launch order: generic loader, aligned loader, staged; by mode within each.
 static inline int launch_wgrad_group(const GemmArgs* probs, int n, hipStream_t s) {
     static bool st_attr = false;
     if (!st_attr) {
@@ -938,57 +925,41 @@ static inline int launch_wgrad_group(const GemmArgs* probs, int n, hipStream_t s
         staged_lds_attr(k_gemm_staged_group<false, false, 2>);
         st_attr = true;
     }
-    for (int want = 0; want < 9; ++want) {
-        const int want_mode = want % 3;
-        const bool want_al = want >= 3;
-        const bool want_st = want >= 6;
-        GemmGroup grp;
-        memset(&grp, 0, sizeof(grp));
-        unsigned blocks = 0;
-        auto flush = [&]() {
-            if (grp.n == 0) return;
+    std::vector<GemmArgs> variant[9];       // 3 * (0 generic, 1 aligned, 2 staged) + mode
+    for (int i = 0; i < n; ++i) {
+        const DirectVariant v = direct_variant<false, false>(probs[i]);
+        GemmArgs g = probs[i];
+        g.kchunk = v.klen;
+        g.vecC = direct_vec_c(g);
+        variant[3 * (v.staged ? 2 : v.aligned ? 1 : 0) + v.mode].push_back(g);
+    }
+    for (int key = 0; key < 9; ++key)
+        for (size_t q0 = 0; q0 < variant[key].size(); q0 += GEMM_GROUP_MAX) {
+            const int mode = key % 3;
+            GemmGroup grp;
+            memset(&grp, 0, sizeof(grp));
+            unsigned blocks = 0;
+            for (size_t q = q0; q < variant[key].size() && q < q0 + GEMM_GROUP_MAX; ++q) {
+                const GemmArgs& g = variant[key][q];
+                grp.first[grp.n] = blocks;
+                grp.g[grp.n++] = g;
+                blocks += (unsigned)(cdiv(g.M, 32) * cdiv(g.N, 32) * cdiv(g.K, g.kchunk));
+            }
             grp.first[grp.n] = blocks;
 #define CDLRM_DGROUP(MODE_, AL_) \
     hipLaunchKernelGGL((k_gemm_direct_group<false, false, false, false, MODE_, AL_>), dim3(blocks), dim3(256), 0, s, grp)
-            if (want_st) {
-                if (want_mode == 2)
-                    hipLaunchKernelGGL((k_gemm_staged_group<false, false, 2>), dim3(blocks), dim3(256), ST_LDS_BYTES, s, grp);
-                else if (want_mode == 1)
-                    hipLaunchKernelGGL((k_gemm_staged_group<false, false, 1>), dim3(blocks), dim3(256), ST_LDS_BYTES, s, grp);
-                else
-                    hipLaunchKernelGGL((k_gemm_staged_group<false, false, 0>), dim3(blocks), dim3(256), ST_LDS_BYTES, s, grp);
-            } else if (want_al) {
-                if (want_mode == 2) CDLRM_DGROUP(2, true);
-                else if (want_mode == 1) CDLRM_DGROUP(1, true);
-                else CDLRM_DGROUP(0, true);
+#define CDLRM_SGROUP(MODE_) \
+    hipLaunchKernelGGL((k_gemm_staged_group<false, false, MODE_>), dim3(blocks), dim3(256), ST_LDS_BYTES, s, grp)
+            if (key >= 6) {
+                if (mode == 2) CDLRM_SGROUP(2); else if (mode == 1) CDLRM_SGROUP(1); else CDLRM_SGROUP(0);
+            } else if (key >= 3) {
+                if (mode == 2) CDLRM_DGROUP(2, true); else if (mode == 1) CDLRM_DGROUP(1, true); else CDLRM_DGROUP(0, true);
             } else {
-                if (want_mode == 2) CDLRM_DGROUP(2, false);
-                else if (want_mode == 1) CDLRM_DGROUP(1, false);
-                else CDLRM_DGROUP(0, false);
+                if (mode == 2) CDLRM_DGROUP(2, false); else if (mode == 1) CDLRM_DGROUP(1, false); else CDLRM_DGROUP(0, false);
             }
+#undef CDLRM_SGROUP
 #undef CDLRM_DGROUP
-            grp.n = 0;
-            blocks = 0;
-        };
-        for (int i = 0; i < n; ++i) {
-            // kchunk < K: the contraction is cut into slabs (C + z*slab, colsum + z*M), summed by the caller
-            const int64_t kc = probs[i].kchunk > 0 && probs[i].kchunk < probs[i].K ? probs[i].kchunk : probs[i].K;
-            GemmArgs pg = probs[i];
-            pg.kchunk = kc;
-            const bool al = direct_aligned<false, false>(pg, kc);
-            const bool st = direct_staged<false, false>(pg, kc);
-            if (st != want_st || (!st && al != (want_al && !want_st)) || direct_mode(kc, al) != want_mode) continue;
-            if (grp.n == GEMM_GROUP_MAX) flush();
-            grp.first[grp.n] = blocks;
-            grp.g[grp.n] = probs[i];
-            grp.g[grp.n].kchunk = kc;
-            grp.g[grp.n].vecC = aligned16(probs[i].C) && probs[i].ldc % 4 == 0 && probs[i].slab % 4 == 0;
-            blocks += (unsigned)(cdiv(probs[i].M, 32) * cdiv(probs[i].N, 32) * cdiv(probs[i].K, kc));
-            grp.n++;
         }
-        flush();
-    }
     CDLRM_LAUNCH_CHECK();
     return 0;
 }
-

@@ -351,31 +351,6 @@ static void launch_gemm_bf16_v(const GemmArgs& g, dim3 grid, hipStream_t s) {
     else CDLRM_LAUNCH_EV((k_gemm_bf16<A_KC, B_KC, TM, TN, false, false, PL>), grid, dim3(256), 0, s, g);
 }
 
-// An un-split forward (A_KC, B_KC) or dgrad (A_KC, !B_KC) in bf16 (planes 1) or bf16x3 (planes 2).  g.vecA / g.vecB are
-// recomputed here from the operands.  rec != nullptr: record the route, launch nothing.
-template <bool A_KC, bool B_KC>
-static int launch_gemm_bf16(GemmArgs g, int planes, hipStream_t s, const GemmRec* rec) {
-    static_assert(A_KC, "forward / dgrad layouts only; the weight gradient goes through launch_wgrad_bf16");
-    g.vecA = bf16_vec<true>(g.A, g.lda, g.M, g.K);
-    g.vecB = bf16_vec<B_KC>(g.B, g.ldb, g.N, g.K);
-    g.kchunk = g.K;
-    int tm, tn;
-    bf16_pick_tile(g.M, g.N, planes, &tm, &tn);
-    if (rec) {
-        gemm_record(rec, bf16_family(planes), tm, tn, 0, 0, 1, g.vecA, g.vecB, 0);
-        return 0;
-    }
-    dim3 grid((unsigned)cdiv(g.N, 64 * tn), (unsigned)cdiv(g.M, 64 * tm), 1);
-    if (planes == 2) {
-        if (tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 1, 2, 2>(g, grid, s);
-        else launch_gemm_bf16_v<A_KC, B_KC, 1, 1, 2>(g, grid, s);
-    } else if (tm == 2 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 2, 2, 1>(g, grid, s);
-    else if (tm == 1 && tn == 2) launch_gemm_bf16_v<A_KC, B_KC, 1, 2, 1>(g, grid, s);
-    else launch_gemm_bf16_v<A_KC, B_KC, 1, 1, 1>(g, grid, s);
-    CDLRM_LAUNCH_CHECK();
-    return 0;
-}
-
 // Contraction slabs of a bf16 weight gradient over the batch M: ~1024 workgroups of 64x64 over `tiles` output tiles, each slab
 // at least 4 K tiles deep, cut on K-tile boundaries.  Returns the slab length (kchunk); the slab count is cdiv(M, kchunk).
 static inline int64_t bf16_wgrad_kchunk(int64_t M, int64_t tiles, int64_t max_splits) {

@@ -17,7 +17,7 @@
 //     i.e. 16 different 16-B bank slots of the 256-B bank row -> conflict-free.
 //   contraction-strided operand: [32][rows] floats as it lies in memory; fragments are ds_read_b32 along the rows
 //     (32 consecutive floats per lane half: conflict-free).
-// Requirements (else the caller falls back to k_gemm): contraction range of every split a multiple of 32, 16-byte
+// Requirements (gemm2_applies; else gemm_plan falls back to k_gemm): contraction range of every split a multiple of 32, 16-byte
 // loadable rows (the vecA / vecB flags), extents >= 4 along vectorised non-contraction directions.
 #pragma once
 #include "gemm.h"
@@ -226,7 +226,7 @@ __device__ __forceinline__ void g2_epilogue_full(const GemmArgs& g, f32x16 (&acc
 }
 
 // what g2_epilogue_full can take: forward = bias (absent or 16-byte loadable) + activation, no mask; dgrad = an activation mask
-// with 16-byte loadable rows (or none), no bias / activation.  `fastep` is set by the host (launch_gemm) from the debug switch.
+// with 16-byte loadable rows (or none), no bias / activation.  `fastep` is set by the host (gemm_args) from the debug switch.
 template <bool B_KC>
 __host__ __device__ __forceinline__ bool g2_full_ok(const GemmArgs& g) {
     if (!g.fastep) return false;
@@ -480,94 +480,9 @@ static inline bool gemm2_applies(const GemmArgs& g) {
 #define G2_EXTRA_LDS(tm, tn) 0
 #endif
 template <bool A_KC, bool B_KC>
-static void launch_gemm2(const GemmArgs& g, int tm, int tn, int splits, hipStream_t s) {
-    dim3 grid((unsigned)cdiv(g.N, 64 * tn), (unsigned)cdiv(g.M, 64 * tm), (unsigned)splits);
-    const size_t dyn = (size_t)G2_EXTRA_LDS(tm, tn);
+static void launch_gemm2(const GemmArgs& g, int tm, int tn, dim3 grid, size_t dyn, hipStream_t s) {
     if (tm == 2 && tn == 2) CDLRM_LAUNCH_EV((k_gemm2<A_KC, B_KC, 2, 2>), grid, dim3(256), dyn, s, g);
     else if (tm == 2 && tn == 1) CDLRM_LAUNCH_EV((k_gemm2<A_KC, B_KC, 2, 1>), grid, dim3(256), dyn, s, g);
     else if (tm == 1 && tn == 2) CDLRM_LAUNCH_EV((k_gemm2<A_KC, B_KC, 1, 2>), grid, dim3(256), dyn, s, g);
     else CDLRM_LAUNCH_EV((k_gemm2<A_KC, B_KC, 1, 1>), grid, dim3(256), dyn, s, g);
-}
-
-// the wide kernel (gemm_wide.h: k_gemm3, one workgroup per CU on 128x128 tiles) takes the un-split forward / dgrad GEMMs whose
-// tiles fill the chip; defined in gemm_wide.h, which a translation unit that calls launch_gemm includes instead of this file
-template <bool A_KC, bool B_KC>
-static bool gemm3_try(const GemmArgs& g, int splits, hipStream_t s, const GemmRec* rec);
-
-// rec != nullptr: record the route in *rec->out, launch nothing (gemm.h: GemmRec)
-template <bool A_KC, bool B_KC>
-static int launch_gemm(GemmArgs g, int splits, hipStream_t s, const GemmRec* rec = nullptr) {
-    if (g.K < 4) g.vecA = g.vecB = 0;
-    if constexpr (A_KC || !B_KC) {
-        if (gemm3_try<A_KC, B_KC>(g, splits, s, rec)) {
-            if (!rec) CDLRM_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    // (long batches with a narrow output -- the 256 -> 128 layer at M = 8192, forward: 256 tiles of 64x64, and its weight
-    //  gradient: 8 tiles x 32 slabs of the batch -- are better off on the LDS-DMA kernel's 64x64 tile than on the LDS-free
-    //  one: 10.3 against 13.1 us forward)
-    const bool long_narrow = (g.M >= 4096 || g.K >= 4096) && cdiv(g.M, 64) * cdiv(g.N, 64) * splits >= 256 &&
-                             gemm2_applies<A_KC, B_KC>(g);
-    if (gemm_use_direct(g.M, g.N, splits) && !long_narrow) {
-        launch_gemm_direct<A_KC, B_KC>(g, splits, s, rec);
-        if (!rec) CDLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (gemm2_applies<A_KC, B_KC>(g)) {
-        // LDS-DMA kernel.  Measured on the c3 layer shapes (tools/gemm2_bench.hip, M = 8192, all three layouts): 128x64
-        // tiles win wherever they leave MORE than one workgroup per CU (512-wide layers 40-42 us against 43-47 for 64x64), the
-        // 64x64 tile from there down (128-wide output: 9.9 against 14.3 us).  At exactly one per CU -- the 256-wide layers at
-        // M = 8192: top forward 512 -> 256, bottom forward 512 -> 256, bottom dgrad 256 <- 128 -- 512 workgroups of 64x64 beat
-        // 256 of 128x64 in the step: 0.5740 against 0.5767 ms, six rounds of 110 steps each, every round (round 4; bit-identical:
-        // a tile's k order does not depend on its shape)
-        int tm2 = 2, tn2 = 1;
-        if (g.M <= 64 || cdiv(g.M, 128) * cdiv(g.N, 64) * splits <= 256) tm2 = 1;
-        // ... and so do the short contractions (K <= 256 un-split: the dgrads 512 <- 256 of both sub-networks, eight K tiles per
-        // workgroup, where prologue and store tail weigh most): 1024 workgroups of 64x64 instead of 512 of 128x64, 0.5681 against
-        // 0.5739 ms per c3 step, six rounds, every round.  (EVERY forward / dgrad on 64x64: 0.5776 against 0.5747; the weight
-        // gradients too: 0.5819 / 0.5863 -- the 512-wide layers keep 128x64.)
-        if (splits == 1 && g.K <= 256) tm2 = 1;
-        // ... and where a CU gets >= 4 tiles of 128x128 (un-split forward / dgrad at M = 65536: c5) that shape, one workgroup per
-        // CU, a third less LDS fill per MFMA: stand-alone 297.5 against 313.7 us (512 x 512 forward), 283.1 / 297.7 (512 <- 480),
-        // 158.7 / 165.9 (256 <- 512), dgrad 318.0 / 322.5 (profiles/r05_gemm_big_tiles.txt); in the c5 step 3.6927 against
-        // 3.7159 ms, ten rounds (-0.6 %; cdlrm_debug_set(6, 16): 128x64 as before).  Bit-identical (a tile's k order does not
-        // depend on its shape).  At M = 8192 the same shape is one tile per CU and loses (round 2, and again in round 5).
-        if (!(g_cdlrm_debug[6] & 16) && A_KC && splits == 1 && tm2 == 2 && cdiv(g.M, 128) * cdiv(g.N, 128) >= 1024) tn2 = 2;
-        // (the same shape for the split-M weight gradients of a long batch: a tie, c5 3.7017 against 3.6995 ms, ten rounds -- not taken)
-        if (rec) {      // full tiles of an un-split forward / dgrad take g2_epilogue_full where g2_full_ok holds (gemm2_tile_body)
-            gemm_record(rec, CDLRM_ROUTE_GEMM2, tm2, tn2, 0, 0, splits, 1, 1, A_KC && splits == 1 && g2_full_ok<B_KC>(g));
-            return 0;
-        }
-        launch_gemm2<A_KC, B_KC>(g, tm2, tn2, splits, s);
-        CDLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    if (g.N <= 32 || g.M <= 32) {
-        // a 13-wide (or 1-wide) side that the DMA kernel cannot load: the LDS-free kernel's 32x32 tiles waste less of the
-        // MFMA than the 64x64 staged tile, whatever the number of slabs (the 512 x 13 weight gradient at M = 65536, 128
-        // slabs: 1100 us on the tiled kernel, c5's longest launch)
-        launch_gemm_direct<A_KC, B_KC>(g, splits, s, rec);
-        if (!rec) CDLRM_LAUNCH_CHECK();
-        return 0;
-    }
-    int tm, tn;
-    gemm_pick_tile(g.M, g.N, splits, &tm, &tn);
-    if (g.N <= 32) tn = 1;
-    if (g.M <= 32) tm = 1;
-    if (tm == 2 && tn == 1) { tm = 1; tn = g.N <= 64 ? 1 : 2; }     // 128x64 is never the best shape here
-    // vector loads also need extents >= 4 in the vectorised direction (clamped addresses must stay inside)
-    if (g.K < 4) g.vecA = g.vecB = 0;
-    if (!A_KC && g.M < 4) g.vecA = 0;
-    if (!B_KC && g.N < 4) g.vecB = 0;
-    if (rec) {
-        gemm_record(rec, CDLRM_ROUTE_GEMM, tm, tn, 0, 0, splits, g.vecA, g.vecB, 0);
-        return 0;
-    }
-    dim3 grid((unsigned)cdiv(g.N, 64 * tn), (unsigned)cdiv(g.M, 64 * tm), (unsigned)splits);
-    if (tm == 2 && tn == 2) launch_gemm_v<A_KC, B_KC, 2, 2>(g, grid, s);
-    else if (tm == 1 && tn == 2) launch_gemm_v<A_KC, B_KC, 1, 2>(g, grid, s);
-    else launch_gemm_v<A_KC, B_KC, 1, 1>(g, grid, s);
-    CDLRM_LAUNCH_CHECK();
-    return 0;
 }

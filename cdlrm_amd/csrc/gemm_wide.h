@@ -496,14 +496,10 @@ static inline bool gemm3_applies(const GemmArgs& g) {
 }
 
 template <bool A_KC, bool B_KC, int IM, int JN, int NS>
-static void launch_gemm3(const GemmArgs& g, int splits, hipStream_t s) {
-    dim3 grid((unsigned)cdiv(g.N, 32 * JN), (unsigned)cdiv(g.M, 32 * IM), (unsigned)splits);
+static void launch_gemm3(const GemmArgs& g, dim3 grid, hipStream_t s) {
     CDLRM_LAUNCH_EV((k_gemm3<A_KC, B_KC, IM, JN, NS>), grid, dim3(256), 0, s, g);
 }
 
-// launch_gemm's hook (gemm_glds.h).  Taken where the 128x128 tiles fill whole rounds of one workgroup per CU (>= 90 % of the
-// slots of the last round too: c3's 512-wide layers at M = 8192 are exactly 256 tiles, c5's 2048 and 1024) -- measured against
-// k_gemm2 on one box (tools/gemm3_bench.hip, profiles/r06_gemm3_vs_gemm2.txt).
 // the launching path's compute-unit count (asked once; 0: the device could not be asked)
 static inline int gemm_device_cus() {
     static int n_cu = 0;
@@ -514,45 +510,4 @@ static inline int gemm_device_cus() {
         n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     return n_cu;
-}
-
-template <bool A_KC, bool B_KC>
-static bool gemm3_try(const GemmArgs& g, int splits, hipStream_t s, const GemmRec* rec) {
-    // Only for launches the caller marks as running ALONE (CDLRM_GEMM_ALONE: the top MLP's forward and its dgrad chain in the
-    // training step).  Beside the weight-gradient GEMMs of the side queues a workgroup of this kernel (96 KB of LDS, 340
-    // registers per lane) waits for a CU to drain: the bottom MLP's 512 <- 256 dgrad took 115.6 us there against 62.9 on
-    // k_gemm2's 1024 small workgroups, the c3 step 0.5790 against 0.5580 ms (profiles/r06_ab_gemm3_in_step.txt).
-    // cdlrm_debug_set(6, 32): never; (6, 256): every eligible launch (the stand-alone benches).
-    if (g_cdlrm_debug[6] & 32) return false;
-    if (!A_KC && (g_cdlrm_debug[6] & 512)) {
-        // (A/B: the split-M weight gradients on this kernel)
-    } else if (!A_KC && (g_cdlrm_debug[6] & 1024) && (int64_t)g.M * g.N >= 512 * 480) {
-        // (A/B: the two 512-wide ones only)
-    } else if (!g.alone && !(g_cdlrm_debug[6] & 256)) return false;
-    const int64_t kc = g.kchunk < g.K ? g.kchunk : g.K;
-    if ((A_KC && splits != 1) || kc < 2 * G3_BK || !gemm3_applies<A_KC, B_KC>(g)) return false;
-    const int n_cu = rec ? rec->n_cu : gemm_device_cus();      // (a route query touches no device)
-    if (n_cu <= 0) return false;
-    // 128x128 tiles where they fill whole rounds of one workgroup per CU (>= 90 % of the last round's slots), else 64x128 tiles
-    // under the same rule (M = 8192 x 256-wide layers, per-rank batches of 4096 x 512-wide: 256 tiles)
-    auto fills = [&](int64_t tiles) { return tiles * 10 >= cdiv(tiles, n_cu) * n_cu * 9; };
-    const int64_t t128 = cdiv(g.M, 128) * cdiv(g.N, 128) * splits, t64 = cdiv(g.M, 64) * cdiv(g.N, 128) * splits;
-    // (short contractions, K <= 256, on k_gemm2's 64x64 tiles instead: c3 step 0.5594 against 0.5558 ms; on the 64x128 tiles: a tie)
-    // (ragged tiles -- N = 480: a quarter of the tiles take the generic epilogue behind the loop -- only where every CU has ONE
-    //  tile: at M = 65536 the 480 <- 512 dgrad took 333 us here against 304 on k_gemm2, at M = 8192 44.4 against 47.2)
-    if ((g.N % 128 != 0 || g.M % 64 != 0) && t128 > n_cu) return false;
-    int im;
-    if (fills(t128)) im = 4;
-    else if (A_KC && fills(t64)) im = 2;
-    else return false;
-    if (rec) {
-        // tiles inside the matrix finish under the last group's MFMAs where the epilogue operands are 16-byte loadable (k_gemm3 `fast`)
-        const bool vbias = g.bias == nullptr || (((uintptr_t)g.bias) & 15) == 0;
-        const bool vmask = g.mask_act == 0 || ((((uintptr_t)g.mask) & 15) == 0 && (g.ldmask & 3) == 0);
-        gemm_record(rec, CDLRM_ROUTE_GEMM3, im, 4, 0, 0, splits, 1, 1, vbias && vmask);
-        return true;
-    }
-    if (im == 4) launch_gemm3<A_KC, B_KC, 4, 4, 3>(g, splits, s);
-    else launch_gemm3<A_KC, B_KC, 2, 4, 3>(g, splits, s);
-    return true;
 }

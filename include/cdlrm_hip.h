@@ -536,8 +536,8 @@ typedef struct cdlrm_gemm_route {
 } cdlrm_gemm_route;
 /* The plan of the same calls without the launches: same arguments (pointers are looked at for their alignment only, nothing is
  * read or written, no device is touched), plus n_cu, the compute-unit count the wide kernel's rule is evaluated for (256 on
- * MI355X).  The route comes out of the same decision code the launching call runs.  fwd: out[0]; bwd: out[0] the dgrad GEMM,
- * out[1] the weight-gradient GEMM (family CDLRM_ROUTE_NONE where the call issues none). */
+ * MI355X).  The route is copied out of the plan the launching call builds: the launch reads the same plan.  fwd: out[0]; bwd:
+ * out[0] the dgrad GEMM, out[1] the weight-gradient GEMM (family CDLRM_ROUTE_NONE where the call issues none). */
 int cdlrm_linear_fwd_route(const float* X, int64_t ld_x, const float* W, const float* bias, float* Y,
                            int64_t ld_y, int64_t M, int32_t N, int32_t K, int32_t act, void* stream, int32_t n_cu,
                            cdlrm_gemm_route* out);

@@ -1,6 +1,6 @@
 """Every dense GEMM route of cdlrm_linear_fwd / cdlrm_linear_bwd against a plain float64 reference.
 
-launch_gemm (csrc/gemm_glds.h, gemm3_try in gemm_wide.h) and the small-K branches of cdlrm_linear_fwd (dense.hip) send an MLP
+gemm_plan (csrc/gemm_plan.h: the matrix-core kernels and the forward's small-K kernels of dense.hip) sends an MLP
 GEMM to one of seven kernel families by shape, alignment, split count, the CDLRM_GEMM_ALONE hint and the CU count; each family has
 its own epilogue code for the bias, the activation and the dgrad's fused activation mask (x_act).  One table of cases below, each
 with the route it is meant to reach, serves three checks:

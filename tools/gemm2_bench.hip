@@ -93,7 +93,7 @@ static int run_case(const char* name, int64_t M, int N, int64_t K, int splits, b
         hipMemset(C0, 0, cn * 4); hipMemset(C1, 0xff, cn * 4); hipMemset(C2, 0xee, cn * 4);
         old_launch<A_KC, B_KC>(g0, tm, tn, zs);
         if (!gemm2_applies<A_KC, B_KC>(g1)) { printf("%s: DMA kernel does not apply\n", name); return 1; }
-        launch_gemm2<A_KC, B_KC>(g1, tm, tn, zs, 0);
+        launch_gemm2<A_KC, B_KC>(g1, tm, tn, gemm_grid(g1, 64 * tm, 64 * tn, zs), (size_t)G2_EXTRA_LDS(tm, tn), 0);
         hipDeviceSynchronize();
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { printf("%s tile %dx%d: %s\n", name, 64 * tm, 64 * tn, hipGetErrorString(e)); return 1; }
@@ -119,7 +119,7 @@ static int run_case(const char* name, int64_t M, int N, int64_t K, int splits, b
             std::vector<double> a, b, c;
             for (int round = 0; round < 5; ++round) {
                 a.push_back(time_us([&]() { old_launch<A_KC, B_KC>(g0, tm, tn, zs); }, 20));
-                b.push_back(time_us([&]() { launch_gemm2<A_KC, B_KC>(g1, tm, tn, zs, 0); }, 20));
+                b.push_back(time_us([&]() { launch_gemm2<A_KC, B_KC>(g1, tm, tn, gemm_grid(g1, 64 * tm, 64 * tn, zs), (size_t)G2_EXTRA_LDS(tm, tn), 0); }, 20));
                 c.push_back(0.0);
             }
             std::sort(a.begin(), a.end()); std::sort(b.begin(), b.end()); std::sort(c.begin(), c.end());
@@ -128,7 +128,7 @@ static int run_case(const char* name, int64_t M, int N, int64_t K, int splits, b
 #ifdef GEMM2_STAMP
         {
             hipMemset(C1, 0, 16);
-            launch_gemm2<A_KC, B_KC>(g1, tm, tn, zs, 0);
+            launch_gemm2<A_KC, B_KC>(g1, tm, tn, gemm_grid(g1, 64 * tm, 64 * tn, zs), (size_t)G2_EXTRA_LDS(tm, tn), 0);
             hipDeviceSynchronize();
             static unsigned long long hs[8 * 4096];
             hipMemcpyFromSymbol(hs, HIP_SYMBOL(g2_stamps), sizeof(hs));

@@ -117,11 +117,11 @@ static void run(const char* name, int64_t M, int N, int64_t K) {
     };
     one("gemm2 128x64", [&]() { launch2<true, B_KC, 2, 1>(g1); }, 0);
     one("gemm2 128x128", [&]() { launch2<true, B_KC, 2, 2>(g1); }, 0);
-    one("gemm3 128x128 S3", [&]() { launch_gemm3<true, B_KC, 4, 4, 3>(g1, 1, 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 128)));
-    one("gemm3 128x128 S4", [&]() { launch_gemm3<true, B_KC, 4, 4, 4>(g1, 1, 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 128)));
+    one("gemm3 128x128 S3", [&]() { launch_gemm3<true, B_KC, 4, 4, 3>(g1, gemm_grid(g1, 128, 128, 1), 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 128)));
+    one("gemm3 128x128 S4", [&]() { launch_gemm3<true, B_KC, 4, 4, 4>(g1, gemm_grid(g1, 128, 128, 1), 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 128)));
     one("gemm2 64x64", [&]() { launch2<true, B_KC, 1, 1>(g1); }, 0);
-    one("gemm3 64x128 S3", [&]() { launch_gemm3<true, B_KC, 2, 4, 3>(g1, 1, 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 64)));
-    one("gemm3 64x128 S4", [&]() { launch_gemm3<true, B_KC, 2, 4, 4>(g1, 1, 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 64)));
+    one("gemm3 64x128 S3", [&]() { launch_gemm3<true, B_KC, 2, 4, 3>(g1, gemm_grid(g1, 64, 128, 1), 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 64)));
+    one("gemm3 64x128 S4", [&]() { launch_gemm3<true, B_KC, 2, 4, 4>(g1, gemm_grid(g1, 64, 128, 1), 0); }, (unsigned)(cdiv(N, 128) * cdiv(M, 64)));
     hipFree(A); hipFree(B); hipFree(bias); hipFree(mask); hipFree(C0); hipFree(C1);
 }
 // weight-gradient layout: dW[N, K] = dZ[M, N]^T X[M, K], split over the batch into `splits` slabs (+ the bias gradient's partials)
@@ -140,7 +140,7 @@ static void run_wgrad(const char* name, int64_t M, int N, int K, int splits) {
         dim3 grid((unsigned)cdiv(a.N, 64), (unsigned)cdiv(a.M, 128), (unsigned)zs);
         hipLaunchKernelGGL((k_gemm2<false, false, 2, 1>), grid, dim3(256), 0, 0, a);
     };
-    auto l3 = [&](const GemmArgs& a) { launch_gemm3<false, false, 4, 4, 3>(a, zs, 0); };
+    auto l3 = [&](const GemmArgs& a) { launch_gemm3<false, false, 4, 4, 3>(a, gemm_grid(a, 128, 128, zs), 0); };
     l2(g0); hipMemset(S1, 0xff, cnt * zs * 4); hipMemset(c1, 0xff, (size_t)zs * N * 4); l3(g1); hipDeviceSynchronize();
     std::vector<float> h0(cnt * zs), h1(cnt * zs), k0((size_t)zs * N), k1((size_t)zs * N);
     hipMemcpy(h0.data(), S0, h0.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(h1.data(), S1, h1.size() * 4, hipMemcpyDeviceToHost);

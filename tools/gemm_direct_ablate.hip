@@ -19,6 +19,19 @@ CdlrmStopState* cdlrm_stop_state() {
     return &st;
 }
 
+// the short-batch kernel gemm_plan (csrc/gemm_plan.h) would take for an un-split g: staged, or LDS-free with the aligned / generic loader
+template <bool A_KC, bool B_KC>
+static void launch_short(GemmArgs g) {
+    g.vecC = direct_vec_c(g);
+    const DirectVariant v = direct_variant<A_KC, B_KC>(g);
+    GemmPlan p;
+    memset(&p, 0, sizeof(p));
+    p.grid = gemm_grid(g, 32, 32, 1);
+    p.r.mode = v.mode; p.r.aligned = v.aligned; p.r.vec_a = A_KC && g.vecA; p.r.vec_b = B_KC && g.vecB;
+    if (v.staged) launch_gemm_staged<A_KC, B_KC>(g, p.grid, v.mode, 0);
+    else launch_gemm_direct<A_KC, B_KC>(p, g, 0);
+}
+
 template <typename F>
 static double time_us(F launch) {
     hipEvent_t e0, e1;
@@ -51,21 +64,21 @@ int main(int argc, char** argv) {
         GemmArgs g = gemm_args();
         g.A = X; g.lda = K; g.B = W; g.ldb = K; g.C = Y; g.ldc = N; g.M = B; g.N = N; g.K = K; g.kchunk = K;
         g.bias = b; g.act = 1; g.vecA = g.vecB = 1;
-        const double us = time_us([&]() { launch_gemm_direct<true, true>(g, 1, 0); });
+        const double us = time_us([&]() { launch_short<true, true>(g); });
         printf("DABL=%d fwd   %ldx%dx%d  %7.1f us %6.1f TF\n", DABL, (long)B, N, K, us, fl / us / 1e6);
     }
     {
         GemmArgs g = gemm_args();
         g.A = dY; g.lda = N; g.B = W; g.ldb = K; g.C = dX; g.ldc = K; g.M = B; g.N = K; g.K = N; g.kchunk = N;
         g.vecA = g.vecB = 1; g.mask = X; g.ldmask = K; g.mask_act = 1;
-        const double us = time_us([&]() { launch_gemm_direct<true, false>(g, 1, 0); });
+        const double us = time_us([&]() { launch_short<true, false>(g); });
         printf("DABL=%d dgrad %ldx%dx%d  %7.1f us %6.1f TF\n", DABL, (long)B, N, K, us, fl / us / 1e6);
     }
     {
         GemmArgs g = gemm_args();
         g.A = dY; g.lda = N; g.B = X; g.ldb = K; g.C = dW; g.ldc = K; g.M = N; g.N = K; g.K = B; g.kchunk = B;
         g.vecA = g.vecB = 1; g.colsum = b;
-        const double us = time_us([&]() { launch_gemm_direct<false, false>(g, 1, 0); });
+        const double us = time_us([&]() { launch_short<false, false>(g); });
         printf("DABL=%d wgrad %ldx%dx%d  %7.1f us %6.1f TF\n", DABL, (long)B, N, K, us, fl / us / 1e6);
     }
     return 0;
