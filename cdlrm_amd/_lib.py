@@ -99,6 +99,9 @@ PROTOTYPES = {
     "cdlrm_plan_probe": (C.c_int, [vp, C.POINTER(Plan), vp]),
     "cdlrm_plan_offsets_sync": (C.c_int, [vp, C.POINTER(Plan), vp, vp, vp, vp]),
     "cdlrm_plan_assign": (C.c_int, [vp, C.POINTER(Plan), vp, c_u64, vp]),
+    "cdlrm_plan_count_reset": (C.c_int, [vp, C.POINTER(Plan), vp, vp]),
+    "cdlrm_plan_count_add": (C.c_int, [vp, C.POINTER(Plan), vp, c_i64, c_i64, vp, vp]),
+    "cdlrm_plan_assign_fill": (C.c_int, [vp, C.POINTER(Plan), vp, vp, vp]),
     "cdlrm_plan_fetch": (C.c_int, [vp, C.POINTER(Plan), C.POINTER(vp), C.c_int, vp]),
     "cdlrm_plan_commit": (C.c_int, [vp, C.POINTER(Plan), vp]),
     "cdlrm_plan_writeback": (C.c_int, [vp, C.POINTER(Plan), C.POINTER(vp), C.c_int, vp]),

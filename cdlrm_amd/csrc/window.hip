@@ -377,18 +377,11 @@ __global__ void __launch_bounds__(WIN_THREADS) k_prot_clear(const TableDesc* __r
     }
 }
 
-extern "C" int cdlrm_plan_assign(cdlrm_ctx* ctx, const cdlrm_plan* plan, const float* q, uint64_t seed, void* stream) {
-    CDLRM_REQUIRE(ctx && plan, "null argument");
-    CDLRM_REQUIRE(plan->winner && plan->win_claim && plan->win_idx && plan->win_row && plan->win_tag && plan->win_off &&
-                      plan->way && plan->hit && plan->kept && plan->flags,
-                  "plan buffers missing");
-    hipStream_t s = (hipStream_t)stream;
+// The tail both insert policies share: way[] and winner[] are filled; list the winners, clear the scratch.
+static int plan_assign_tail(cdlrm_ctx* ctx, const cdlrm_plan* plan, hipStream_t s) {
     int64_t gx = cdiv(plan->cap_uniq, WIN_THREADS);
     if (gx > WIN_BLOCKS) gx = WIN_BLOCKS;
     if (gx < 1) gx = 1;
-    hipLaunchKernelGGL(k_assign, dim3((unsigned)gx), dim3(WIN_THREADS), 0, s, ctx->d_tab, ctx->T, ctx->ways, plan->uniq,
-                       plan->uniq_off, plan->kept, plan->kept_off, plan->cap_uniq,
-                       (const unsigned long long*)plan->prot, q, seed, plan->way, plan->winner);
     uint8_t* flags = plan->flags;
     hipLaunchKernelGGL(k_winner_flags, dim3((unsigned)gx), dim3(WIN_THREADS), 0, s, ctx->d_tab, ctx->T, plan->uniq,
                        plan->uniq_off, plan->kept, plan->kept_off, plan->cap_uniq, plan->way, plan->winner, flags);
@@ -408,6 +401,222 @@ extern "C" int cdlrm_plan_assign(cdlrm_ctx* ctx, const cdlrm_plan* plan, const f
                        plan->uniq_off, plan->cap_uniq, plan->hit, (unsigned long long*)plan->prot);
     CDLRM_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int cdlrm_plan_assign(cdlrm_ctx* ctx, const cdlrm_plan* plan, const float* q, uint64_t seed, void* stream) {
+    CDLRM_REQUIRE(ctx && plan, "null argument");
+    CDLRM_REQUIRE(plan->winner && plan->win_claim && plan->win_idx && plan->win_row && plan->win_tag && plan->win_off &&
+                      plan->way && plan->hit && plan->kept && plan->flags,
+                  "plan buffers missing");
+    hipStream_t s = (hipStream_t)stream;
+    int64_t gx = cdiv(plan->cap_uniq, WIN_THREADS);
+    if (gx > WIN_BLOCKS) gx = WIN_BLOCKS;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(k_assign, dim3((unsigned)gx), dim3(WIN_THREADS), 0, s, ctx->d_tab, ctx->T, ctx->ways, plan->uniq,
+                       plan->uniq_off, plan->kept, plan->kept_off, plan->cap_uniq,
+                       (const unsigned long long*)plan->prot, q, seed, plan->way, plan->winner);
+    return plan_assign_tail(ctx, plan, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// K3 "fill": the opt-in insert policy that replaces main_no_ddp.py:171-204 -- a defined departure from the reference.
+// No random draw and no contest: inside one set the claimants are ranked by the number of lookups the window makes of
+// them (clamped to 65 535; descending), then by index (ascending), and the claimant of rank r takes the set's r-th free
+// way -- empty ways (tag -1) first, then occupied ones, each group by ascending way number.  min(claimants, free ways)
+// rows are inserted in every set; the result is a function of (tags, window) alone.
+//   k_count_add : one pass over the window's lookups; count[u] += 1 for the lookups of uniq[u] (integer atomics: the sum
+//                 does not depend on the order).  Equal destinations are combined inside the wave first, and a counter a
+//                 plain read already shows at the clamp takes no more adds (a stale read can only under-see, and every
+//                 value >= 65 535 means the same priority -- the argument k_bm_set makes for its bitmap).
+//   k_fill_post / k_fill_take : round r = 0 .. ways - 1.  Every set with claimants and free ways left has placed exactly r
+//                 claimants before round r.  post: each unplaced claimant whose set has more than r free ways raises the
+//                 set's claim word to (r + 1) << 48 | priority << 32 | (0x7fffffff - m) by a 64-bit atomicMax (the round
+//                 tag makes a later round's keys beat the earlier winner's, so the word needs no reset in between); take:
+//                 the claimant whose key the word holds takes the r-th free way.  way[m] doubles as the state:
+//                 0xFF = not placed yet, 0xFE = never placed (rank >= free ways).
+//   k_fill_finish : claimants that were not placed get a way another claimant won (the set's lowest free way: all of them
+//                 are taken), which is what the shared tail expects of a loser; the claim words go back to zero.
+// ---------------------------------------------------------------------------------------------
+#define FILL_CLAMP 65535
+#define FILL_COMBINE_ROUNDS 4
+
+__global__ void __launch_bounds__(WIN_THREADS) k_count_add(const TableDesc* __restrict__ tab, const int64_t* __restrict__ idx,
+                                                           int64_t n, int64_t ld_idx, const int64_t* __restrict__ uniq,
+                                                           const int64_t* __restrict__ uniq_off, int64_t cap,
+                                                           int32_t* count) {
+    const int t = blockIdx.y;
+    const int64_t n_rows = tab[t].n_rows;
+    const int64_t seg_lo = min(uniq_off[t], cap), seg_hi = min(uniq_off[t + 1], cap);
+    const int64_t* row = idx + (int64_t)t * ld_idx;
+    const int lane = threadIdx.x & 63;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n_round = cdiv_dev(n, stride) * stride;      // whole waves stay in the loop for the cross-lane combine
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_round; i += stride) {
+        int u = -1;                                            // (cap_uniq < 2^31)
+        if (i < n) {
+            const int64_t v = row[i];
+            if (v >= 0 && v < n_rows) {
+                int64_t lo = seg_lo, hi = seg_hi;
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (uniq[mid] < v) lo = mid + 1; else hi = mid;
+                }
+                // not in the (possibly capacity-cut) list: counted nowhere
+                if (lo < seg_hi && uniq[lo] == v && count[lo] < FILL_CLAMP) u = (int)lo;
+            }
+        }
+        // Zipf windows: most lanes of a wave name a handful of rows -- one atomic per distinct row for the first few
+        for (int r = 0; r < FILL_COMBINE_ROUNDS; ++r) {
+            const unsigned long long act = __ballot(u >= 0);
+            if (!act) break;
+            const int leader = __ffsll((long long)act) - 1;
+            const int lu = __shfl(u, leader, 64);
+            const unsigned long long same = __ballot(u == lu);
+            if (u == lu) {
+                if (lane == leader) atomicAdd(&count[u], (int32_t)__popcll(same));
+                u = -1;
+            }
+        }
+        if (u >= 0) atomicAdd(&count[u], 1);
+    }
+}
+
+struct FillClaimant {
+    int64_t set, P, set_slot;        // set inside the table, the table's sets, the set's place in the flat per-set arrays
+    int t;
+    unsigned long long avail;        // the set's unprotected ways
+    unsigned long long key;          // what the claimant posts in `round`
+};
+
+__device__ __forceinline__ FillClaimant fill_claimant(const TableDesc* __restrict__ tab, int T, int ways,
+                                                      const int64_t* __restrict__ uniq, const int64_t* __restrict__ uniq_off,
+                                                      const int32_t* __restrict__ kept,
+                                                      const unsigned long long* __restrict__ prot,
+                                                      const int32_t* __restrict__ count, int round, int64_t m) {
+    FillClaimant c;
+    const int64_t u = kept[m];
+    c.t = table_of(uniq_off, T, u);
+    c.P = tab[c.t].P;
+    c.set = mod_sets(uniq[u], c.P);
+    c.set_slot = tab[c.t].set_base + c.set;
+    const unsigned long long full = ways == 64 ? ~0ull : ((1ull << ways) - 1);
+    c.avail = ~prot[c.set_slot] & full;
+    const unsigned long long pri = count ? (unsigned long long)min(max(count[u], 0), FILL_CLAMP) : 0ull;
+    c.key = ((unsigned long long)(round + 1) << 48) | (pri << 32) | (unsigned long long)(0x7fffffff - (int32_t)m);
+    return c;
+}
+
+__global__ void __launch_bounds__(WIN_THREADS) k_fill_post(const TableDesc* __restrict__ tab, int T, int ways,
+                                                           const int64_t* __restrict__ uniq,
+                                                           const int64_t* __restrict__ uniq_off,
+                                                           const int32_t* __restrict__ kept,
+                                                           const int64_t* __restrict__ kept_off, int64_t cap,
+                                                           const unsigned long long* __restrict__ prot,
+                                                           const int32_t* __restrict__ count, int round,
+                                                           uint8_t* __restrict__ way, unsigned long long* __restrict__ claim) {
+    const int64_t M = min(kept_off[T], cap);
+    for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (int64_t)gridDim.x * blockDim.x) {
+        if (round > 0 && way[m] != 0xFF) continue;             // placed, or out for good
+        const FillClaimant c = fill_claimant(tab, T, ways, uniq, uniq_off, kept, prot, count, round, m);
+        if (round >= __popcll(c.avail)) { way[m] = 0xFE; continue; }
+        atomicMax(&claim[c.set_slot], c.key);
+    }
+}
+
+__global__ void __launch_bounds__(WIN_THREADS) k_fill_take(const TableDesc* __restrict__ tab, int T, int ways,
+                                                           const int64_t* __restrict__ tags,
+                                                           const int64_t* __restrict__ uniq,
+                                                           const int64_t* __restrict__ uniq_off,
+                                                           const int32_t* __restrict__ kept,
+                                                           const int64_t* __restrict__ kept_off, int64_t cap,
+                                                           const unsigned long long* __restrict__ prot,
+                                                           const int32_t* __restrict__ count, int round,
+                                                           const unsigned long long* __restrict__ claim,
+                                                           uint8_t* __restrict__ way, int32_t* __restrict__ winner) {
+    const int64_t M = min(kept_off[T], cap);
+    for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (int64_t)gridDim.x * blockDim.x) {
+        if (round > 0 && way[m] != 0xFF) continue;
+        const FillClaimant c = fill_claimant(tab, T, ways, uniq, uniq_off, kept, prot, count, round, m);
+        if (claim[c.set_slot] != c.key) {
+            if (round == 0) way[m] = 0xFF;
+            continue;
+        }
+        // the set's round-th free way: empty ways first, then occupied ones, each by ascending way number
+        const int64_t* tg = tags + tab[c.t].tag_base + c.set * ways;
+        unsigned long long empty = 0ull;
+        for (int w = 0; w < ways; ++w)
+            if (((c.avail >> w) & 1ull) && tg[w] == -1) empty |= 1ull << w;
+        const int ne = __popcll(empty);
+        unsigned long long mask = round < ne ? empty : (c.avail & ~empty);
+        for (int k = round < ne ? round : round - ne; k > 0; --k) mask &= mask - 1;
+        if (!mask) continue;                                   // (cannot be: post lets only round < popcount(avail) claim)
+        const int wy = __ffsll((long long)mask) - 1;
+        way[m] = (uint8_t)wy;
+        winner[tab[c.t].row_base + c.P * wy + c.set] = (int32_t)m;     // one claimant per (set, round): no contest
+    }
+}
+
+__global__ void __launch_bounds__(WIN_THREADS) k_fill_finish(const TableDesc* __restrict__ tab, int T, int ways,
+                                                             const int64_t* __restrict__ uniq,
+                                                             const int64_t* __restrict__ uniq_off,
+                                                             const int32_t* __restrict__ kept,
+                                                             const int64_t* __restrict__ kept_off, int64_t cap,
+                                                             const unsigned long long* __restrict__ prot,
+                                                             uint8_t* __restrict__ way, unsigned long long* __restrict__ claim) {
+    const int64_t M = min(kept_off[T], cap);
+    for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += (int64_t)gridDim.x * blockDim.x) {
+        const FillClaimant c = fill_claimant(tab, T, ways, uniq, uniq_off, kept, prot, nullptr, 0, m);
+        if (way[m] >= 0xFE) way[m] = (uint8_t)(__ffsll((long long)c.avail) - 1);
+        claim[c.set_slot] = 0ull;                              // (every claimant of the set stores the same zero)
+    }
+}
+
+extern "C" int cdlrm_plan_count_reset(cdlrm_ctx* ctx, const cdlrm_plan* plan, int32_t* count, void* stream) {
+    CDLRM_REQUIRE(ctx && plan && count, "null argument");
+    CDLRM_REQUIRE(plan->cap_uniq >= 1, "plan buffers missing");
+    CDLRM_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)plan->cap_uniq, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int cdlrm_plan_count_add(cdlrm_ctx* ctx, const cdlrm_plan* plan, const int64_t* idx, int64_t n, int64_t ld_idx,
+                                    int32_t* count, void* stream) {
+    CDLRM_REQUIRE(ctx && plan && idx && count, "null argument");
+    CDLRM_REQUIRE(plan->uniq && plan->uniq_off, "plan buffers missing");
+    CDLRM_REQUIRE(n >= 1 && ld_idx >= n, "bad n / ld_idx");
+    CDLRM_REQUIRE(plan->cap_uniq < ((int64_t)1 << 31), "cap_uniq < 2^31");
+    int64_t gx = cdiv(n, WIN_THREADS);
+    if (gx > 1024) gx = 1024;
+    hipLaunchKernelGGL(k_count_add, dim3((unsigned)gx, (unsigned)ctx->T), dim3(WIN_THREADS), 0, (hipStream_t)stream, ctx->d_tab,
+                       idx, n, ld_idx, plan->uniq, plan->uniq_off, plan->cap_uniq, count);
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cdlrm_plan_assign_fill(cdlrm_ctx* ctx, const cdlrm_plan* plan, const int32_t* count, uint64_t* claim,
+                                      void* stream) {
+    CDLRM_REQUIRE(ctx && plan && claim, "null argument");
+    CDLRM_REQUIRE(ctx->tags, "cdlrm_ctx_bind_cache first");
+    CDLRM_REQUIRE(plan->winner && plan->win_claim && plan->win_idx && plan->win_row && plan->win_tag && plan->win_off &&
+                      plan->way && plan->hit && plan->kept && plan->flags,
+                  "plan buffers missing");
+    CDLRM_REQUIRE(plan->cap_uniq < ((int64_t)1 << 31), "cap_uniq < 2^31");
+    hipStream_t s = (hipStream_t)stream;
+    int64_t gx = cdiv(plan->cap_uniq, WIN_THREADS);
+    if (gx > WIN_BLOCKS) gx = WIN_BLOCKS;
+    if (gx < 1) gx = 1;
+    const unsigned long long* prot = (const unsigned long long*)plan->prot;
+    unsigned long long* cl = (unsigned long long*)claim;
+    for (int round = 0; round < ctx->ways; ++round) {
+        hipLaunchKernelGGL(k_fill_post, dim3((unsigned)gx), dim3(WIN_THREADS), 0, s, ctx->d_tab, ctx->T, ctx->ways, plan->uniq,
+                           plan->uniq_off, plan->kept, plan->kept_off, plan->cap_uniq, prot, count, round, plan->way, cl);
+        hipLaunchKernelGGL(k_fill_take, dim3((unsigned)gx), dim3(WIN_THREADS), 0, s, ctx->d_tab, ctx->T, ctx->ways, ctx->tags,
+                           plan->uniq, plan->uniq_off, plan->kept, plan->kept_off, plan->cap_uniq, prot, count, round,
+                           (const unsigned long long*)cl, plan->way, plan->winner);
+    }
+    hipLaunchKernelGGL(k_fill_finish, dim3((unsigned)gx), dim3(WIN_THREADS), 0, s, ctx->d_tab, ctx->T, ctx->ways, plan->uniq,
+                       plan->uniq_off, plan->kept, plan->kept_off, plan->cap_uniq, prot, plan->way, cl);
+    CDLRM_LAUNCH_CHECK();
+    return plan_assign_tail(ctx, plan, s);
 }
 
 // ---------------------------------------------------------------------------------------------

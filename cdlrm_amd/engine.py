@@ -196,7 +196,7 @@ class WindowPipeline:
                  world_size: int = 1, cap_uniq: Optional[int] = None, cap_win: Optional[int] = None,
                  victim_rows: Optional[int] = None, host_gather: bool = False, gather_threads: int = 16,
                  shard_fetch: Optional[bool] = None, process_group=None, write_back: bool = True,
-                 force_collectives: bool = False):
+                 force_collectives: bool = False, insert_policy: str = "reference"):
         """victim_rows: capacity (rows) of each of the two HBM buffers that hold the host rows of a window's
         non-cached indices (None: every unique index of a window, at most 8 GiB per buffer; 0: off -- every miss
         reads the host table over PCIe as the reference does).
@@ -213,7 +213,16 @@ class WindowPipeline:
         write_back=False: evicted rows are dropped instead of written to the host tables (repeatability tests that must
         leave the host tables as they found them; never in training).
         force_collectives: take the multi-rank code paths (sharded fetch + in-place all-gather, barrier) at world_size 1
-        too -- a 1-rank communicator executes every collective the N-rank run issues (tests/test_rccl_one_rank.py)."""
+        too -- a 1-rank communicator executes every collective the N-rank run issues (tests/test_rccl_one_rank.py).
+        insert_policy: which of a window's new indices get a slot.  "reference": every claimant picks a random unprotected
+        way, a contested slot goes to the claimant latest in index order (main_no_ddp.py:171-204).  "fill": the
+        collision-free, frequency-ranked policy (cdlrm_plan_assign_fill) -- a count pass over the window's lookups
+        runs between the probe and the assignment (a streamed window is iterated a second time for it), every set inserts
+        min(claimants, free ways) rows, and no random number is drawn: with parity_rng the fill policy takes nothing from
+        the torch CPU generator (and ignores q_source), with the device RNG the seed has no effect on the plan."""
+        if insert_policy not in ("reference", "fill"):
+            raise ValueError("insert_policy must be 'reference' or 'fill', not %r" % (insert_policy,))
+        self.insert_policy = insert_policy
         self.cg, self.host = cache_group, host_tables
         self.write_back = bool(write_back)
         self.ctx = cache_group.ctx
@@ -457,6 +466,19 @@ class WindowPipeline:
         else:
             plan.unique(window_idx, stream=side)
 
+    def _assign_fill(self, window_idx, side):
+        """The "fill" policy's half of a plan, between probe and fetch: count the window's lookups per unique index, then
+        the ranked way assignment."""
+        plan = self.plan
+        plan.count_reset(stream=side)
+        if callable(window_idx):
+            for chunk in window_idx():
+                plan.count_add(chunk, stream=side)
+                del chunk
+        else:
+            plan.count_add(window_idx, stream=side)
+        plan.assign_fill(stream=side)
+
     def plan_window(self, window_idx, q_source=None):
         """Launch the plan of one window on the side stream.  window_idx: [T, n] int64 on the device, or a callable
         that yields the window's chunks (called under the plan stream; see _unique)."""
@@ -470,7 +492,10 @@ class WindowPipeline:
             with S.on_stream(side):
                 self._unique(window_idx, side)
                 plan.probe(stream=side)
-                plan.assign(None, seed=self.seed * 1000003 + self.window_no, stream=side)
+                if self.insert_policy == "fill":
+                    self._assign_fill(window_idx, side)
+                else:
+                    plan.assign(None, seed=self.seed * 1000003 + self.window_no, stream=side)
                 if self.victims is not None:
                     plan.victims(self.victims[self._vnext], stream=side, list_only=True)
                 lists_ready = S.new_event(self.dev)
@@ -486,7 +511,9 @@ class WindowPipeline:
         with S.on_stream(side):
             self._unique(window_idx, side)
             plan.probe(stream=side)
-            if self.parity_rng:
+            if self.insert_policy == "fill":
+                self._assign_fill(window_idx, side)
+            elif self.parity_rng:
                 # Categorical.sample() draws from the torch CPU generator, table by table (main_no_ddp.py:184-185)
                 uo, ko, _ = plan.offsets(stream=side)
                 T, ways = self.ctx.T, self.ctx.ways

@@ -136,7 +136,20 @@ def ProcessArgs(argv=None):
     parser.add_argument("--device-rng", action="store_true", default=False,
                         help="way choice by counter-based Philox on the GPU (perf mode; not bit-comparable with the "
                              "reference's torch-CPU Categorical draw)")
-    return parser.parse_args(argv)
+    parser.add_argument("--insert-policy", type=str, default="reference",
+                        help="which of a window's new indices get a cache slot: `reference` = a random unprotected way each, "
+                             "the latest claimant wins a contested slot (main_no_ddp.py:171-204); `fill` = collision-free and "
+                             "ranked by the window's lookup counts (DESIGN.md; draws no random numbers)")
+    args = parser.parse_args(argv)
+    # (checked here and not by argparse `choices`: the run ends with the one ERROR: line every other refusal prints)
+    if args.insert_policy not in ("reference", "fill"):
+        sys.exit("ERROR: --insert-policy=%s is not supported (reference | fill)" % args.insert_policy)
+    if args.insert_policy == "fill" and args.data_generation in ("random", "synthetic"):
+        # the ragged front ends hand the plan a rectangle padded with a repeated index (engine.pad_window): counting the
+        # padding would inflate that index's priority
+        sys.exit("ERROR: --insert-policy=fill counts the window's lookups, and --data-generation=%s pads the plan's "
+                 "window with a repeated index (dataset | criteo-synthetic only)" % args.data_generation)
+    return args
 
 
 # --------------------------------------------------------------------------------------------------
@@ -380,6 +393,9 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
     multi_hot = getattr(train_ld, "multi_hot", False)
     aux_rows = args.mini_batch_size
     bag_windows = None
+    if multi_hot and getattr(args, "insert_policy", "reference") == "fill":
+        sys.exit("ERROR: --insert-policy=fill counts the window's lookups; a multi-hot loader's plan window is padded with "
+                 "a repeated index")
     if multi_hot:
         aux_rows = (args.mini_batch_size * max(1, args.num_indices_per_lookup) + 255) // 256 * 256
         if world > 1:       # a window's global lists go to HBM once; each step's rank slice is cut there
@@ -431,7 +447,11 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         eng.evict_victim = True
     pipe = WindowPipeline(cache_group, emb_tables, L * aux_rows * 2, parity_rng=not args.device_rng,
                           seed=args.numpy_rand_seed, average_on_writeback=args.average_on_writeback, rank=rank,
-                          world_size=world, host_gather=lookahead_plan)
+                          world_size=world, host_gather=lookahead_plan,
+                          insert_policy=getattr(args, "insert_policy", "reference"))
+    if pipe.insert_policy != "reference" and rank == 0:
+        print("Insert policy: %s (collision-free, ranked by the window's lookup counts; not the reference's random way choice)"
+              % pipe.insert_policy)
 
     # Print statistics (main_no_ddp.py:427-476) stay on the device between print boundaries: the head's finish launch adds
     # [#correct, loss * mbs] of every step to the engine's float64 accumulator (`eng.stat_acc`, on the side stream: no launch on

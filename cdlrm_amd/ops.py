@@ -349,6 +349,7 @@ class WindowPlan:
         self.win_off = z(T + 1, i64)
         self.stage = torch.empty((self.cap_win, ctx.D), dtype=torch.float32, device=dev)
         self.ev_tag = torch.full((self.cap_win,), -1, dtype=i64, device=dev)
+        self.count = self.claim = None         # the "fill" insert policy's buffers (_fill_buffers)
         self.c = Plan(self.bitmap.data_ptr(), self.uniq.data_ptr(), self.uniq_off.data_ptr(), self.cap_uniq,
                       self.prot.data_ptr(), self.hit.data_ptr(), self.kept.data_ptr(), self.kept_off.data_ptr(),
                       self.way.data_ptr(), self.flags.data_ptr(), self.winner.data_ptr(), self.win_claim.data_ptr(),
@@ -402,6 +403,32 @@ class WindowPlan:
             assert q.dtype == torch.float32 and q.is_contiguous()
         check(_lib.lib().cdlrm_plan_assign(self.ctx.handle, C.byref(self.c), ptr(q), int(seed) & (2 ** 64 - 1),
                                            stream_ptr(stream)))
+
+    # K3, "fill" insert policy (cdlrm_plan_assign_fill in the header): its two extra buffers exist from the first use on
+    def _fill_buffers(self):
+        if self.count is None:
+            dev = self.ctx.device
+            self.count = torch.zeros(max(self.cap_uniq, 1), dtype=torch.int32, device=dev)
+            self.claim = torch.zeros(max(int(self.ctx.total_sets), 1), dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()       # (zeroed on the current stream, used on the plan's)
+
+    def count_reset(self, stream=None):
+        self._fill_buffers()
+        check(_lib.lib().cdlrm_plan_count_reset(self.ctx.handle, C.byref(self.c), self.count.data_ptr(), stream_ptr(stream)))
+
+    def count_add(self, idx: torch.Tensor, stream=None):
+        """Add the lookups of one chunk [T, n] of the window to the per-unique counters (after unique / unique_finish)."""
+        _require_cuda(idx, "window indices")
+        assert idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == self.ctx.T and idx.stride(1) == 1
+        self._fill_buffers()
+        check(_lib.lib().cdlrm_plan_count_add(self.ctx.handle, C.byref(self.c), idx.data_ptr(), idx.shape[1], idx.stride(0),
+                                              self.count.data_ptr(), stream_ptr(stream)))
+
+    def assign_fill(self, use_counts: bool = True, stream=None):
+        """Instead of assign(): the collision-free, frequency-ranked policy (use_counts=False: index order)."""
+        self._fill_buffers()
+        check(_lib.lib().cdlrm_plan_assign_fill(self.ctx.handle, C.byref(self.c), self.count.data_ptr() if use_counts else None,
+                                                self.claim.data_ptr(), stream_ptr(stream)))
 
     # K5a
     def fetch(self, src_ptrs: Sequence[int], by_position: bool, stream=None):

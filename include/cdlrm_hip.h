@@ -287,6 +287,29 @@ int cdlrm_plan_offsets_sync(cdlrm_ctx* ctx, const cdlrm_plan* plan, int64_t* uni
 int cdlrm_plan_assign(cdlrm_ctx* ctx, const cdlrm_plan* plan, const float* q, uint64_t seed,
                       void* stream);
 
+/* K3, opt-in "fill" insert policy: a collision-free, frequency-ranked way assignment that REPLACES the reference's way
+ * choice and contested-slot rule (main_no_ddp.py:171-204).  A defined departure from the reference: no random number is
+ * drawn, so the result is a pure function of (tags, window) and can be checked bit for bit.
+ *   count     device int32 [plan->cap_uniq], caller-owned: count[u] = lookups of plan->uniq[u] in the window.
+ *             _count_reset zeroes it; _count_add (after cdlrm_window_unique / _finish, any number of chunks [T, n] with
+ *             row stride ld_idx) adds a chunk's lookups.  Out-of-range ids and ids that are not in the (possibly
+ *             capacity-cut) unique list count nowhere.  A counter stops growing somewhere at or above 65 535: the
+ *             priority is min(count, 65535).
+ *   _assign_fill (after cdlrm_plan_probe, instead of cdlrm_plan_assign): inside one set of one table the claimants are
+ *             ordered by priority descending, then index ascending; the claimant of rank r takes the set's r-th free way
+ *             (~prot & full), empty ways (tag -1) first, then occupied ones, each group by ascending way number.
+ *             Claimants of rank >= the number of free ways are not inserted (they become victims as cdlrm_plan_assign's
+ *             losers do).  min(claimants, free ways) rows are inserted in every set, no slot is claimed twice, and no valid
+ *             row is evicted while an empty way of its set stays empty.  count == NULL: all priorities equal (index order:
+ *             the CacheEmbeddings drop-in entry has unique lists and no window).
+ *   claim     device uint64 [sum_k P_k] scratch, caller-owned, zero on entry and on return.
+ * Fills way / win_* exactly as cdlrm_plan_assign does; fetch, victims, commit and writeback follow unchanged. */
+int cdlrm_plan_count_reset(cdlrm_ctx* ctx, const cdlrm_plan* plan, int32_t* count, void* stream);
+int cdlrm_plan_count_add(cdlrm_ctx* ctx, const cdlrm_plan* plan, const int64_t* idx, int64_t n,
+                         int64_t ld_idx, int32_t* count, void* stream);
+int cdlrm_plan_assign_fill(cdlrm_ctx* ctx, const cdlrm_plan* plan, const int32_t* count,
+                           uint64_t* claim, void* stream);
+
 /* K5a: fetch the winners' rows into plan->stage.
  *   src_rows [T] host array of device-visible base pointers; by_position = 0: row = src[k][index]
  *   (host master tables, Embedding_Table_Group.fetch_unique_idx_slices, model_no_ddp.py:80-87);
