@@ -182,6 +182,18 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __device__ __forceinline__ int64_t cdiv_dev(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
+// lanes that share one embedding row of D4 float4 (16 B per lane and trip), and the dispatch over the LPR template argument
+static inline int lanes_per_row(int D4) { int l = pow2ceil(D4); return l > 64 ? 64 : (l < 4 ? 4 : l); }
+
+#define DISPATCH_LPR(lpr, CALL)                 \
+    switch (lpr) {                              \
+        case 4: { CALL(4); break; }             \
+        case 8: { CALL(8); break; }             \
+        case 16: { CALL(16); break; }           \
+        case 32: { CALL(32); break; }           \
+        default: { CALL(64); break; }           \
+    }
+
 // ---- device helpers -----------------------------------------------------------------------------
 
 __device__ __forceinline__ int64_t mod_sets(int64_t idx, int64_t P) {

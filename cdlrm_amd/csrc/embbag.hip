@@ -333,17 +333,6 @@ __global__ void __launch_bounds__(256) k_embbag_fwd_bags(const TableDesc* __rest
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int lanes_per_row(int D4) { int l = pow2ceil(D4); return l > 64 ? 64 : (l < 4 ? 4 : l); }
-
-#define DISPATCH_LPR(lpr, CALL)                 \
-    switch (lpr) {                              \
-        case 4: { CALL(4); break; }             \
-        case 8: { CALL(8); break; }             \
-        case 16: { CALL(16); break; }           \
-        case 32: { CALL(32); break; }           \
-        default: { CALL(64); break; }           \
-    }
-
 extern "C" int cdlrm_embbag_probe(cdlrm_ctx* ctx, const int64_t* idx, int64_t n, int64_t ld_idx,
                                   int32_t* slots_out, int32_t* miss_pos, int32_t* miss_count, int32_t aux_phase,
                                   void* stream) {

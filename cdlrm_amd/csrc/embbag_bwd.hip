@@ -625,55 +625,58 @@ __global__ void __launch_bounds__(256) k_bwd_long(const TableDesc* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int lanes_per_row_b(int D4) { int l = pow2ceil(D4); return l > 64 ? 64 : (l < 4 ? 4 : l); }
+static uint64_t align256(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
+template <typename P> static P* at(const void* base, uint64_t off) { return (P*)((char*)base + off); }
 
-#define DISPATCH_LPR_B(lpr, CALL)               \
-    switch (lpr) {                              \
-        case 4: { CALL(4); break; }             \
-        case 8: { CALL(8); break; }             \
-        case 16: { CALL(16); break; }           \
-        case 32: { CALL(32); break; }           \
-        default: { CALL(64); break; }           \
-    }
-
+// ---- buffer layouts: byte offsets of every region and the byte count ------------------------------------------------------------
 // work layout: keys A [T*n] u64 | keys B [T*n] u64 | meta [T*n] i32 | partials [T*pstride*D] f32 |
 //              longlist [T*(n/SEG_CH+2)] i64 | long-run counter | runend [T*n] i32 (end of a long run, at its head) |
 //              once [T*n] u8 (by position in the batch: the lookup's slot occurs once in the batch)
-static int64_t bwd_pstride(int64_t n) { return 2 * (cdiv(n, SEG_CH) + 1); }
-static uint64_t align256(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
-
-struct BwdWork {
-    uint64_t *keysA, *keysB;
-    int32_t* meta;
-    float4* partials;
-    int64_t* longlist;
-    int32_t* longcount;
-    int32_t* runend;
-    uint8_t* once;          // [T*n] by position in the batch: this lookup's slot occurs once in the batch
+struct BwdLayout {
+    uint64_t keysA, keysB, meta, partials, longlist, longcount, runend, once, bytes;
     int64_t pstride;
 };
-
-static BwdWork carve(void* work, int T, int64_t n, int D) {
-    BwdWork w;
-    char* wp = (char*)work;
-    w.keysA = (uint64_t*)wp; wp += align256((uint64_t)T * n * 8);
-    w.keysB = (uint64_t*)wp; wp += align256((uint64_t)T * n * 8);
-    w.meta = (int32_t*)wp; wp += align256((uint64_t)T * n * 4);
-    w.pstride = bwd_pstride(n);
-    w.partials = (float4*)wp; wp += align256((uint64_t)T * w.pstride * D * 4);
-    w.longlist = (int64_t*)wp; wp += align256((uint64_t)T * (n / SEG_CH + 2) * 8);
-    w.longcount = (int32_t*)wp; wp += 256;
-    w.runend = (int32_t*)wp; wp += align256((uint64_t)T * n * 4);
-    w.once = (uint8_t*)wp;
-    return w;
+static BwdLayout bwd_layout(int32_t T, int64_t n, int32_t D) {
+    BwdLayout l;
+    uint64_t o = 0;
+    l.keysA = o; o += align256((uint64_t)T * n * 8);
+    l.keysB = o; o += align256((uint64_t)T * n * 8);
+    l.meta = o; o += align256((uint64_t)T * n * 4);
+    l.pstride = 2 * (cdiv(n, SEG_CH) + 1);
+    l.partials = o; o += align256((uint64_t)T * l.pstride * D * 4);
+    l.longlist = o; o += align256((uint64_t)T * (n / SEG_CH + 2) * 8);
+    l.longcount = o; o += 256;
+    l.runend = o; o += align256((uint64_t)T * n * 4);
+    l.once = o; o += align256((uint64_t)T * n);
+    l.bytes = o;
+    return l;
 }
 
-extern "C" uint64_t cdlrm_embbag_bwd_work_bytes(int32_t T, int64_t n, int32_t dim) {
-    return 2 * align256((uint64_t)T * n * 8) + align256((uint64_t)T * n * 4) +
-           align256((uint64_t)T * bwd_pstride(n) * dim * 4) + align256((uint64_t)T * (n / SEG_CH + 2) * 8) + 256 +
-           align256((uint64_t)T * n * 4) + align256((uint64_t)T * n);
+// ---- a window chunk's batches sorted at once (the look-ahead resolver's slot ids: cdlrm_window_resolve) ----------------------
+// sorted layout: keys A [T*nb*n] u64 | keys B | meta [T*nb*n] i32 | once [T*nb*n] u8 | 256 B; list t * nb + j = table t, batch j
+// (the 256 B: the counter words the sort kernel clears -- `longcount` of a buffer no apply reads)
+struct SortedLayout {
+    uint64_t keysA, keysB, meta, once, longcount, bytes;
+};
+static SortedLayout sorted_layout(int32_t T, int32_t nb, int64_t n) {
+    SortedLayout l;
+    const uint64_t e = (uint64_t)T * nb * n;
+    uint64_t o = 0;
+    l.keysA = o; o += align256(e * 8);
+    l.keysB = o; o += align256(e * 8);
+    l.meta = o; o += align256(e * 4);
+    l.once = o; o += align256(e);
+    l.longcount = o; o += 256;
+    l.bytes = o;
+    return l;
 }
 
+extern "C" uint64_t cdlrm_embbag_bwd_work_bytes(int32_t T, int64_t n, int32_t dim) { return bwd_layout(T, n, dim).bytes; }
+extern "C" uint64_t cdlrm_embbag_bwd_sorted_bytes(int32_t num_tables, int32_t nb, int64_t n) {
+    return sorted_layout(num_tables, nb, n).bytes;
+}
+
+// ---- the sort ------------------------------------------------------------------------------------------------------------------
 // Keys per sorting workgroup.  The in-LDS sort is bound by vector-instruction issue on ONE CU (measured: 9 / 16 / 33 / 83 us
 // for 1024 / 2048 / 4096 / 8192 keys per workgroup, tools/sort_scale.py), so mid-sized inputs are cut into 2048-key
 // chunks that sort on different CUs and meet in global rank-merge passes (k_merge_pass, ~8 us each at 26 x 8192 keys);
@@ -683,266 +686,278 @@ static int64_t sort_chunk(int64_t n) {
     return n <= 16384 ? 2048 : SORT_CHUNK;
 }
 
-// number of rank-merge passes decides which key buffer ends up sorted
-static bool sorted_in_B(int64_t n) {
-    int passes = 0;
-    for (int64_t run = sort_chunk(n); run < n; run *= 2) ++passes;
-    return passes & 1;
-}
-
 // the sort of `lists` lists of n slot ids each (a batch: one list per table; a window chunk: one per table and batch)
 // (Measured for the look-ahead slices, which have a whole step of slack, and not taken: ONE workgroup per list of 8192 keys -- 83
 //  us on 52 CUs, no merge passes, one launch instead of four -- 0.5401 against 0.5363 ms per c3 step; a tie at a batch of 2048.)
-// rec != nullptr: the route query (cdlrm_embbag_bwd_route) -- every decision below is taken, its outcome recorded, nothing launched
-static int bwd_sort(int lists, int64_t n, const int32_t* slots, int nb, int64_t ld_in, int64_t batch_len, int nbt, int j0,
-                    uint64_t* keysA, uint64_t* keysB, int32_t* meta, uint8_t* once, int32_t* longcount, hipStream_t s,
-                    cdlrm_emb_bwd_route* rec = nullptr) {
-    const int64_t chunk = sort_chunk(n);
-    const int64_t nchunks = cdiv(n, chunk);
-    const int npow2 = (int)chunk;
-    // keys per thread: the chunk spread over the 1024 threads
-    const int E = (int)(chunk / SORT_THREADS);
-    const dim3 sgrid((unsigned)nchunks, (unsigned)lists);
-    const size_t slds = (size_t)SORT_THREADS * E * 8;
-    const int wm = nchunks == 1 ? 1 : 0;
-    if (rec) {
-        rec->sort_chunk = (int32_t)chunk; rec->sort_e = E; rec->sort_chunks = (int32_t)nchunks; rec->seg_meta = !wm;
-    } else {
-        static bool attr_set = false;
-        if (!attr_set) {
-            CDLRM_HIP_CHECK(hipFuncSetAttribute((const void*)k_sort_chunks<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                SORT_CHUNK * 8));
-            attr_set = true;
+struct BwdSortPlan {
+    int chunk, E, nchunks;      // keys per sorting workgroup / per thread (the chunk spread over the 1024 threads), workgroups per list
+    int passes;                 // rank-merge passes: k_merge_pass launches, keys A -> B -> A ...
+    bool keys_in_b;             // ... so an odd number of them leaves the sorted keys in keys B
+    bool seg_meta;              // several chunks per list: k_seg_meta writes the run distances and once-only flags, not the sort kernel
+    dim3 sort_grid, merge_grid, meta_grid;
+    size_t lds;                 // k_sort_chunks' dynamic LDS
+};
+static BwdSortPlan bwd_sort_plan(int lists, int64_t n) {
+    BwdSortPlan p;
+    const int64_t chunk = sort_chunk(n), nchunks = cdiv(n, chunk);
+    p.chunk = (int)chunk;
+    p.E = (int)(chunk / SORT_THREADS);
+    p.nchunks = (int)nchunks;
+    p.passes = 0;
+    for (int64_t run = chunk; run < n; run *= 2) ++p.passes;
+    p.keys_in_b = p.passes & 1;
+    p.seg_meta = nchunks > 1;
+    int64_t gx = cdiv(n, 256);
+    if (gx > 4096) gx = 4096;
+    p.sort_grid = dim3((unsigned)nchunks, (unsigned)lists);
+    p.merge_grid = p.meta_grid = dim3((unsigned)gx, (unsigned)lists);
+    p.lds = (size_t)SORT_THREADS * p.E * 8;
+    return p;
+}
+
+// what the sort writes, in `work` or in a window chunk's `sorted`
+struct SortBufs {
+    uint64_t *keysA, *keysB;
+    int32_t* meta;
+    uint8_t* once;
+    int32_t* longcount;
+};
+template <typename Layout>
+static SortBufs sort_bufs(void* base, const Layout& l) {
+    return {at<uint64_t>(base, l.keysA), at<uint64_t>(base, l.keysB), at<int32_t>(base, l.meta), at<uint8_t>(base, l.once),
+            at<int32_t>(base, l.longcount)};
+}
+
+// byte offsets of the sorted keys / run distances / once-only flags of list j (table 0; a batch's own sort: j = 0): what
+// _sorted_views, the per-batch apply and the route query all read
+struct SortedOffs {
+    uint64_t keys, meta, once;
+};
+template <typename Layout>
+static SortedOffs sorted_offs(const Layout& l, const BwdSortPlan& p, int64_t n, int64_t j) {
+    return {(p.keys_in_b ? l.keysB : l.keysA) + (uint64_t)(j * n) * 8, l.meta + (uint64_t)(j * n) * 4, l.once + (uint64_t)(j * n)};
+}
+
+// slots: list t = batch t % nb of table t / nb, at slots[(t / nb) * ld_in + (t % nb) * batch_len ..]; its output list:
+// (t / nb) * nbt + j0 + t % nb (k_sort_chunks)
+static int bwd_sort_launch(const BwdSortPlan& p, const SortBufs& b, const int32_t* slots, int64_t n, int nb, int64_t ld_in,
+                           int64_t batch_len, int nbt, int j0, hipStream_t s) {
+    const int wm = p.seg_meta ? 0 : 1;
+#define SORT_CALL(E_)                                                                                                      \
+    hipLaunchKernelGGL(k_sort_chunks<E_>, p.sort_grid, dim3(SORT_THREADS), p.lds, s, slots, n, b.keysA, b.meta, p.chunk, wm, \
+                       b.longcount, b.once, nb, ld_in, batch_len, nbt, j0)
+    switch (p.E) {
+        case 1: SORT_CALL(1); break;
+        case 2: SORT_CALL(2); break;
+        case 4: SORT_CALL(4); break;
+        default: {
+            const int rc = cdlrm_grant_dynamic_lds<k_sort_chunks<8>>(p.lds);
+            if (rc) return rc;
+            SORT_CALL(8);
         }
-#define SORT_CALL(E_) hipLaunchKernelGGL(k_sort_chunks<E_>, sgrid, dim3(SORT_THREADS), slds, s, slots, n, keysA, meta, npow2, wm, longcount, once, nb, ld_in, batch_len, nbt, j0)
-        if (E == 1) SORT_CALL(1);
-        else if (E == 2) SORT_CALL(2);
-        else if (E == 4) SORT_CALL(4);
-        else SORT_CALL(8);
+    }
 #undef SORT_CALL
-    }
-    uint64_t* cur = keysA;
-    uint64_t* alt = keysB;
-    for (int64_t run = chunk; run < n; run *= 2) {
-        int64_t gx = cdiv(n, 256);
-        if (gx > 4096) gx = 4096;
-        if (rec) ++rec->merge_passes;
-        else hipLaunchKernelGGL(k_merge_pass, dim3((unsigned)gx, (unsigned)lists), dim3(256), 0, s, cur, alt, n, run, nb, nbt, j0);
-        uint64_t* tmp = cur; cur = alt; alt = tmp;
-    }
-    if (rec) {
-        rec->keys_in_b = cur == keysB;
-        return 0;
-    }
-    if (nchunks > 1) {
-        int64_t gx = cdiv(n, 256);
-        if (gx > 4096) gx = 4096;
-        hipLaunchKernelGGL(k_seg_meta, dim3((unsigned)gx, (unsigned)lists), dim3(256), 0, s, cur, n, meta, once, nb, nbt, j0);
-    }
+    int64_t run = p.chunk;
+    for (int i = 0; i < p.passes; ++i, run *= 2)
+        hipLaunchKernelGGL(k_merge_pass, p.merge_grid, dim3(256), 0, s, (i & 1) ? b.keysB : b.keysA, (i & 1) ? b.keysA : b.keysB, n,
+                           run, nb, nbt, j0);
+    if (p.seg_meta)
+        hipLaunchKernelGGL(k_seg_meta, p.meta_grid, dim3(256), 0, s, p.keys_in_b ? b.keysB : b.keysA, n, b.meta, b.once, nb, nbt, j0);
     CDLRM_LAUNCH_CHECK();
     return 0;
 }
 
-static int bwd_prepare(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, void* work, void* stream, cdlrm_emb_bwd_route* rec) {
-    CDLRM_REQUIRE(ctx && (rec || (slots && work)), "null argument");
+// ---- the apply -----------------------------------------------------------------------------------------------------------------
+struct BwdApplyPlan {
+    int kernel;                 // CDLRM_BWD_APPLY_*
+    int arange, lpr;            // one lookup per bag (no offsets); lanes per row
+    int64_t grid_x, grid_y;     // the apply kernel's grid
+    int64_t long_grid;          // k_bwd_long's
+};
+static BwdApplyPlan bwd_apply_plan(int T, int D, int64_t n, bool has_offsets, bool skip_once) {
+    BwdApplyPlan p;
+    p.arange = !has_offsets;
+    p.lpr = lanes_per_row(D / 4);
+    const int gpb = 256 / p.lpr;
+    // a lane group per block of SEG_CH sorted positions (k_bwd_blocks): the form for the runs of >= 2 lookups that
+    // cdlrm_embbag_bwd_apply_rest is left with (few heads per block).  With every run of one lookup in the list it is slower
+    // than a lane group per position (c3: 48.8 against 44.0 us alone, 144 against 105 us inside the step: a block of a large
+    // table holds 30 heads = 8 trips); cdlrm_debug_set(6, 64) selects it there too
+    const bool blocks = skip_once || (g_cdlrm_debug[6] & 64);
+    // The lean form: the runs of >= 2 lookups, one lookup per bag: ONE head at a time with four rows in flight (eight when the block
+    // holds one head) -- 4 x 4 / 16 rows in flight need 239 registers, and beside the weight-gradient GEMMs it is the kernel's
+    // footprint on a SIMD, not its own latency chain, that the step pays for (alone it finishes in 30 us either way).  c3,
+    // tools/ab_step.py, one box, 4 rounds: heads x rows / lone-head rows 4x4/16: 0.5393 ms, 2x4/8: 0.5357, 1x4/8: 0.5332,
+    // 2x4/4: 0.5362, 1x4/4: 0.5350.  cdlrm_debug_set(6, 128): the 4x4/16 form.
+    const bool lean = blocks && !has_offsets && skip_once && !(g_cdlrm_debug[6] & 128);
+    p.kernel = !blocks ? CDLRM_BWD_APPLY_CHUNKS : lean ? CDLRM_BWD_APPLY_BLOCKS_LEAN : CDLRM_BWD_APPLY_BLOCKS;
+    int64_t gx = blocks ? cdiv(cdiv(n, SEG_CH), gpb) : cdiv(n, gpb);
+    if (!blocks && gx > 65535) gx = 65535;
+    // at most 12 workgroups per CU (the position loop strides): the kernel runs on a side queue beside the weight-gradient and
+    // bottom-MLP GEMMs, and an unbounded grid (26 624 workgroups at c3, 213 k at c5) takes every free wave slot between their
+    // launches.  Same box, same process, 6 x 90 steps each (tools/ab_step.py --attr debug:1): uncapped / 12 / 8 / 6 / 4 per CU
+    // -> 0.5804 / 0.5754 / 0.5762 / 0.5977 / 0.6386 ms at c3 (10 .. 24: the same as 12), 3.762 / 3.722 ms at c5, nothing at a
+    // per-rank batch of 1024 (3328 workgroups to begin with).  Results do not depend on the grid (a position is owned by
+    // one lane group).  cdlrm_debug_set(1, n): n per CU, -1 uncapped
+    const int per_cu = g_cdlrm_debug[1] > 0 ? g_cdlrm_debug[1] : 12;
+    const int64_t cap = cdiv((int64_t)256 * per_cu, T);
+    if (g_cdlrm_debug[1] >= 0 && gx > cap) gx = cap;
+    p.grid_x = gx;
+    p.grid_y = T;
+    p.long_grid = cdiv((int64_t)T * (n / SEG_CH + 1), gpb);
+    if (p.long_grid > 1024) p.long_grid = 1024;
+    return p;
+}
+
+// what k_bwd_chunks, k_bwd_blocks and k_bwd_long share.  keys / meta: table 0's sorted list, table t's lies kstride elements further
+// (a batch's own sort: n; a window chunk's: nb * n); aux_add: the sorted slots are phase-0 aux slots, the batch trains on aux region
+// aux_add / aux (0 for a batch's own sort: k_take has added the phase); partials .. runend: the scratch of `work`
+struct BwdApplyArgs {
+    const TableDesc* tab;
+    int D4;
+    float4* weight;
+    const uint64_t* keys;
+    const int32_t* meta;
+    int64_t kstride;
+    const int64_t* offsets;
+    int64_t n, n_bags, ld_off;
+    const float* grad;
+    int64_t ld_bag, ld_table;
+    float lr;
+    float4* partials;
+    int64_t pstride;
+    int64_t* longlist;
+    int32_t *longcount, *runend;
+    uint8_t* touched;
+    int64_t aux_total;
+    int skip_once, ways, aux_add;
+};
+
+template <auto Kernel>
+static void launch_chunks(dim3 grid, const BwdApplyArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, a.n, a.n_bags, a.ld_off,
+                       a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist, a.longcount, a.touched, a.aux_total,
+                       a.runend, a.kstride, a.ways, a.aux_add);
+}
+template <auto Kernel>
+static void launch_blocks(dim3 grid, const BwdApplyArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, a.n, a.n_bags, a.ld_off,
+                       a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist, a.longcount, a.touched, a.aux_total,
+                       a.runend, a.skip_once, a.kstride, a.ways, a.aux_add);
+}
+template <int L>
+static void launch_long(dim3 grid, const BwdApplyArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_bwd_long<L>, grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.n, a.lr, a.partials, a.pstride,
+                       a.longlist, a.longcount, a.touched, a.aux_total, a.runend, a.kstride, a.ways, a.aux_add);
+}
+
+// sums + row updates (the plan's apply kernel), then the long runs
+template <int L>
+static void bwd_apply_launch_lpr(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+    if (p.kernel == CDLRM_BWD_APPLY_CHUNKS) {
+        if (p.arange) launch_chunks<k_bwd_chunks<L, true>>(grid, a, s);
+        else launch_chunks<k_bwd_chunks<L, false>>(grid, a, s);
+    } else if (p.kernel == CDLRM_BWD_APPLY_BLOCKS_LEAN) {
+        launch_blocks<k_bwd_blocks<L, true, 1, 8>>(grid, a, s);
+    } else {
+        if (p.arange) launch_blocks<k_bwd_blocks<L, true>>(grid, a, s);
+        else launch_blocks<k_bwd_blocks<L, false>>(grid, a, s);
+    }
+    launch_long<L>(dim3((unsigned)p.long_grid), a, s);
+}
+static int bwd_apply_launch(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
+#define APPLY_CALL(L) bwd_apply_launch_lpr<L>(p, a, s)
+    DISPATCH_LPR(p.lpr, APPLY_CALL)
+#undef APPLY_CALL
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- argument checks shared by the launching calls and the route query (pointer and alignment checks: the launching calls' own) --
+static int bwd_check_batch(int T, int64_t n) {
+    CDLRM_REQUIRE(n < ((int64_t)1 << 31) && T < (1 << 20), "n < 2^31");
+    return 0;
+}
+static int bwd_check_window(int T, int32_t nb, int64_t n, int32_t j0, int32_t count, int64_t batch_len, int64_t ld_w) {
+    CDLRM_REQUIRE(nb >= 1 && n >= 1 && n < ((int64_t)1 << 31) && (int64_t)T * nb < 65536, "1 <= nb, T * nb < 65536, n < 2^31");
+    CDLRM_REQUIRE(j0 >= 0 && count >= 1 && j0 + count <= nb, "0 <= j0, 1 <= count, j0 + count <= nb");
+    CDLRM_REQUIRE(batch_len >= n && ld_w >= (int64_t)(nb - 1) * batch_len + n, "a batch's n slot ids lie inside its batch_len columns");
+    return 0;
+}
+
+// ---- entry points: check, plan, launch -------------------------------------------------------------------------------------------
+extern "C" int cdlrm_embbag_bwd_prepare(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, void* work, void* stream) {
+    CDLRM_REQUIRE(ctx && slots && work, "null argument");
     CDLRM_REQUIRE(((uintptr_t)work & 255) == 0, "work must be 256-byte aligned");
-    CDLRM_REQUIRE(n < ((int64_t)1 << 31) && ctx->T < (1 << 20), "n < 2^31");
+    const int rc = bwd_check_batch(ctx->T, n);
+    if (rc) return rc;
     if (n == 0) return 0;
 #ifdef CDLRM_DEV
     if (g_cdlrm_debug[6] & 2) return 0;     // development build (tools/ab_step.py --attr debug:6): what the step costs WITHOUT the slot sort
 #endif
-    BwdWork w = carve(work, ctx->T, n, ctx->D);
-    return bwd_sort(ctx->T, n, slots, 1, n, 0, 1, 0, w.keysA, w.keysB, w.meta, w.once, w.longcount, (hipStream_t)stream, rec);
-}
-
-extern "C" int cdlrm_embbag_bwd_prepare(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, void* work, void* stream) {
-    return bwd_prepare(ctx, slots, n, work, stream, nullptr);
-}
-
-// ---- a window chunk's batches sorted at once (the look-ahead resolver's slot ids: cdlrm_window_resolve) ----------------------
-// sorted layout: keys A [T*nb*n] u64 | keys B | meta [T*nb*n] i32 | once [T*nb*n] u8 | 256 B; list t * nb + j = table t, batch j
-struct SortedWin {
-    uint64_t *keysA, *keysB;
-    int32_t* meta;
-    uint8_t* once;
-    int32_t* pad;
-};
-static SortedWin carve_sorted(void* sorted, int T, int nb, int64_t n) {
-    SortedWin w;
-    char* wp = (char*)sorted;
-    const uint64_t e = (uint64_t)T * nb * n;
-    w.keysA = (uint64_t*)wp; wp += align256(e * 8);
-    w.keysB = (uint64_t*)wp; wp += align256(e * 8);
-    w.meta = (int32_t*)wp; wp += align256(e * 4);
-    w.once = (uint8_t*)wp; wp += align256(e);
-    w.pad = (int32_t*)wp;
-    return w;
-}
-
-extern "C" uint64_t cdlrm_embbag_bwd_sorted_bytes(int32_t num_tables, int32_t nb, int64_t n) {
-    const uint64_t e = (uint64_t)num_tables * nb * n;
-    return 2 * align256(e * 8) + align256(e * 4) + align256(e) + 256;
-}
-
-static int bwd_prepare_window(cdlrm_ctx* ctx, const int32_t* wslots, int64_t ld_w, int64_t batch_len, int32_t nb, int64_t n,
-                              int32_t j0, int32_t count, void* sorted, void* stream, cdlrm_emb_bwd_route* rec) {
-    CDLRM_REQUIRE(ctx && (rec || (wslots && sorted)), "null argument");
-    CDLRM_REQUIRE(((uintptr_t)sorted & 255) == 0, "sorted must be 256-byte aligned");
-    CDLRM_REQUIRE(nb >= 1 && n >= 1 && n < ((int64_t)1 << 31) && (int64_t)ctx->T * nb < 65536, "1 <= nb, T * nb < 65536, n < 2^31");
-    CDLRM_REQUIRE(j0 >= 0 && count >= 1 && j0 + count <= nb, "0 <= j0, 1 <= count, j0 + count <= nb");
-    CDLRM_REQUIRE(batch_len >= n && ld_w >= (int64_t)(nb - 1) * batch_len + n, "a batch's n slot ids lie inside its batch_len columns");
-    SortedWin w = carve_sorted(sorted, ctx->T, nb, n);
-    return bwd_sort(ctx->T * count, n, wslots + (int64_t)j0 * batch_len, count, ld_w, batch_len, nb, j0, w.keysA, w.keysB, w.meta,
-                    w.once, w.pad, (hipStream_t)stream, rec);
+    return bwd_sort_launch(bwd_sort_plan(ctx->T, n), sort_bufs(work, bwd_layout(ctx->T, n, ctx->D)), slots, n, 1, n, 0, 1, 0,
+                           (hipStream_t)stream);
 }
 
 extern "C" int cdlrm_embbag_bwd_prepare_window(cdlrm_ctx* ctx, const int32_t* wslots, int64_t ld_w, int64_t batch_len,
                                                int32_t nb, int64_t n, int32_t j0, int32_t count, void* sorted, void* stream) {
-    return bwd_prepare_window(ctx, wslots, ld_w, batch_len, nb, n, j0, count, sorted, stream, nullptr);
+    CDLRM_REQUIRE(ctx && wslots && sorted, "null argument");
+    CDLRM_REQUIRE(((uintptr_t)sorted & 255) == 0, "sorted must be 256-byte aligned");
+    const int rc = bwd_check_window(ctx->T, nb, n, j0, count, batch_len, ld_w);
+    if (rc) return rc;
+    return bwd_sort_launch(bwd_sort_plan(ctx->T * count, n), sort_bufs(sorted, sorted_layout(ctx->T, nb, n)),
+                           wslots + (int64_t)j0 * batch_len, n, count, ld_w, batch_len, nb, j0, (hipStream_t)stream);
 }
 
 extern "C" int cdlrm_embbag_bwd_sorted_views(cdlrm_ctx* ctx, void* sorted, int32_t nb, int64_t n, int32_t j,
                                              const uint64_t** keys, const int32_t** meta, const uint8_t** once) {
     CDLRM_REQUIRE(ctx && sorted && keys && meta && once && nb >= 1 && j >= 0 && j < nb && n >= 1, "bad argument");
-    SortedWin w = carve_sorted(sorted, ctx->T, nb, n);
-    *keys = (sorted_in_B(n) ? w.keysB : w.keysA) + (int64_t)j * n;
-    *meta = w.meta + (int64_t)j * n;
-    *once = w.once + (int64_t)j * n;
+    const SortedOffs v = sorted_offs(sorted_layout(ctx->T, nb, n), bwd_sort_plan(ctx->T, n), n, j);
+    *keys = at<const uint64_t>(sorted, v.keys);
+    *meta = at<const int32_t>(sorted, v.meta);
+    *once = at<const uint8_t>(sorted, v.once);
     return 0;
 }
 
 extern "C" int cdlrm_embbag_bwd_once_flags(cdlrm_ctx* ctx, void* work, int64_t n, const uint8_t** once) {
     CDLRM_REQUIRE(ctx && work && once && n >= 1, "bad argument");
-    *once = carve(work, ctx->T, n, ctx->D).once;
+    *once = at<const uint8_t>(work, bwd_layout(ctx->T, n, ctx->D).once);
     return 0;
 }
 
-// sums + row updates over sorted lists: `cur` / `meta` are table 0's list, table t's lies kstride elements further (a batch's own
-// sort: n; a window chunk's: nb * n); aux_phase: the sorted slots are phase-0 aux slots (0 for a batch's own sort: k_take has
-// added the phase); scratch: partials, long-run list and run ends of `work`.  rec != nullptr: the route query -- the kernels and
-// grids are chosen and recorded, nothing is launched
-static int cdlrm_embbag_bwd_apply_core(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off,
-                     const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work, const uint64_t* cur,
-                     const int32_t* meta, int64_t kstride, int aux_phase, uint8_t* touched, void* stream, int skip_once,
-                     cdlrm_emb_bwd_route* rec = nullptr) {
-    CDLRM_REQUIRE(ctx && (rec || (grad && work)), "null argument");
-    CDLRM_REQUIRE(rec || ctx->weight, "cdlrm_ctx_bind_cache first");
+// sums + row updates over sorted lists: keys / meta / kstride / aux_phase as BwdApplyArgs has them, or keys == nullptr: the sort
+// that cdlrm_embbag_bwd_prepare left in `work` itself; the scratch is `work`'s either way
+static int bwd_apply(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off, const float* grad,
+                     int64_t ld_bag, int64_t ld_table, float lr, void* work, const uint64_t* keys, const int32_t* meta,
+                     int64_t kstride, int aux_phase, uint8_t* touched, void* stream, int skip_once) {
+    CDLRM_REQUIRE(ctx && grad && work, "null argument");
+    CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
     CDLRM_REQUIRE(((uintptr_t)grad & 15) == 0 && ld_bag % 4 == 0 && ld_table % 4 == 0 && ((uintptr_t)work & 255) == 0,
                   "aligned grad rows / work");
     CDLRM_REQUIRE(offsets != nullptr || n_bags == n, "Criteo layout needs n_bags == n");
-    hipStream_t s = (hipStream_t)stream;
     if (n == 0) return 0;
 #ifdef CDLRM_DEV
     if (g_cdlrm_debug[6] & 1) return 0;     // development build: ... without the embedding update (an upper bound on what moving it buys)
 #endif
-    const int T = ctx->T, D4 = ctx->D / 4;
-    const int lpr = lanes_per_row_b(D4);
-    const int gpb = 256 / lpr;
-    BwdWork w = carve(work, T, n, ctx->D);
-    if (!cur) {
-        cur = sorted_in_B(n) ? w.keysB : w.keysA;
-        meta = w.meta;
+    const BwdLayout l = bwd_layout(ctx->T, n, ctx->D);
+    if (!keys) {
+        const SortedOffs v = sorted_offs(l, bwd_sort_plan(ctx->T, n), n, 0);
+        keys = at<const uint64_t>(work, v.keys);
+        meta = at<const int32_t>(work, v.meta);
         kstride = n;
     }
-    const int ways = ctx->ways, aux_add = aux_phase * ctx->aux;
-    float4* wt = reinterpret_cast<float4*>(ctx->weight);
-    const int64_t aux_total = (int64_t)ctx->aux * ctx->aux_phases;
-    if (rec) {
-        rec->lpr = lpr;
-        rec->arange = offsets == nullptr;
-        rec->apply_keys_off = (int64_t)((const char*)cur - (const char*)work);
-    }
-    if (skip_once || (g_cdlrm_debug[6] & 64)) {
-        // a lane group per block of SEG_CH sorted positions (k_bwd_blocks): the form for the runs of >= 2 lookups that
-        // cdlrm_embbag_bwd_apply_rest is left with (few heads per block).  With every run of one lookup in the list it is slower
-        // than a lane group per position (c3: 48.8 against 44.0 us alone, 144 against 105 us inside the step: a block of a large
-        // table holds 30 heads = 8 trips); cdlrm_debug_set(6, 64) selects it there too
-        int64_t bx = cdiv(cdiv(n, SEG_CH), gpb);
-        const int per_cu = g_cdlrm_debug[1] > 0 ? g_cdlrm_debug[1] : 12;
-        const int64_t cap = cdiv((int64_t)256 * per_cu, T);
-        if (g_cdlrm_debug[1] >= 0 && bx > cap) bx = cap;
-        dim3 bgrid((unsigned)bx, (unsigned)T);
-        // (the lean form, below: the runs of >= 2 lookups, one lookup per bag)
-        const bool lean = !offsets && skip_once && !(g_cdlrm_debug[6] & 128);
-        if (rec) {
-            rec->apply = lean ? CDLRM_BWD_APPLY_BLOCKS_LEAN : CDLRM_BWD_APPLY_BLOCKS;
-            rec->apply_grid_x = bx; rec->apply_grid_y = T;
-        } else {
-#define BLK_LEAN(L, HU_, RA_)                                                                                      \
-    hipLaunchKernelGGL((k_bwd_blocks<L, true, HU_, RA_>), bgrid, dim3(256), 0, s, ctx->d_tab, D4, wt, cur, meta, offsets, n, \
-                       n_bags, ld_off, grad, ld_bag, ld_table, lr, w.partials, w.pstride, w.longlist, w.longcount,      \
-                       touched, aux_total, w.runend, skip_once, kstride, ways, aux_add)
-#define BLK_CALL_LEAN(L) BLK_LEAN(L, 1, 8)
-        // The runs of >= 2 lookups, one lookup per bag: ONE head at a time with four rows in flight (eight when the block holds one
-        // head) -- 4 x 4 / 16 rows in flight need 239 registers, and beside the weight-gradient GEMMs it is the kernel's footprint on
-        // a SIMD, not its own latency chain, that the step pays for (alone it finishes in 30 us either way).  c3, tools/ab_step.py,
-        // one box, 4 rounds: heads x rows / lone-head rows 4x4/16: 0.5393 ms, 2x4/8: 0.5357, 1x4/8: 0.5332, 2x4/4: 0.5362,
-        // 1x4/4: 0.5350.  cdlrm_debug_set(6, 128): the 4x4/16 form.
-        if (lean) {
-            DISPATCH_LPR_B(lpr, BLK_CALL_LEAN)
-        } else {
-#define BLK_CALL(L)                                                                                                \
-    if (offsets)                                                                                                   \
-        hipLaunchKernelGGL((k_bwd_blocks<L, false>), bgrid, dim3(256), 0, s, ctx->d_tab, D4, wt, cur, meta, offsets, n,   \
-                           n_bags, ld_off, grad, ld_bag, ld_table, lr, w.partials, w.pstride, w.longlist, w.longcount,  \
-                           touched, aux_total, w.runend, skip_once, kstride, ways, aux_add);                       \
-    else                                                                                                           \
-        hipLaunchKernelGGL((k_bwd_blocks<L, true>), bgrid, dim3(256), 0, s, ctx->d_tab, D4, wt, cur, meta, offsets, n,    \
-                           n_bags, ld_off, grad, ld_bag, ld_table, lr, w.partials, w.pstride, w.longlist, w.longcount,  \
-                           touched, aux_total, w.runend, skip_once, kstride, ways, aux_add)
-        DISPATCH_LPR_B(lpr, BLK_CALL)
-#undef BLK_CALL
-        }
-#undef BLK_CALL_LEAN
-#undef BLK_LEAN
-        }
-    } else {
-        int64_t gx = cdiv(n, gpb);
-        if (gx > 65535) gx = 65535;
-        // at most 12 workgroups per CU (the position loop strides): the kernel runs on a side queue beside the weight-gradient and
-        // bottom-MLP GEMMs, and an unbounded grid (26 624 workgroups at c3, 213 k at c5) takes every free wave slot between their
-        // launches.  Same box, same process, 6 x 90 steps each (tools/ab_step.py --attr debug:1): uncapped / 12 / 8 / 6 / 4 per CU
-        // -> 0.5804 / 0.5754 / 0.5762 / 0.5977 / 0.6386 ms at c3 (10 .. 24: the same as 12), 3.762 / 3.722 ms at c5, nothing at a
-        // per-rank batch of 1024 (3328 workgroups to begin with).  Results do not depend on the grid (a position is owned by
-        // one lane group).  cdlrm_debug_set(1, n): n per CU, -1 uncapped
-        const int per_cu = g_cdlrm_debug[1] > 0 ? g_cdlrm_debug[1] : 12;
-        const int64_t cap = cdiv((int64_t)256 * per_cu, T);
-        if (g_cdlrm_debug[1] >= 0 && gx > cap) gx = cap;
-        dim3 grid((unsigned)gx, (unsigned)T);
-        if (rec) {
-            rec->apply = CDLRM_BWD_APPLY_CHUNKS;
-            rec->apply_grid_x = gx; rec->apply_grid_y = T;
-        } else {
-#define BWD_CALL(L)                                                                                                \
-    if (offsets)                                                                                                   \
-        hipLaunchKernelGGL((k_bwd_chunks<L, false>), grid, dim3(256), 0, s, ctx->d_tab, D4, wt, cur, meta, offsets, n,    \
-                           n_bags, ld_off, grad, ld_bag, ld_table, lr, w.partials, w.pstride, w.longlist, w.longcount,  \
-                           touched, aux_total, w.runend, kstride, ways, aux_add);                                  \
-    else                                                                                                           \
-        hipLaunchKernelGGL((k_bwd_chunks<L, true>), grid, dim3(256), 0, s, ctx->d_tab, D4, wt, cur, meta, offsets, n,     \
-                           n_bags, ld_off, grad, ld_bag, ld_table, lr, w.partials, w.pstride, w.longlist, w.longcount,  \
-                           touched, aux_total, w.runend, kstride, ways, aux_add)
-        DISPATCH_LPR_B(lpr, BWD_CALL)
-#undef BWD_CALL
-        }
-    }
-    int64_t lx = cdiv((int64_t)T * (n / SEG_CH + 1), gpb);
-    if (lx > 1024) lx = 1024;
-    if (rec) {
-        rec->long_grid = lx;
-        return 0;
-    }
-#define LONG_CALL(L) hipLaunchKernelGGL(k_bwd_long<L>, dim3((unsigned)lx), dim3(256), 0, s, ctx->d_tab, D4, wt, cur, n, lr, w.partials, w.pstride, w.longlist, w.longcount, touched, aux_total, w.runend, kstride, ways, aux_add)
-    DISPATCH_LPR_B(lpr, LONG_CALL)
-#undef LONG_CALL
-    CDLRM_LAUNCH_CHECK();
-    return 0;
+    const BwdApplyArgs a = {ctx->d_tab, ctx->D / 4, reinterpret_cast<float4*>(ctx->weight), keys, meta, kstride, offsets, n, n_bags,
+                            ld_off, grad, ld_bag, ld_table, lr, at<float4>(work, l.partials), l.pstride,
+                            at<int64_t>(work, l.longlist), at<int32_t>(work, l.longcount), at<int32_t>(work, l.runend), touched,
+                            (int64_t)ctx->aux * ctx->aux_phases, skip_once, ctx->ways, aux_phase * ctx->aux};
+    return bwd_apply_launch(bwd_apply_plan(ctx->T, ctx->D, n, offsets != nullptr, skip_once != 0), a, (hipStream_t)stream);
 }
 
 extern "C" int cdlrm_embbag_bwd_apply(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off,
                                       const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work,
                                       uint8_t* touched, void* stream) {
-    return cdlrm_embbag_bwd_apply_core(ctx, offsets, n, n_bags, ld_off, grad, ld_bag, ld_table, lr, work, nullptr, nullptr, 0, 0, touched, stream, 0);
+    return bwd_apply(ctx, offsets, n, n_bags, ld_off, grad, ld_bag, ld_table, lr, work, nullptr, nullptr, 0, 0, touched, stream, 0);
 }
 
 // The apply behind cdlrm_gather_interact_bwd_sgd: slots the batch reads once were updated there (their gradient rows were
@@ -950,25 +965,19 @@ extern "C" int cdlrm_embbag_bwd_apply(cdlrm_ctx* ctx, const int64_t* offsets, in
 extern "C" int cdlrm_embbag_bwd_apply_rest(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off,
                                            const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work,
                                            uint8_t* touched, void* stream) {
-    return cdlrm_embbag_bwd_apply_core(ctx, offsets, n, n_bags, ld_off, grad, ld_bag, ld_table, lr, work, nullptr, nullptr, 0, 0, touched, stream, 1);
+    return bwd_apply(ctx, offsets, n, n_bags, ld_off, grad, ld_bag, ld_table, lr, work, nullptr, nullptr, 0, 0, touched, stream, 1);
 }
 
 // The apply over a window chunk's sorted lists (cdlrm_embbag_bwd_prepare_window; keys / meta: batch j's views, tstride = nb * n):
 // no per-batch sort.  `work` only lends its scratch (partial sums, long-run list); its long-run counter must be zero -- every
 // apply leaves it zero, a fresh buffer is zero-filled by the caller.  One lookup per bag (the Criteo layout).
-static int bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work,
-                            const uint64_t* keys, const int32_t* meta, int64_t tstride, int32_t aux_phase, int32_t rest,
-                            uint8_t* touched, void* stream, cdlrm_emb_bwd_route* rec) {
-    CDLRM_REQUIRE(ctx && keys && meta && tstride >= n, "null argument / tstride");
-    CDLRM_REQUIRE(aux_phase >= 0 && aux_phase < (ctx->aux_phases > 0 ? ctx->aux_phases : 1), "aux_phase outside the geometry's aux_phases");
-    return cdlrm_embbag_bwd_apply_core(ctx, nullptr, n, n, 0, grad, ld_bag, ld_table, lr, work, keys, meta, tstride, aux_phase, touched, stream,
-                     rest ? 1 : 0, rec);
-}
-
 extern "C" int cdlrm_embbag_bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table,
                                              float lr, void* work, const uint64_t* keys, const int32_t* meta, int64_t tstride,
                                              int32_t aux_phase, int32_t rest, uint8_t* touched, void* stream) {
-    return bwd_apply_sorted(ctx, n, grad, ld_bag, ld_table, lr, work, keys, meta, tstride, aux_phase, rest, touched, stream, nullptr);
+    CDLRM_REQUIRE(ctx && keys && meta && tstride >= n, "null argument / tstride");
+    CDLRM_REQUIRE(aux_phase >= 0 && aux_phase < (ctx->aux_phases > 0 ? ctx->aux_phases : 1), "aux_phase outside the geometry's aux_phases");
+    return bwd_apply(ctx, nullptr, n, n, 0, grad, ld_bag, ld_table, lr, work, keys, meta, tstride, aux_phase, touched, stream,
+                     rest ? 1 : 0);
 }
 
 extern "C" int cdlrm_embbag_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, const int64_t* offsets, int64_t n,
@@ -979,41 +988,28 @@ extern "C" int cdlrm_embbag_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, const 
     return cdlrm_embbag_bwd_apply(ctx, offsets, n, n_bags, ld_off, grad, ld_bag, ld_table, lr, work, touched, stream);
 }
 
-// The route query: the calls above on a geometry of num_tables x dim, with `rec` set.  No context, device or buffer exists: `work` /
-// `sorted` are a made-up, aligned base address the buffers are carved from (the offsets below are relative to it), no pointer is read.
+// The route query: the checks, plans and layouts of the calls above on a geometry of num_tables x dim, copied out.  No context,
+// device or buffer exists; the offsets are relative to the start of `work` (window entries: of `sorted`).
 extern "C" int cdlrm_embbag_bwd_route(int32_t num_tables, int32_t dim, int64_t n, int32_t has_offsets, int32_t entry, int32_t nb,
                                       int32_t j0, int32_t count, cdlrm_emb_bwd_route* out) {
     CDLRM_REQUIRE(out && num_tables >= 1 && dim >= 4 && dim % 4 == 0, "bad argument");
     CDLRM_REQUIRE(entry >= CDLRM_BWD_ENTRY_APPLY && entry <= CDLRM_BWD_ENTRY_SORTED_REST, "entry: CDLRM_BWD_ENTRY_*");
-    CDLRM_REQUIRE(entry < CDLRM_BWD_ENTRY_SORTED || !has_offsets, "the window-sorted path has one lookup per bag");
+    const bool window = entry >= CDLRM_BWD_ENTRY_SORTED;
+    CDLRM_REQUIRE(!window || !has_offsets, "the window-sorted path has one lookup per bag");     // (_apply_sorted takes no offsets)
     memset(out, 0, sizeof(*out));
-    cdlrm_ctx c;
-    c.T = num_tables; c.D = dim;
-    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);
-    const int64_t* offsets = has_offsets ? reinterpret_cast<const int64_t*>(base) : nullptr;
-    if (entry < CDLRM_BWD_ENTRY_SORTED) {
-        int rc = bwd_prepare(&c, nullptr, n, base, nullptr, out);
-        if (rc || n == 0) return rc;
-        const BwdWork w = carve(base, c.T, n, c.D);
-        out->keys_off = (int64_t)((const char*)(out->keys_in_b ? w.keysB : w.keysA) - base);
-        out->meta_off = (int64_t)((const char*)w.meta - base);
-        out->once_off = (int64_t)((const char*)w.once - base);
-        return cdlrm_embbag_bwd_apply_core(&c, offsets, n, n, 0, nullptr, 4 * dim, dim, 0.f, base, nullptr, nullptr, 0, 0, nullptr,
-                                           nullptr, entry == CDLRM_BWD_ENTRY_REST, out);
-    }
-    int rc = bwd_prepare_window(&c, nullptr, (int64_t)nb * n, n, nb, n, j0, count, base, nullptr, out);
-    if (rc) return rc;
-    const uint64_t* keys;
-    const int32_t* meta;
-    const uint8_t* once;
-    rc = cdlrm_embbag_bwd_sorted_views(&c, base, nb, n, j0, &keys, &meta, &once);
-    if (rc) return rc;
-    const SortedWin w = carve_sorted(base, c.T, nb, n);
-    CDLRM_REQUIRE((out->keys_in_b ? w.keysB : w.keysA) + (int64_t)j0 * n == keys, "the sort and the views disagree on A / B");
-    out->keys_off = (int64_t)((const char*)keys - base);
-    out->meta_off = (int64_t)((const char*)meta - base);
-    out->once_off = (int64_t)((const char*)once - base);
-    // (apply_sorted's `work` is a buffer of its own: its scratch is carved from the same made-up base)
-    return bwd_apply_sorted(&c, n, nullptr, 4 * dim, dim, 0.f, base, keys, meta, (int64_t)nb * n, 0,
-                            entry == CDLRM_BWD_ENTRY_SORTED_REST, nullptr, nullptr, out);
+    const int rc = window ? bwd_check_window(num_tables, nb, n, j0, count, n, (int64_t)nb * n) : bwd_check_batch(num_tables, n);
+    if (rc || n == 0) return rc;
+    const BwdSortPlan sp = bwd_sort_plan(window ? num_tables * count : num_tables, n);
+    const BwdApplyPlan ap = bwd_apply_plan(num_tables, dim, n, has_offsets != 0,
+                                           entry == CDLRM_BWD_ENTRY_REST || entry == CDLRM_BWD_ENTRY_SORTED_REST);
+    // (the window entries: batch j0's lists, as _sorted_views gives them and _apply_sorted is handed them)
+    const SortedOffs v = window ? sorted_offs(sorted_layout(num_tables, nb, n), sp, n, j0)
+                                : sorted_offs(bwd_layout(num_tables, n, dim), sp, n, 0);
+    out->sort_chunk = sp.chunk; out->sort_e = sp.E; out->sort_chunks = sp.nchunks; out->merge_passes = sp.passes;
+    out->seg_meta = sp.seg_meta; out->keys_in_b = sp.keys_in_b;
+    out->apply = ap.kernel; out->arange = ap.arange; out->lpr = ap.lpr;
+    out->apply_grid_x = ap.grid_x; out->apply_grid_y = ap.grid_y; out->long_grid = ap.long_grid;
+    out->keys_off = (int64_t)v.keys; out->meta_off = (int64_t)v.meta; out->once_off = (int64_t)v.once;
+    out->apply_keys_off = (int64_t)v.keys;
+    return 0;
 }

@@ -690,8 +690,6 @@ __global__ void __launch_bounds__(256) k_writeback(int T, int D4, int lpr, const
     }
 }
 
-static int lanes_per_row_w(int D4) { int l = pow2ceil(D4); return l > 64 ? 64 : (l < 4 ? 4 : l); }
-
 // Rows of the pinned HOST tables -> HBM, for the plan's bulk fetches (winners, victims).  PCIe-bound: the link needs
 // ~1 MB of reads in flight, not thousands of waves -- a wide grid of waves parked on PCIe round trips takes the wave
 // slots of every CU and starves the training kernels running beside the plan (measured: GEMMs 2x slower for the
@@ -759,7 +757,7 @@ extern "C" int cdlrm_plan_fetch(cdlrm_ctx* ctx, const cdlrm_plan* plan, const fl
     hipStream_t s = (hipStream_t)stream;
     for (int k = 0; k < ctx->T; ++k) CDLRM_REQUIRE(src_rows[k] && ((uintptr_t)src_rows[k] & 15) == 0, "aligned sources");
     CDLRM_HIP_CHECK(hipMemcpyAsync(ctx->d_ptr_fetch, src_rows, sizeof(float*) * ctx->T, hipMemcpyHostToDevice, s));
-    const int D4 = ctx->D / 4, lpr = lanes_per_row_w(D4);
+    const int D4 = ctx->D / 4, lpr = lanes_per_row(D4);
     int64_t gx = cdiv(plan->cap_win * lpr, 256);
     if (gx > WIN_BLOCKS) gx = WIN_BLOCKS;
     if (gx < 1) gx = 1;
@@ -783,7 +781,7 @@ extern "C" int cdlrm_plan_commit(cdlrm_ctx* ctx, const cdlrm_plan* plan, void* s
     CDLRM_REQUIRE(ctx->tags && ctx->weight, "cdlrm_ctx_bind_cache first");
     CDLRM_REQUIRE(plan->stage && plan->ev_tag && plan->win_off, "plan buffers missing");
     hipStream_t s = (hipStream_t)stream;
-    const int D4 = ctx->D / 4, lpr = lanes_per_row_w(D4);
+    const int D4 = ctx->D / 4, lpr = lanes_per_row(D4);
     int64_t gx = cdiv(plan->cap_win * lpr, 256);
     if (gx > WIN_BLOCKS) gx = WIN_BLOCKS;
     if (gx < 1) gx = 1;
@@ -800,7 +798,7 @@ extern "C" int cdlrm_plan_writeback(cdlrm_ctx* ctx, const cdlrm_plan* plan, floa
     hipStream_t s = (hipStream_t)stream;
     for (int k = 0; k < ctx->T; ++k) CDLRM_REQUIRE(dst_rows[k] && ((uintptr_t)dst_rows[k] & 15) == 0, "aligned tables");
     CDLRM_HIP_CHECK(hipMemcpyAsync(ctx->d_ptr_wb, dst_rows, sizeof(float*) * ctx->T, hipMemcpyHostToDevice, s));
-    const int D4 = ctx->D / 4, lpr = lanes_per_row_w(D4);
+    const int D4 = ctx->D / 4, lpr = lanes_per_row(D4);
     int64_t gx = cdiv(plan->cap_win * lpr, 256);
     if (gx > WIN_BLOCKS) gx = WIN_BLOCKS;
     if (gx < 1) gx = 1;

@@ -301,7 +301,7 @@ BWD_APPLY_KERNELS = {0: None, 1: "chunks", 2: "blocks", 3: "blocks_lean"}      #
 
 def embbag_bwd_route(T: int, D: int, n: int, offsets: bool, entry: str, nb: int = 1, j0: int = 0,
                      count: Optional[int] = None) -> dict:
-    """The kernels one embedding backward launches, from the same decision code, without launching them: entry "apply"
+    """The kernels one embedding backward launches, from the same plan, without launching them: entry "apply"
     (embbag_bwd_prepare + embbag_bwd_apply), "rest" (+ embbag_bwd_apply_rest), "sorted" / "sorted_rest"
     (embbag_bwd_prepare_window(nb, j0, count) + embbag_bwd_apply_sorted(rest = 0 / 1)) on T tables of D columns with n lookups
     each, offsets given or not.  Sort (sort_chunk, sort_e, sort_chunks, merge_passes, seg_meta, keys_in_b), apply kernel

@@ -221,7 +221,7 @@ typedef struct cdlrm_emb_bwd_route {
 } cdlrm_emb_bwd_route;
 /* The plan of one backward without the launches: entry CDLRM_BWD_ENTRY_*, on num_tables tables of dim columns, n lookups per
  * table, offsets given or not (has_offsets; the window entries take none), nb / j0 / count as _prepare_window takes them (the
- * other entries ignore them).  The answer comes out of the same decision code the launching calls run; no device is touched and
+ * other entries ignore them).  The answer comes out of the same plan the launching calls launch from; no device is touched and
  * no pointer is read (the offsets are relative to the buffer's start). */
 int cdlrm_embbag_bwd_route(int32_t num_tables, int32_t dim, int64_t n, int32_t has_offsets, int32_t entry, int32_t nb,
                            int32_t j0, int32_t count, cdlrm_emb_bwd_route* out);

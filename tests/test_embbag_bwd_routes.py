@@ -1,13 +1,14 @@
 """Every route of the embedding backward + sparse SGD (K8, csrc/embbag_bwd.hip) against a plain float64 reference.
 
-The sort (bwd_sort: k_sort_chunks at 1024 / 2048 / 8192 keys per workgroup, k_merge_pass, k_seg_meta) and the apply
-(cdlrm_embbag_bwd_apply_core: k_bwd_chunks, the full and the lean k_bwd_blocks, k_bwd_long) have many branches, and K8 writes the
-cache rows that persist from step to step: a lookup summed twice or dropped at a chunk edge is never overwritten.  One table of
+The sort (bwd_sort_plan / bwd_sort_launch: k_sort_chunks at 1024 / 2048 / 8192 keys per workgroup, k_merge_pass, k_seg_meta) and
+the apply (bwd_apply_plan / bwd_apply_launch: k_bwd_chunks, the full and the lean k_bwd_blocks, k_bwd_long) have many branches, and
+K8 writes the cache rows that persist from step to step: a lookup summed twice or dropped at a chunk edge is never overwritten.  One table of
 cases below, each a deterministic RUN-LENGTH SCRIPT (how many lookups each slot gets, in sorted order; positions scattered by a
 fixed permutation) with the route it is meant to reach, serves three checks:
 
-  * CPU: ops.embbag_bwd_route (the same decision code as the launching calls, nothing launched) gives the declared route, and the
-    table reaches every kernel instantiation the dispatch can launch;
+  * CPU: ops.embbag_bwd_route (the plans and layouts the launching calls read, nothing launched) gives the declared route, the
+    table reaches every kernel instantiation the dispatch can launch, and the offsets it reports lie inside the buffer in the
+    layout's order;
   * CPU: one TrainEngine step per configuration (c1 ... c5 embedding widths, per-rank batches 1024 ... 65536, tests/fake_ops.py)
     records the step's embbag_bwd_prepare / embbag_bwd_apply arguments; every sort and apply route they resolve to, with its
     layout and grad pitches, is in the table;
@@ -550,9 +551,28 @@ def test_declared_route(ops, case):
     r = query(ops, case)
     assert route_str(r) == case.route, "%s: routed to %r, the table declares %r" % (case.id, route_str(r), case.route)
     if not case.window:
-        # per batch, the apply finds the keys on its own (sorted_in_B) while the sort leaves them where its merge passes end:
-        # the two must agree.  (The window entries hand the apply the views' keys: equal by construction, nothing to check.)
+        # per batch, the apply finds the keys on its own (bwd_sort_plan's keys_in_b) while the sort leaves them where its merge
+        # passes end: the two must agree.  (The window entries hand the apply the views' keys: equal by construction, nothing to check.)
         assert r["apply_keys_off"] == r["keys_off"], "the apply reads other keys than the sort leaves"
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c.id)
+def test_offsets_lie_inside_the_buffer(ops, case):
+    """The sorted keys, run distances and once-only flags the query reports: regions that start 256-byte aligned, distinct, in the
+    order of the layout comment (keys A | keys B | meta | ... | once), the last one ending inside the byte count the library
+    reports.  (Batch j0 of a window chunk lies j0 * n elements inside its region: it is the region's start that is aligned.)"""
+    from cdlrm_amd import _lib
+    c, r = case, query(ops, case)
+    j = c.j0 if c.window else 0
+    offs = (r["keys_off"], r["meta_off"], r["once_off"])
+    for off, size in zip(offs, (8, 4, 1)):
+        assert off >= 0 and (off - j * c.n * size) % 256 == 0, (offs, size)
+    assert offs[0] < offs[1] < offs[2], offs
+    assert offs[0] + c.n * 8 <= offs[1] and offs[1] + c.n * 4 <= offs[2], offs
+    if c.window:
+        assert offs[2] + c.T * c.nb * c.n - c.j0 * c.n <= _lib.raw().cdlrm_embbag_bwd_sorted_bytes(c.T, c.nb, c.n)
+    else:
+        assert offs[2] + c.T * c.n <= _lib.raw().cdlrm_embbag_bwd_work_bytes(c.T, c.n, c.D)
 
 
 def test_table_reaches_every_instantiation(ops):
@@ -861,6 +881,19 @@ def _run(ops, d, j=None):
                                 _u8(sbuf, m - base + t * c.nb * c.n * 4, c.n, np.int32),
                                 _u8(sbuf, o - base + t * c.nb * c.n, c.n, np.uint8))
         return r, views, work
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", [c for c in CASES if c.window], ids=lambda c: c.id)
+def test_sorted_views_are_the_query_offsets(ops, case):
+    """embbag_bwd_sorted_views needs a context, a context a device; nothing is launched."""
+    c = case
+    ctx = ops.CacheCtx([10 ** 6] * c.T, Geo(c).P, c.D, WAYS, Geo(c).aux, torch.device(DEV), aux_phases=2)
+    sbuf = ops.embbag_bwd_sorted(ctx, c.nb, c.n, DEV)
+    r = query(ops, c)
+    k, m, o = ops.embbag_bwd_sorted_views(ctx, sbuf, c.nb, c.n, c.j0)
+    base = sbuf.data_ptr()
+    assert (k - base, m - base, o - base) == (r["keys_off"], r["meta_off"], r["once_off"])
 
 
 @pytest.mark.gpu
