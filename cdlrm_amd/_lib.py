@@ -91,6 +91,11 @@ PROTOTYPES = {
     "cdlrm_embbag_bwd_route": (C.c_int, [c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(EmbBwdRoute)]),
     "cdlrm_qr_embbag_fwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
     "cdlrm_qr_embbag_bwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp]),
+    "cdlrm_qr_split": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, c_i64, vp, c_i64, vp]),
+    "cdlrm_qr_cached_fwd": (C.c_int, [vp, vp, vp, c_i64, vp, vp, c_i32, c_i32, c_i64, vp, c_i64, c_i64, vp]),
+    "cdlrm_qr_cached_bwd_work_bytes": (c_u64, [c_i32, c_i64, c_i32, c_i32]),
+    "cdlrm_qr_cached_bwd": (C.c_int, [vp, vp, vp, c_i64, vp, vp, c_i32, c_i32, c_i64, vp, c_i64, c_i64, vp, vp]),
+    "cdlrm_qr_cached_bwd_finish": (C.c_int, [vp, vp, c_i32, c_i64, vp, c_f32, vp, vp, vp]),
     "cdlrm_bag_fwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, c_i64, c_i32, vp, vp, vp]),
     "cdlrm_bag_bwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, c_i64, c_i32, vp, vp]),
     "cdlrm_window_unique": (C.c_int, [vp, C.POINTER(Plan), vp, c_i64, c_i64, vp]),

@@ -102,6 +102,7 @@ static const std::vector<TapeEntry>& tape_registry() {
         TAPE_FN(cdlrm_embbag_bwd_prepare), TAPE_FN(cdlrm_embbag_bwd_apply), TAPE_FN(cdlrm_embbag_bwd_apply_rest),
         TAPE_FN(cdlrm_gather_interact_bwd_sgd), TAPE_FN(cdlrm_embbag_bwd_prepare_window), TAPE_FN(cdlrm_embbag_bwd_apply_sorted),
         TAPE_FN(cdlrm_window_resolve),
+        TAPE_FN(cdlrm_qr_split), TAPE_FN(cdlrm_qr_cached_fwd), TAPE_FN(cdlrm_qr_cached_bwd), TAPE_FN(cdlrm_qr_cached_bwd_finish),
         TAPE_FN(cdlrm_mark_rows), TAPE_FN(cdlrm_interact_fwd), TAPE_FN(cdlrm_interact_bwd), TAPE_FN(cdlrm_gather_interact_fwd),
         TAPE_FN(cdlrm_gather_interact_bwd), TAPE_FN(cdlrm_linear_fwd),
         TAPE_FN(cdlrm_linear_bwd), TAPE_FN(cdlrm_mlp_wgrad), TAPE_FN(cdlrm_mlp_wgrad_sgd), TAPE_FN(cdlrm_mlp_wgrad_ex),

@@ -878,6 +878,13 @@ class TrainEngine:
         self._flatten_params()
         self.ctx.bind_host_tables(host_tables.device_pointers())
         self._bufs = {}
+        # quotient-remainder mode: the cache holds quotient rows keyed by q -- everything above the gather runs
+        # unchanged on the q stream --, the remainder tables Wr [T, c, D] live whole in HBM and are composed with the rows by
+        # cdlrm_qr_cached_fwd / _bwd.  None: plain tables, no Wr, no r columns, the launch sequence of a plain run.
+        self.qr = getattr(cache_group, "qr", None)
+        self.Wr = self._r = None
+        if self.qr is not None:
+            self._init_qr(host_tables)
         self.iter = 0
         self.comm = S.new_stream(self.dev) if self.multi else None
         self.side = S.new_stream(self.dev)
@@ -1005,6 +1012,63 @@ class TrainEngine:
         self._fwd_marked = False
         self._pending_resolve = None
 
+    # ---- quotient-remainder mode -------------------------------------------------------------------------------------
+    def _init_qr(self, host_tables):
+        q = self.qr
+        c = int(q["c"])
+        assert host_tables.qr_layout() == q, "the cache group's quotient-remainder layout is not the host group's"
+        if q["operation"] not in ops.QR_OPS:
+            raise ValueError("--qr-operation=%s changes the row width: the cached path composes mult / add" % q["operation"])
+        if not 2 <= c <= 16:
+            raise ValueError("--qr-collisions=%d: the cached path takes 2 .. 16" % c)
+        if not ops.qr_cached_shape_ok(self.D, c):
+            raise ValueError("embedding dim %d x %d collisions: the backward's remainder accumulators exceed 64 KB of LDS"
+                             % (self.D, c))
+        self.qr_op = ops.QR_OPS[q["operation"]]
+        self.qr_coll = torch.tensor(q["collisions"], dtype=torch.int32, device=self.dev)
+        self.qr_rows = torch.tensor(q["rows"], dtype=torch.int64, device=self.dev)
+        self.Wr = torch.zeros(self.T, c, self.D, dtype=torch.float32, device=self.dev)
+        self.load_wr(host_tables)
+
+    def load_wr(self, host_tables):
+        """Wr <- the host group's weight_r (construction, --load-model)."""
+        for k, E in enumerate(host_tables.emb_l):
+            if self.qr["collisions"][k]:
+                self.Wr[k].copy_(E.weight_r.data)
+
+    def flush_wr(self, host_tables):
+        """The host group's weight_r <- Wr: call it wherever the cache is flushed (beside Embedding_Table_Cache_Group.flush_to_host;
+        Run does at --save-model).  Not collective: it waits for this rank's last embedding update only."""
+        if self._emb_done is not None:
+            S.current_stream(self.dev).wait_event(self._emb_done)
+        wr = self.Wr.cpu()
+        for k, E in enumerate(host_tables.emb_l):
+            if self.qr["collisions"][k]:
+                E.weight_r.data.copy_(wr[k])
+
+    def qr_split(self, idx, q=None, r=None, stream=None):
+        """idx [T, n] -> (q, r) (ops.qr_split; q=idx splits a window rectangle in place): what plan_window / WindowResolver /
+        step() / evaluate() take in this mode."""
+        return ops.qr_split(self.ctx, idx, self.qr_coll, self.qr_rows, q, r, stream=stream)
+
+    def _qr_work(self, n):
+        key = ("qr", n)
+        if key not in self._bufs:
+            self._bufs[key] = ops.qr_cached_bwd_work(self.ctx, n, int(self.qr["c"]))
+        return self._bufs[key]
+
+    def _merge_wr(self):
+        """Wr over the ranks with --table-agg-op, as oracle.table_aggregate merges a table every rank touched all rows of."""
+        if self.agg_op == "mean":
+            ops.scale_div(self.Wr.view(-1), float(self.world))
+            dist.all_reduce(self.Wr, op=dist.ReduceOp.SUM, group=self.pg)
+        elif self.agg_op == "sum":
+            dist.all_reduce(self.Wr, op=dist.ReduceOp.SUM, group=self.pg)
+        elif self.agg_op == "max":
+            dist.all_reduce(self.Wr, op=dist.ReduceOp.MAX, group=self.pg)
+        else:
+            raise ValueError(self.agg_op)
+
     # all Linear weights in one flat buffer (one all-reduce, main_no_ddp.py:234-247), biases behind them
     def _flatten_params(self):
         """All Linear weights in one flat buffer, biases behind them.  The first top-MLP layer reads the interaction
@@ -1078,7 +1142,8 @@ class TrainEngine:
 
     def _fused_gather(self, lS_o) -> bool:
         """This step's gather rides in the interaction kernels (fuse_gather)."""
-        return bool(self.fuse_gather and lS_o is None and not self.cat and S.is_hip(self.dev)
+        # (quotient-remainder mode composes the rows with Wr in the stand-alone gather: the fused kernels are a later step)
+        return bool(self.fuse_gather and lS_o is None and not self.cat and S.is_hip(self.dev) and self.qr is None
                     and ops.gather_interact_supported(self.ctx))
 
     def _side_gather(self, B: int) -> bool:
@@ -1294,7 +1359,7 @@ class TrainEngine:
 
     def step(self, X: torch.Tensor, lS_i: torch.Tensor, T: torch.Tensor, lS_o: Optional[torch.Tensor] = None,
              j: Optional[int] = None, gather_events: Optional[list] = None, next_idx: Optional[torch.Tensor] = None,
-             res=None, next_res=None, loss_sync: bool = True):
+             res=None, next_res=None, loss_sync: bool = True, r: Optional[torch.Tensor] = None):
         """One training iteration on this rank's slice (next_idx: the NEXT batch's indices, if it belongs to the same
         window: its tag probe and aux fill are then issued behind this step's embedding backward).  X [B, m_den] fp32, lS_i [T, n] int64, T [B, 1] fp32, all
         on the device; lS_o None = Criteo layout (one lookup per bag), else int64 [T, B] offsets -- or [T, B + 1] from
@@ -1306,8 +1371,17 @@ class TrainEngine:
         sums, and the one-workgroup launch that adds them up (and accumulates `stat_acc`) runs on the side stream in front of
         the embedding backward instead of holding the training queue for ~6 us; the returned buffer and `stat_acc` are then
         valid after finish() (bench.py, Run), not right behind step() on the current stream.
+        r: quotient-remainder mode only -- lS_i (and next_idx, the window, the resolver's chunks) are QUOTIENTS and r uint8
+        [T, n] holds this batch's remainders (qr_split; columns of a window's r rectangle are fine).
         Returns the device loss buffer (element 0 = the loss, 1 = correct predictions, 2 = loss * batch)."""
         B, n = X.shape[0], lS_i.shape[1]
+        if self.qr is not None:
+            if lS_o is not None:
+                raise ValueError("quotient-remainder mode takes one lookup per bag (the operator pools before it combines)")
+            assert r is not None and r.dtype == torch.uint8 and tuple(r.shape) == (self.T, n) and r.stride(1) == 1
+        else:
+            assert r is None, "r columns belong to quotient-remainder mode"
+        self._r = r
         if self.evict_victim:
             assert not self.multi, "--evict-victim-cache is defined for one rank (every rank would write its own misses' rows)"
             next_idx = next_res = None          # the next batch's take follows this batch's write-back
@@ -1474,6 +1548,9 @@ class TrainEngine:
 
         def gather(st):
             if fused:       # the rows are the interaction kernel's operand loads: nothing to launch here
+                return
+            if self.qr is not None:
+                ops.qr_cached_fwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, feat[:, 1:, :], feat.stride(0), D, stream=st)
                 return
             if self._gslot is not None:         # bench.py: the roofline kernel's own start / stop timestamps
                 ops.time_next_gather(ctx, self._gslot[0], self._gslot[1])
@@ -1652,6 +1729,13 @@ class TrainEngine:
             # the head's partial sums -> loss buffer + running statistics, off the training queue.  The next head kernel
             # overwrites the partials only behind the next gather, which is ordered behind this stream's embedding update
             ops.head_finish(self._head_scratch, B, buf["loss"], stream=side, acc=self.stat_acc)
+        if self.qr is not None:
+            # dL/dE -> the quotient rows' gradient, in place, and the remainder tables' sums and SGD step: both factors are read
+            # here, in front of the row update below (same stream) and of Wr's own
+            qw = self._qr_work(n)
+            ops.qr_cached_bwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, dfeat[:, 1:, :], dfeat.stride(0), D, qw,
+                              stream=side)
+            ops.qr_cached_bwd_finish(ctx, self.qr_coll, n, qw, self.lr_embeds, self.Wr, stream=side)
         if sv is not None:
             ops.embbag_bwd_apply_sorted(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work, sv[0], sv[1], sv[3],
                                         self._phase, once, cg.touched if self.multi else None, stream=side)
@@ -1708,7 +1792,8 @@ class TrainEngine:
         return split is not None and sgd_in_wgrad
 
     # ----------------------------------------------------------------------------------------------
-    def evaluate(self, X: torch.Tensor, lS_i: torch.Tensor, lS_o: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def evaluate(self, X: torch.Tensor, lS_i: torch.Tensor, lS_o: Optional[torch.Tensor] = None,
+                 r: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Forward only (the test loop of main_no_ddp.py:479-494: `cache_group(lS_o, lS_i, emb_tables, rank)` then
         `dlrm(X, lookups)` under no_grad): tag probe with the aux-miss path (test indices outside the cache read their
         host rows -- into the aux region of the batch trained last, whose rows are dead), cached gather, bottom MLP,
@@ -1743,7 +1828,13 @@ class TrainEngine:
         if self._fused_gather(lS_o):
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         else:
-            ops.embbag_fwd(ctx, slots, lS_o, feat[:, 1:, :], feat.stride(0), D, n_bags=(B if lS_o is None else lS_o.shape[1]))
+            if self.qr is not None:         # (lS_i: quotients, r: the batch's remainders -- qr_split)
+                if lS_o is not None:
+                    raise ValueError("quotient-remainder mode takes one lookup per bag")
+                assert r is not None and r.dtype == torch.uint8 and tuple(r.shape) == (self.T, n) and r.stride(1) == 1
+                ops.qr_cached_fwd(ctx, slots, r, self.Wr, self.qr_coll, self.qr_op, feat[:, 1:, :], feat.stride(0), D)
+            else:
+                ops.embbag_fwd(ctx, slots, lS_o, feat[:, 1:, :], feat.stride(0), D, n_bags=(B if lS_o is None else lS_o.shape[1]))
             if not self.cat:
                 ops.interact_fwd(feat, self.itself, R)
         cur = R
@@ -1799,7 +1890,8 @@ class TrainEngine:
                self.matmul_precision,
                None if self._cur_sorted is None else self._cur_sorted[3], self._next_sorted is not None,
                self._res[0].stride(0) if (self._res is not None and not hit) else 0,
-               self._next_res[0].stride(0) if self._next_res is not None else 0)
+               self._next_res[0].stride(0) if self._next_res is not None else 0,
+               self._r.stride(0) if self._r is not None else 0)
         tape = self._tapes.get(key)
         if tape is None:
             calls = []
@@ -1875,6 +1967,8 @@ class TrainEngine:
             p["skeys"], p["smeta"], p["sonce"] = self._cur_sorted[:3]
         if self._gslot is not None:
             p["g0"], p["g1"] = self._gslot[0].handle, self._gslot[1].handle
+        if self._r is not None:         # quotient-remainder mode: the batch's remainder columns
+            p["r"] = self._r.data_ptr()
         if self._mark_this:             # the placed resolve's chunk: index columns, ring slot, the slot's event
             pr = self._pending_resolve
             p["rcols"], p["rws"] = pr["cols"].data_ptr(), pr["ws"].data_ptr()
@@ -2011,6 +2105,8 @@ class TrainEngine:
             return
         main = S.current_stream(self.dev)
         self._pump_finish()         # (a merge period shorter than the look-ahead: the previous merge's rows land first)
+        if self.Wr is not None:
+            self._merge_wr()        # one small all-reduce: the remainder tables, whole
         dist.all_reduce(touched, op=dist.ReduceOp.MAX, group=self.pg)
         self._agg_alloc()
         U = self._agg_list(touched)                   # consumes (clears) the flags

@@ -149,6 +149,24 @@ def ProcessArgs(argv=None):
         # padding would inflate that index's priority
         sys.exit("ERROR: --insert-policy=fill counts the window's lookups, and --data-generation=%s pads the plan's "
                  "window with a repeated index (dataset | criteo-synthetic only)" % args.data_generation)
+    if args.qr_flag:
+        # quotient-remainder tables train through the cache: one lookup per bag, rows of one width
+        if args.qr_operation not in ("mult", "add"):
+            sys.exit("ERROR: --qr-operation=%s is not supported on the cached path (mult | add; concat changes the row width)"
+                     % args.qr_operation)
+        if not 2 <= args.qr_collisions <= 16:
+            sys.exit("ERROR: --qr-collisions=%d is not supported on the cached path (2 .. 16)" % args.qr_collisions)
+        if not ops.qr_cached_shape_ok(args.arch_sparse_feature_size, args.qr_collisions):
+            sys.exit("ERROR: --arch-sparse-feature-size=%d with --qr-collisions=%d is not supported on the cached path (the "
+                     "backward's remainder accumulators exceed 64 KB of LDS)" % (args.arch_sparse_feature_size, args.qr_collisions))
+        if args.world_size > 1:
+            # the quotient tables would have to go through hostmem.make_host_tables' decision (one shared mapping, or replicas
+            # checked against the job's memory limit) and --load-model through every rank's copy: neither exists yet
+            sys.exit("ERROR: --qr-flag runs at --world-size=1 in this CLI (its host tables are not shared between ranks yet; "
+                     "TrainEngine itself merges Wr over ranks)")
+        if args.data_generation in ("random", "synthetic"):
+            sys.exit("ERROR: --qr-flag takes one lookup per bag, and --data-generation=%s yields ragged multi-hot bags (the "
+                     "operator pools before it combines; dataset | criteo-synthetic only)" % args.data_generation)
     return args
 
 
@@ -396,12 +414,17 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
     if multi_hot and getattr(args, "insert_policy", "reference") == "fill":
         sys.exit("ERROR: --insert-policy=fill counts the window's lookups; a multi-hot loader's plan window is padded with "
                  "a repeated index")
+    qr_layout = emb_tables.qr_layout()      # None: plain tables
+    if multi_hot and qr_layout is not None:
+        sys.exit("ERROR: --qr-flag takes one lookup per bag (the operator pools before it combines); this loader yields "
+                 "multi-hot bags")
     if multi_hot:
         aux_rows = (args.mini_batch_size * max(1, args.num_indices_per_lookup) + 255) // 256 * 256
         if world > 1:       # a window's global lists go to HBM once; each step's rank slice is cut there
             bag_windows = BagWindows(len(ln_emb), dev, local_batch_size, world_size=world, rank=rank)
     cache_group = Embedding_Table_Cache_Group(m_spa, ln_emb, max_cache_size=args.cache_size,
-                                              aux_table_size=aux_rows, num_ways=args.num_ways).to(dev)
+                                              aux_table_size=aux_rows, num_ways=args.num_ways,
+                                              qr_layout=qr_layout).to(dev)
     dlrm = DLRM_Net(ln_bot, ln_top, arch_interaction_op=args.arch_interaction_op,
                     arch_interaction_itself=args.arch_interaction_itself, sync_dense_params=args.sync_dense_params,
                     sigmoid_bot=-1, sigmoid_top=ln_top.size - 2, loss_threshold=args.loss_threshold).to(dev)
@@ -416,8 +439,12 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         ld = torch.load(args.load_model, map_location="cpu")
         dlrm.load_state_dict({k: v.to(dev) for k, v in ld["dlrm"].items()})
         if rank == 0 or world == 1:
-            for E, w in zip(emb_tables.emb_l, ld["emb"]):
-                E.weight.data.copy_(w)
+            for k, (E, w) in enumerate(zip(emb_tables.emb_l, ld["emb"])):
+                if hasattr(E, "weight_q"):      # a quotient-remainder table: its quotient rows, and its remainder rows
+                    E.weight_q.data.copy_(w)
+                    E.weight_r.data.copy_(ld["emb_r"][k])
+                else:
+                    E.weight.data.copy_(w)
         if world > 1:
             dist.barrier()
     eng = TrainEngine(cache_group, dlrm, emb_tables, lr=args.learning_rate, lr_embeds=args.lr_embeds, world_size=world,
@@ -474,6 +501,8 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         next_win_idx = cur_win_idx = None
         next_bags = cur_bags = None     # world > 1 multi-hot: the window's engine.BagWindow, kept beside its plan indices
         resolver, wj = None, 0
+        cur_rem = next_rem = None   # quotient-remainder mode: the r columns of the windows whose (split) indices are above
+        win_col = 0                 # ... and the current batch's first column in them
         carried_idx = None          # device indices of the batch whose probe the previous step already issued
         j = 0
         torch.cuda.synchronize(dev)
@@ -510,6 +539,19 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             return torch.cat([torch.as_tensor(b[2]) if not isinstance(b[2], (list, tuple)) else
                               torch.stack([torch.as_tensor(s).reshape(-1) for s in b[2]]) for b in win], dim=1).to(dev), None
 
+        def plan_indices(win):
+            """window_indices -- and, in quotient-remainder mode, the rectangle split where it is built: the plan, the resolver
+            and the steps see q (batches are columns of it), their r columns lie in a parallel uint8 rectangle"""
+            idx, bags = window_indices(win)
+            if eng.qr is None:
+                return idx, bags, None
+            b0 = win[0]
+            if getattr(b0, "window_rect", None) is idx:
+                b0.wait_upload(torch.cuda.current_stream(dev))
+            # a rectangle the loader owns (and reuses) is left as it is; one built for this window is split in place
+            q, rem = eng.qr_split(idx, q=None if getattr(b0, "window_rect", None) is idx else idx)
+            return q, bags, rem
+
         while True:
             if not window:
                 # look-ahead: the next L batches; their insert plan is made now, or was made while the last window trained
@@ -519,10 +561,11 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                     break
                 torch.cuda.synchronize(dev)     # the steps issued so far belong to the iteration time, not to the refill
                 start = timer()
-                cur_win_idx, cur_bags = (next_win_idx, next_bags) if planned else (None, None)
-                next_win_idx = next_bags = None
+                cur_win_idx, cur_bags, cur_rem = (next_win_idx, next_bags, next_rem) if planned else (None, None, None)
+                next_win_idx = next_bags = next_rem = None
+                win_col = 0
                 if not planned:
-                    cur_win_idx, cur_bags = window_indices(window)
+                    cur_win_idx, cur_bags, cur_rem = plan_indices(window)
                     pipe.plan_window(cur_win_idx)
                 if world > 1:
                     eng.sync_touched_to_rank0()
@@ -532,7 +575,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                 resolver, wj = None, 0
                 if not multi_hot:
                     if cur_win_idx is None:
-                        cur_win_idx, _ = window_indices(window)
+                        cur_win_idx, _, cur_rem = plan_indices(window)
                     if cur_win_idx.shape[1] == len(window) * args.mini_batch_size:      # whole batches only
                         # (chunks of 32 batches at world > 1: the row merge orders its rows by the batches resolved ahead)
                         resolver = WindowResolver(eng, cur_win_idx, args.mini_batch_size, chunk=16 if world == 1 else 32)
@@ -541,10 +584,10 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                 if lookahead_plan:
                     next_window = read_window() or None
                     if next_window is not None:     # evictions are in the host tables: the next plan may read them
-                        next_win_idx, next_bags = window_indices(next_window)
+                        next_win_idx, next_bags, next_rem = plan_indices(next_window)
                         pipe.plan_window(next_win_idx)
             X, lS_o, lS_i, T = window.pop(0)
-            Or = nxt = None
+            Or = nxt = Rr = None
             sl = slice(rank * local_batch_size, (rank + 1) * local_batch_size)
 
             def rank_indices(li):       # this rank's slice of a batch's indices, on the device
@@ -563,6 +606,16 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             elif multi_hot:
                 Or, Ir = square_bags([lS_o[k] for k in range(len(ln_emb))], lS_i, dev)
                 Xr, Tr = X.to(dev), T.to(dev)
+            elif eng.qr is not None:
+                # quotient-remainder mode: the batch is columns [win_col, win_col + its width) of the window's q / r rectangles
+                Xr, Tr = X[sl, :].to(dev), T[sl, :].to(dev)
+                lo = win_col + rank * local_batch_size
+                Ir, Rr = cur_win_idx[:, lo:lo + Xr.shape[0]], cur_rem[:, lo:lo + Xr.shape[0]]
+                win_col += X.shape[0]
+                if window:
+                    lo = win_col + rank * local_batch_size
+                    nxt = cur_win_idx[:, lo:lo + min(local_batch_size, max(0, window[0][0].shape[0] - rank * local_batch_size))]
+                    nxt = nxt if nxt.shape[1] else None
             else:
                 Xr = X[sl, :].to(dev)
                 Ir = carried_idx if carried_idx is not None else rank_indices(lS_i)
@@ -575,7 +628,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             lossbuf = eng.step(Xr, Ir, Tr, lS_o=Or, j=j, next_idx=nxt,
                                res=rs.batch(wj) if rs is not None else None,
                                next_res=rs.batch(wj + 1) if (rs is not None and nxt is not None) else None,
-                               loss_sync=False)
+                               loss_sync=False, r=Rr)
             if rs is not None:
                 rs.ensure(wj + rs.CH + 2)
             wj += 1
@@ -622,7 +675,11 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                     else:
                         lS_it = torch.as_tensor(lS_it) if not isinstance(lS_it, (list, tuple)) else torch.stack(
                             [torch.as_tensor(s).reshape(-1) for s in lS_it])
-                        Zt = eng.evaluate(Xt.to(dev), lS_it.contiguous().to(dev))
+                        if eng.qr is not None:
+                            qt, rt = eng.qr_split(lS_it.contiguous().to(dev))
+                            Zt = eng.evaluate(Xt.to(dev), qt, r=rt)
+                        else:
+                            Zt = eng.evaluate(Xt.to(dev), lS_it.contiguous().to(dev))
                     S_ = Zt.cpu().numpy()
                     Tn = Tt.cpu().numpy()
                     total_test_acc += np.sum((np.round(S_, 0) == Tn).astype(np.uint32))
@@ -656,8 +713,12 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         # cache row to its host row (rank 0's replica, as for evictions), then save the MLPs and the host tables
         if rank == 0:
             cache_group.flush_to_host(emb_tables, average=args.average_on_writeback)
+            if eng.qr is not None:
+                eng.flush_wr(emb_tables)        # the remainder tables: the engine's, not the cache group's
             torch.save({"dlrm": {k: v.detach().cpu() for k, v in dlrm.state_dict().items()},
-                        "emb": [E.weight.data.clone() for E in emb_tables.emb_l],
+                        "emb": [(E.weight_q if hasattr(E, "weight_q") else E.weight).data.clone() for E in emb_tables.emb_l],
+                        **({} if qr_layout is None else
+                           {"emb_r": [E.weight_r.data.clone() if hasattr(E, "weight_r") else None for E in emb_tables.emb_l]}),
                         "ln_emb": [int(n) for n in ln_emb], "m_spa": int(m_spa)}, args.save_model)
         if world > 1:
             dist.barrier()
@@ -792,12 +853,13 @@ def main(argv=None):
     ln_top = np.fromstring(str(num_int) + "-" + args.arch_mlp_top, dtype=int, sep="-")
     if m_spa != m_den_out:
         sys.exit("ERROR: arch-sparse-feature-size " + str(m_spa) + " does not match last dim of bottom mlp " + str(m_den_out))
-    if args.md_flag or args.qr_flag:
+    if args.md_flag:
         # the reference computes md_solver's width list here and then builds plain tables from it (main_no_ddp.py:612-621),
-        # which raises in nn.EmbeddingBag; --qr-flag only changes a width check (:579-596), the tables stay plain.  A cache row has one width and one source
-        # row, so neither trick has cached semantics: the operators are available stand-alone
-        # (cdlrm_amd.tricks, Embedding_Table_Group(qr_flag= / md_flag=)).
-        sys.exit("ERROR: --md-flag / --qr-flag tables cannot feed the embedding cache (stand-alone operators only)")
+        # which raises in nn.EmbeddingBag.  A cache row has one width, so the trick has no cached semantics: the operator is
+        # available stand-alone (cdlrm_amd.tricks, Embedding_Table_Group(md_flag=)).  (--qr-flag: the reference only changes a
+        # width check, :579-596, and its tables stay plain; here the quotient rows train through the cache, DESIGN.md 4.4 --
+        # --qr-operation=concat, which changes the row width, is refused where the arguments are read.)
+        sys.exit("ERROR: --md-flag tables cannot feed the embedding cache (stand-alone operator only)")
     from . import _lib
     try:
         _lib.require_gpu("cdlrm_amd.main_no_ddp")
@@ -827,9 +889,22 @@ def main(argv=None):
                   flush=True)
     from . import synth
     from .hostmem import make_host_tables
-    emb_tables = make_host_tables(ln_emb, m_spa, device=dev, seed=args.numpy_rand_seed, rank=rank, world=args.world_size,
-                                  shm_name="cdlrm_run_%d" % args.master_port,
-                                  barrier=(dist.barrier if args.world_size > 1 else (lambda: None)))
+    if args.qr_flag:
+        # quotient-remainder host tables (tables above --qr-threshold; the others plain); one rank (ProcessArgs refuses more: the
+        # tables would have to go through make_host_tables' shared / replicas decision), one pinned copy
+        np.random.seed(args.numpy_rand_seed)
+        torch.manual_seed(args.numpy_rand_seed)
+        emb_tables = Embedding_Table_Group(m_spa, ln_emb, qr_flag=True, qr_operation=args.qr_operation,
+                                           qr_collisions=args.qr_collisions, qr_threshold=args.qr_threshold).pin()
+        if rank == 0 and emb_tables.qr_layout() is not None:
+            lay = emb_tables.qr_layout()
+            print("Quotient-remainder tables: %d of %d (c = %d, %s), %.2f GB of quotient rows instead of %.2f GB"
+                  % (sum(1 for c in lay["collisions"] if c), len(lay["rows"]), lay["c"], lay["operation"],
+                     sum(lay["rows_q"]) * m_spa * 4 / 1e9, sum(lay["rows"]) * m_spa * 4 / 1e9), flush=True)
+    else:
+        emb_tables = make_host_tables(ln_emb, m_spa, device=dev, seed=args.numpy_rand_seed, rank=rank, world=args.world_size,
+                                      shm_name="cdlrm_run_%d" % args.master_port,
+                                      barrier=(dist.barrier if args.world_size > 1 else (lambda: None)))
     if train_ld is None and args.data_generation in ("random", "synthetic"):
         # the reference's random front ends (dlrm_data_pytorch.py:658-684): uniform multi-hot bags, or bags with the reuse
         # profile of a recorded trace (--data-trace-file, "j" = table number); ragged tables either way

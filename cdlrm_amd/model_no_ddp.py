@@ -119,6 +119,13 @@ class Embedding_Table_Group(nn.Module):
         """Pinned (page-locked, GPU-mapped) copies of the tables; idempotent."""
         if not self._pinned:
             for E in self.emb_l:
+                if hasattr(E, "weight_q"):      # a quotient-remainder table: the cache reads its quotient rows
+                    w = E.weight_q.data
+                    if not w.is_pinned():
+                        p = torch.empty(w.shape, dtype=w.dtype, pin_memory=True)
+                        p.copy_(w)
+                        E.weight_q.data = p
+                    continue
                 if not hasattr(E, "weight"):
                     continue
                 w = E.weight.data
@@ -155,15 +162,33 @@ class Embedding_Table_Group(nn.Module):
                                  "dimension table; the cached path needs plain host tables)" % (type(E).__name__, k))
         return E
 
+    def qr_layout(self):
+        """The quotient-remainder layout the cached path trains through, or None for a group of plain tables:
+        dict(rows = rows of the unsplit tables, rows_q = rows the cache sees (quotient rows of a QR table), collisions = c per
+        QR table and 0 per plain one, c, operation)."""
+        if not getattr(self, "qr_flag", False) or not any(hasattr(E, "weight_q") for E in self.emb_l):
+            return None
+        rows, rows_q, coll = [], [], []
+        for E in self.emb_l:
+            if hasattr(E, "weight_q"):
+                rows.append(int(E.num_categories)); rows_q.append(int(E.weight_q.shape[0])); coll.append(int(E.num_collisions))
+            else:
+                rows.append(int(E.weight.shape[0])); rows_q.append(int(E.weight.shape[0])); coll.append(0)
+        return dict(rows=rows, rows_q=rows_q, collisions=coll, c=int(self.qr_collisions), operation=self.qr_operation)
+
     def device_pointers(self) -> List[int]:
+        """The host rows the cache is fed from, per table: a plain table's rows, a quotient-remainder table's QUOTIENT rows."""
         if not self._pinned:
             self.pin()
-        return [int(self._plain(E, k).weight.data.data_ptr()) for k, E in enumerate(self.emb_l)]
+        return [int((E.weight_q if hasattr(E, "weight_q") else self._plain(E, k).weight).data.data_ptr())
+                for k, E in enumerate(self.emb_l)]
 
     def fetch_unique_idx_slices(self, lists_of_unique_indices):
         """rows[k] = W_host[k][uniq_k] (model_no_ddp.py:80-87), gathered by the GPU straight from the
         pinned tables; returns device tensors."""
         out = []
+        for k, E in enumerate(self.emb_l):
+            self._plain(E, k)
         ptrs = self.device_pointers()
         for k, uniq in enumerate(lists_of_unique_indices):
             if not uniq.is_cuda:
@@ -254,16 +279,23 @@ class Embedding_Table_Cache_Group(nn.Module):
     """
 
     def __init__(self, m_spa, ln_emb, max_cache_size, aux_table_size, num_ways, cache_init="normal", aux_phases=2,
-                 device=None):
+                 device=None, qr_layout=None):
         """aux_phases = 2 (default) appends a second aux region to every table so that the fused engine can fill the
         NEXT batch's miss rows while the current batch still trains on its own (engine.py); callers that never pass
         aux_phase see exactly the reference's tables.
         Build-only keywords (not in the reference's signature, model_no_ddp.py:102): cache_init ("normal" = the
         reference's nn.EmbeddingBag default init drawn from the torch CPU generator; "zeros" / "empty" for synthetic
         runs), aux_phases, device (allocate the "zeros" / "empty" buffers directly in HBM instead of moving 10-34 GB
-        through host memory with .to(device))."""
+        through host memory with .to(device)), qr_layout (Embedding_Table_Group.qr_layout(): the cache of a quotient-remainder
+        table holds QUOTIENT rows keyed by q, so its geometry uses rows_q where it uses n_k for a plain table; ln_emb is then
+        the UNSPLIT sizes, kept as `ln_emb_full`)."""
         super().__init__()
         self.aux_phases = max(1, int(aux_phases))
+        self.qr = qr_layout
+        if qr_layout is not None:
+            assert [int(n) for n in ln_emb] == list(qr_layout["rows"]), "qr_layout belongs to other tables"
+            self.ln_emb_full = np.asarray(ln_emb)
+            ln_emb = qr_layout["rows_q"]
         self.ln_emb = np.asarray(ln_emb)
         self.num_ways = int(num_ways)
         self.m_spa = int(m_spa)
@@ -335,7 +367,8 @@ class Embedding_Table_Cache_Group(nn.Module):
         """End-of-run cache flush (the reference only ever writes EVICTED rows back,
         cache_manager.py:57-62): every valid tag's cache row goes to its host row, `W_host[k][tag] = cache row`
         (or the average with average=True, as --average-on-writeback does for evictions).  Aux rows are transient
-        copies and are not written.  Synchronises."""
+        copies and are not written.  Synchronises.  (Quotient-remainder mode: the rows are quotient rows; the remainder tables
+        belong to the engine, TrainEngine.flush_wr writes them back.)"""
         ptrs = emb_tables.device_pointers()
         for k in range(len(self.cache_sizes)):
             P = self.cache_sizes[k]
@@ -387,6 +420,10 @@ class Embedding_Table_Cache_Group(nn.Module):
         T = len(self.emb_l)
         if (lS_o is not None and T != len(lS_o)) or (T != len(lS_i)):
             sys.exit("ERROR: corrupted model input detected in parallel_forward call")
+        if self.qr is not None:
+            # a missing kernel is an error, not a pass-through of the quotient rows
+            raise NotImplementedError("quotient-remainder tables train through engine.TrainEngine (DESIGN.md 4.4); the "
+                                      "drop-in forward() has no remainder tables to compose with")
         dev = self.weight.device
         if isinstance(lS_i, (list, tuple)):
             if len({int(x.numel()) for x in lS_i}) != 1:

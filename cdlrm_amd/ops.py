@@ -209,6 +209,78 @@ def embbag_fwd(ctx: CacheCtx, slots: torch.Tensor, offsets: Optional[torch.Tenso
                                       stream_ptr(stream)))
 
 
+# ---- the quotient-remainder trick on the cached step (csrc/qr_cached.hip) ----------
+
+QR_OPS = {"mult": 0, "add": 1}
+
+
+def qr_cached_shape_ok(dim: int, c: int) -> bool:
+    """The backward keeps one [c, D] accumulator per lane group of a 256-thread workgroup in LDS: 64 KB at the most."""
+    d4 = max(1, int(dim) // 4)
+    lpr = min(64, max(4, 1 << (d4 - 1).bit_length()))
+    return (256 // lpr) * int(c) * d4 * 16 <= 65536
+
+
+def qr_split(ctx: CacheCtx, idx: torch.Tensor, collisions: torch.Tensor, table_rows: torch.Tensor,
+             q: Optional[torch.Tensor] = None, r: Optional[torch.Tensor] = None, stream=None):
+    """idx int64 [T, n] (any row pitch) -> (q int64, r uint8), both [T, n]; q=idx splits in place.  collisions int32 [T]
+    (0 = a plain table), table_rows int64 [T] (rows of the unsplit tables), both on the device."""
+    _require_cuda(idx, "idx")
+    assert idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == ctx.T and idx.stride(1) == 1
+    assert collisions.dtype == torch.int32 and collisions.numel() == ctx.T and collisions.is_cuda
+    assert table_rows.dtype == torch.int64 and table_rows.numel() == ctx.T and table_rows.is_cuda
+    n = idx.shape[1]
+    if q is None:
+        q = torch.empty((ctx.T, n), dtype=torch.int64, device=idx.device)
+    if r is None:
+        r = torch.empty((ctx.T, n), dtype=torch.uint8, device=idx.device)
+    assert q.dtype == torch.int64 and tuple(q.shape) == (ctx.T, n) and q.stride(1) == 1
+    assert r.dtype == torch.uint8 and tuple(r.shape) == (ctx.T, n) and r.stride(1) == 1
+    ld = lambda t: t.stride(0) if ctx.T > 1 else max(n, 1)
+    check(_lib.lib().cdlrm_qr_split(ctx.handle, idx.data_ptr(), n, ld(idx), collisions.data_ptr(), table_rows.data_ptr(),
+                                    q.data_ptr(), ld(q), r.data_ptr(), ld(r), stream_ptr(stream)))
+    return q, r
+
+
+def _qr_args(ctx: CacheCtx, slots, r, Wr, collisions):
+    n = slots.shape[1]
+    assert slots.dtype == torch.int32 and tuple(slots.shape) == (ctx.T, n) and slots.is_contiguous()
+    assert r.dtype == torch.uint8 and tuple(r.shape) == (ctx.T, n) and r.stride(1) == 1
+    assert Wr.dtype == torch.float32 and Wr.dim() == 3 and Wr.shape[0] == ctx.T and Wr.shape[2] == ctx.D and Wr.is_contiguous()
+    assert collisions.dtype == torch.int32 and collisions.numel() == ctx.T
+    return n, (r.stride(0) if ctx.T > 1 else max(n, 1)), int(Wr.shape[1])
+
+
+def qr_cached_fwd(ctx: CacheCtx, slots: torch.Tensor, r: torch.Tensor, Wr: torch.Tensor, collisions: torch.Tensor, op: int,
+                  out: torch.Tensor, ld_bag: int, ld_table: int, stream=None):
+    """cdlrm_embbag_fwd's gather composed with the remainder rows in one pass: out[b, k] = row(slot) (*|+) Wr[k][r]."""
+    n, ld_r, c = _qr_args(ctx, slots, r, Wr, collisions)
+    check(_lib.lib().cdlrm_qr_cached_fwd(ctx.handle, slots.data_ptr(), r.data_ptr(), ld_r, Wr.data_ptr(), collisions.data_ptr(),
+                                         c, int(op), n, out.data_ptr(), ld_bag, ld_table, stream_ptr(stream)))
+
+
+def qr_cached_bwd_work(ctx: CacheCtx, n: int, c: int) -> torch.Tensor:
+    nbytes = int(_lib.lib().cdlrm_qr_cached_bwd_work_bytes(ctx.T, n, ctx.D, int(c)))
+    return torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=ctx.device)
+
+
+def qr_cached_bwd(ctx: CacheCtx, slots: torch.Tensor, r: torch.Tensor, Wr: torch.Tensor, collisions: torch.Tensor, op: int,
+                  grad: torch.Tensor, ld_bag: int, ld_table: int, work: torch.Tensor, stream=None):
+    """grad (dL/dE, addressed like the forward's out) -> the cache rows' gradient, in place; the remainder tables' partial sums
+    into `work` (qr_cached_bwd_work)."""
+    n, ld_r, c = _qr_args(ctx, slots, r, Wr, collisions)
+    check(_lib.lib().cdlrm_qr_cached_bwd(ctx.handle, slots.data_ptr(), r.data_ptr(), ld_r, Wr.data_ptr(), collisions.data_ptr(),
+                                         c, int(op), n, grad.data_ptr(), ld_bag, ld_table, work.data_ptr(), stream_ptr(stream)))
+
+
+def qr_cached_bwd_finish(ctx: CacheCtx, collisions: torch.Tensor, n: int, work: torch.Tensor, lr: float, Wr: torch.Tensor,
+                         gWr: Optional[torch.Tensor] = None, stream=None):
+    """Wr -= lr * gWr, gWr = the partial sums of qr_cached_bwd in ascending order (optionally stored)."""
+    assert Wr.dtype == torch.float32 and Wr.is_contiguous() and (gWr is None or (gWr.shape == Wr.shape and gWr.is_contiguous()))
+    check(_lib.lib().cdlrm_qr_cached_bwd_finish(ctx.handle, collisions.data_ptr(), int(Wr.shape[1]), n, work.data_ptr(), float(lr),
+                                                Wr.data_ptr(), ptr(gWr), stream_ptr(stream)))
+
+
 def embbag_bwd_work(ctx: CacheCtx, n: int, device) -> torch.Tensor:
     """(zero-filled: embbag_bwd_apply_sorted uses the buffer's scratch without a prepare in front)"""
     nbytes = int(_lib.lib().cdlrm_embbag_bwd_work_bytes(ctx.T, n, ctx.D))

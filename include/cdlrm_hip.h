@@ -387,6 +387,38 @@ int cdlrm_qr_embbag_bwd(const int64_t* idx, const int64_t* offsets, int64_t n, i
                         const float* eq, const float* er, const float* grad_out, int64_t rows_q,
                         int32_t collisions, int32_t dim, int32_t op, float* gWq, float* gWr, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The quotient-remainder trick ON the cached training step (the reference never wires it there, so the
+ * semantics are this build's).  The cache holds QUOTIENT rows keyed by q; the remainder tables Wr fp32 [T, c, D] live whole
+ * in HBM (the rows of plain tables unused).  One lookup per bag.  collisions: device int32 [T], c for a QR table, 0 for a
+ * plain one (q = idx, r = 0, the row passes through).  op 0: mult, 1: add.
+ *   cdlrm_qr_split   idx int64 [T, n] (row pitch ld_idx) -> q int64 (pitch ld_q; may alias idx) and r uint8 (pitch ld_r):
+ *                    r = idx % c, q = (int64)((float)idx / (float)c) -- the stand-alone operator's float32 quotient -- and,
+ *                    for an in-range idx, clamped to rows_q - 1 (rows_q = ceil(table_rows / c)).  table_rows: device int64
+ *                    [T], the rows of the UNSPLIT tables; an idx outside [0, table_rows) sets the context's error word
+ *                    (CDLRM_ERANGE) and yields q = r = 0.
+ *   _fwd             out[b, k] = row(slots[k, b]) (*|+) Wr[k][r[k, b]]; slots int32 [T, n] as the probe / take left them,
+ *                    out addressed as cdlrm_embbag_fwd's.  One rounding per element.
+ *   _bwd             grad (addressed like out) holds dL/dE; rewritten IN PLACE to the cache rows' gradient (mult: g * Wr[k][r];
+ *                    add: unchanged), what cdlrm_embbag_bwd_apply / _apply_sorted then consume; the [c, D] sums
+ *                    gWr[k][r] = sum_b g * row (mult) / sum_b g (add) of fixed ranges of bags go to `work`
+ *                    (cdlrm_qr_cached_bwd_work_bytes(T, n, D, c) bytes, 16-byte aligned), in a fixed order, no float atomics.
+ *   _bwd_finish      adds those partial sums in ascending order and applies Wr -= lr * gWr; gWr fp32 [T, c, D] or NULL
+ *                    receives the sums.  The partition depends on (T, n, D, c) only: two calls give the same bits.
+ * Both factors of a step are read by _bwd before _bwd_finish (Wr) and the sparse-SGD path (rows) update them.
+ * ------------------------------------------------------------------------------------------- */
+int cdlrm_qr_split(cdlrm_ctx* ctx, const int64_t* idx, int64_t n, int64_t ld_idx, const int32_t* collisions,
+                   const int64_t* table_rows, int64_t* q, int64_t ld_q, uint8_t* r, int64_t ld_r, void* stream);
+int cdlrm_qr_cached_fwd(cdlrm_ctx* ctx, const int32_t* slots, const uint8_t* r, int64_t ld_r, const float* Wr,
+                        const int32_t* collisions, int32_t c, int32_t op, int64_t n, float* out, int64_t ld_bag,
+                        int64_t ld_table, void* stream);
+uint64_t cdlrm_qr_cached_bwd_work_bytes(int32_t num_tables, int64_t n, int32_t dim, int32_t c);
+int cdlrm_qr_cached_bwd(cdlrm_ctx* ctx, const int32_t* slots, const uint8_t* r, int64_t ld_r, const float* Wr,
+                        const int32_t* collisions, int32_t c, int32_t op, int64_t n, float* grad, int64_t ld_bag,
+                        int64_t ld_table, void* work, void* stream);
+int cdlrm_qr_cached_bwd_finish(cdlrm_ctx* ctx, const int32_t* collisions, int32_t c, int64_t n, const void* work, float lr,
+                               float* Wr, float* gWr, void* stream);
+
 /* Plain EmbeddingBag(mode="sum") over one stand-alone table of ANY width, forward and dense backward: the `embs` of the
  * mixed-dimension trick's PrEmbeddingBag (tricks/md_embedding_bag.py:60-78; its widths are powers of two down to 1).
  * Stand-alone operator like the QR bag: the reference never wires it into the cached path (main_no_ddp.py:612-621).
