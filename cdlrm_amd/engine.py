@@ -23,7 +23,7 @@ from __future__ import annotations
 import itertools
 import math
 import os
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -607,6 +607,95 @@ class WindowPipeline:
         return out
 
 
+class Resolved(NamedTuple):
+    """What WindowResolver.batch(j) hands a step: this rank's lookups of batch j as views into the chunk's ring slot, the
+    chunk's ready event and where the batch sits (resolver, j) -- the row merge looks AHEAD from there (lookahead()).  step()
+    also takes a plain (slots, src, ready) tuple: a batch without a position."""
+    slots: torch.Tensor
+    src: torch.Tensor
+    ready: object
+    pos: Optional[tuple] = None
+
+
+class SortedViews(NamedTuple):
+    """WindowResolver.sorted_views(j): the addresses of batch j's sorted lists (keys, meta, once-only flags), the elements
+    between two tables' lists, the slice's event and the slice sort's serial."""
+    keys: int
+    meta: int
+    once: int
+    stride: int
+    event: object
+    serial: int
+
+
+class Handover(NamedTuple):
+    """What a step leaves for the next one when it has issued that batch's take: which index tensor it took (ptr, shape), the
+    aux region the misses went to, the probe buffers and the event behind the take, and what rode along -- the wait for the
+    deferred top-MLP update (chained_top), the batch's slot sort (prepared), and whether the take was ordered behind its
+    slice's sort (sorted_ok).  A launch tape keeps stored(); every replay hands it on with handed()."""
+    ptr: int
+    shape: tuple
+    phase: int
+    out: tuple
+    probed: object
+    chained_top: bool = False
+    prepared: bool = False
+    sorted_ok: bool = False
+
+    def matches(self, lS_i) -> bool:
+        """Was this batch's take issued by the previous step?"""
+        return self.ptr == lS_i.data_ptr() and self.shape == tuple(lS_i.shape)
+
+    def stored(self) -> "Handover":
+        return self._replace(ptr=0)
+
+    def handed(self, next_idx) -> "Handover":
+        return self._replace(ptr=next_idx.data_ptr())
+
+
+class StepPath(NamedTuple):
+    """Every decision one training step makes, settled once by TrainEngine._step_path before anything is issued: _wait_slices,
+    _fwd_bwd, _issue_resolve and step()'s gradient exchange read them here, a launch tape is keyed by (path, layout) and
+    _tape_ptrs names its cells from it.  Two steps with equal paths issue the same calls with the same arguments up to the
+    addresses and strides of the layout.  What is fixed when the engine is built -- defer_top, cat, multi, the fused head, the
+    layer lists, the loss, quotient-remainder mode, the device -- is a constant and not part of it."""
+    B: int
+    n: int
+    n_bags: int                 # bags per table: B, or B + 1 for squared-off ragged bags
+    offsets: bool               # multi-hot bags (lS_o given)
+    next_n: int                 # lookups per table of the batch handed over (0: none)
+    hit: bool                   # this batch's take was issued by the previous step
+    phase: int                  # aux region of the batch being trained
+    top_waited: bool            # ... and that take was recorded behind the deferred top-MLP update
+    prepared: bool              # ... and sorted this batch's slots right behind itself
+    nxt: bool                   # a next batch is handed over
+    resolved: bool              # an in-line take reads the window's resolved views (else: a tag probe)
+    next_resolved: bool
+    two_phase: bool             # the next batch's take at the head of the step, into the other aux region
+    chain: bool                 # ... or chained behind this step's embedding update
+    side_gather: bool           # the gather on the side stream, beside the bottom MLP
+    gather_alone: bool          # B >= gather_alone_min: a two-phase take starts behind the gather
+    fused: bool                 # the gather rides in the interaction kernels
+    sorted: Optional[int]       # this batch's lists were sorted with its slice: their stride (None: the step sorts)
+    once: bool                  # the once-only slots are updated by the interaction backward
+    next_sorted: bool
+    chain_sort: bool            # the chained take sorts the next batch's slots
+    chained_top: bool           # ... and waits for this step's top-MLP update
+    next_bufs: int              # the probe buffers a next take writes
+    emb_done_seen: bool         # emb_done has been recorded before
+    timed: bool                 # the gather's launch carries timing events
+    loss_sync: bool
+    resolve_cols: Optional[int]  # a look-ahead chunk's resolve is placed behind the interaction forward: its columns
+    fwd_marked: bool            # ... and its event completes with the fused forward's launch
+    attach: bool                # cross-stream events complete with the launch they follow
+    join: str                   # what the training queue waits for at the end: "full", "emb_done" or "none"
+    lanes: int                  # issuing threads of a native tape
+    wide_gemm: bool
+    matmul_precision: str
+    lr: float
+    lr_embeds: float
+
+
 class WindowResolver:
     """The look-ahead window's lookups resolved ONCE (tags only change at a refill, main_no_ddp.py:393-399): tag match,
     ordered miss numbering per batch and the place of every miss in the window's victim rows (cdlrm_window_resolve), in
@@ -741,7 +830,7 @@ class WindowResolver:
                 self._armed = c
                 break               # one chunk per step
             if hasattr(eng, "_issue_resolve"):
-                eng._issue_resolve(pr, lambda fn, *a: fn(*a), S.current_stream(eng.dev), placed=False)
+                eng._issue_resolve(pr, lambda fn, *a: fn(*a), S.current_stream(eng.dev), placed=None)
             else:                   # (host-logic tests: a bare engine stand-in)
                 ops.window_resolve(self.ctx, pr["cols"], self.lbs, pr["ws"], pr["wsrc"], stream=eng.pref, batch_len=self.B)
         if not urgent:
@@ -789,9 +878,8 @@ class WindowResolver:
             self.sorted_upto = b0 + cnt
             self._sorted_at.pop(b0 - self.RING * self.CH, None)
 
-    def sorted_views(self, j: int):
-        """(keys, meta, once addresses of batch j's sorted lists, elements between two tables' lists, the slice's event, the
-        slice sort's serial) -- or None: not sorted (yet)."""
+    def sorted_views(self, j: int) -> Optional[SortedViews]:
+        """Batch j's sorted lists -- or None: not sorted (yet)."""
         if not self.sort_chunks or j >= self.sorted_upto:
             return None
         c = j // self.CH
@@ -801,10 +889,10 @@ class WindowResolver:
         if at is None:
             return None
         k, m, o = ops.embbag_bwd_sorted_views(self.ctx, self._sorted_ring[c % self.RING], nbc, self.width, jl)
-        return k, m, o, nbc * self.width, self._sorted_ev[c % self.RING][jl // self.SL], at[1]
+        return SortedViews(k, m, o, nbc * self.width, self._sorted_ev[c % self.RING][jl // self.SL], at[1])
 
-    def batch(self, j: int):
-        """(wslots view, wsrc view, ready event) of this rank's lookups of batch j of the window."""
+    def batch(self, j: int) -> Resolved:
+        """This rank's lookups of batch j of the window."""
         c = j // self.CH
         self.maxj = max(self.maxj, j)
         self.ensure(j + 1, urgent=True)
@@ -812,8 +900,7 @@ class WindowResolver:
         col = (j - c * self.CH) * self.B + self.col0
         if c >= 2 and (c - 2) in self.chunks:       # chunks far behind the training position are not needed any more
             del self.chunks[c - 2]
-        # (4th entry: where this batch sits in which window -- the engine's row merge looks AHEAD from there, lookahead())
-        return ws[:, col:col + self.width], wsrc[:, col:col + self.width], ev, (self, j)
+        return Resolved(ws[:, col:col + self.width], wsrc[:, col:col + self.width], ev, (self, j))
 
     def lookahead(self, j: int, kmax: int):
         """[(k, slot ids of GLOBAL batch j + k -- every rank's lookups --, ready event)] for k = 1, 2, ... while the batch
@@ -1009,8 +1096,8 @@ class TrainEngine:
         self.place_resolve_min = 8192
         self.mark_next = False
         self._mark_this = False
-        self._fwd_marked = False
         self._pending_resolve = None
+        self._step_key = None                   # (StepPath, layout) of the last step
 
     # ---- quotient-remainder mode -------------------------------------------------------------------------------------
     def _init_qr(self, host_tables):
@@ -1110,12 +1197,13 @@ class TrainEngine:
             off_b += m
         self.r_width = kp[top0]
 
-    def _issue_resolve(self, pr, rec, main, placed: bool):
-        """One look-ahead chunk's resolve on the prefetch stream (WindowResolver prepares `pr`).  placed: from inside a step,
-        behind its interaction forward (an event recorded on the training queue: one marker packet per chunk, i.e. per 16 steps)."""
+    def _issue_resolve(self, pr, rec, main, placed: Optional[StepPath]):
+        """One look-ahead chunk's resolve on the prefetch stream (WindowResolver prepares `pr`).  placed: the path of the step
+        that issues it behind its interaction forward (an event recorded on the training queue: one marker packet per chunk, i.e.
+        per 16 steps); None: issued at once."""
         pst, ev = self.pref, self._events
-        if placed:
-            if not self._fwd_marked:            # (else: fwd_mark completes with the interaction forward's launch)
+        if placed is not None:
+            if not placed.fwd_marked:            # (else: fwd_mark completes with the interaction forward's launch)
                 rec(ev["fwd_mark"].record, main)
             rec(pst.wait_event, ev["fwd_mark"])
         elif pr["first"]:
@@ -1138,7 +1226,7 @@ class TrainEngine:
         pr, self._pending_resolve = self._pending_resolve, None
         self.mark_next = False
         if pr is not None:
-            self._issue_resolve(pr, lambda fn, *a: fn(*a), S.current_stream(self.dev), placed=False)
+            self._issue_resolve(pr, lambda fn, *a: fn(*a), S.current_stream(self.dev), placed=None)
 
     def _fused_gather(self, lS_o) -> bool:
         """This step's gather rides in the interaction kernels (fuse_gather)."""
@@ -1155,32 +1243,90 @@ class TrainEngine:
         the side stream (see _fwd_bwd)."""
         return not self._side_gather(B) and next_idx is not None and self._next_res is not None and lS_o is None
 
+    def _step_path(self, X, lS_i, lS_o, next_idx) -> StepPath:
+        """The decisions of the step step() is about to issue (StepPath), from the batch, the hand-over of the previous step, the
+        resolver's views and the schedule knobs.  The one place that evaluates them."""
+        B, n = X.shape[0], lS_i.shape[1]
+        pf = self._pref
+        hit = pf is not None and pf.matches(lS_i)
+        phase = pf.phase if hit else self._phase
+        nxt = next_idx is not None
+        side_gather = self._side_gather(B)
+        # Long batches with the window-resident probe: the next batch's take costs ~10 us stand-alone, so it no longer needs
+        # a stream and an aux region of its own (that pipeline hid 250 us of PCIe reads).  It follows this step's embedding
+        # update in order on the side stream, and ONE event recorded there -- after the take and, on one rank, after the
+        # deferred top-MLP update -- is all the next step's gather waits for: the main queue carries one wait per step
+        # instead of three (probe, top update, embedding update) plus a record, each a 6-8 us bubble (measured).
+        chain = self._chain(B, next_idx, lS_o)
+        two_phase = self.ctx.aux_phases >= 2 and not chain
+        fused = self._fused_gather(lS_o)
+        # this batch's slot lists were sorted with its look-ahead chunk (WindowResolver.ensure_sorted): no sort in the step, and
+        # the once-only slots can be updated by the interaction backward (it reads the sort's flags)
+        # (the flags of a batch's OWN sort would cost the training queue a wait for the side stream in front of the interaction
+        #  backward: measured 21 us, three times what the folding saves)
+        sv = self._cur_sorted if (lS_o is None and n == B) else None
+        attach = bool(self.attach_events and S.is_hip(self.dev))
+        # the next step's gather runs on the side stream, in order behind this embedding update, and its probe waits for emb_done
+        # on its own stream -- nothing on the main stream reads the cache rows before the next full join (window boundary, row
+        # merge, evaluate(), finish()), so the main queue is spared one more wait (6-8 us bubble)
+        spared = nxt and side_gather and two_phase
+        if self.multi:          # step() joins AFTER it has issued the gradient all-reduce: the exchange overlaps the embedding update
+            join = "none" if (self.defer_top and spared) else "emb_done"
+        elif not nxt:
+            join = "full"
+        elif chain or spared:   # (chain: the next gather waits for the take's event, recorded behind emb_done)
+            join = "none"
+        else:                   # cache rows are updated; the prefetched probe keeps running
+            join = "emb_done"
+        pr = self._pending_resolve if self._mark_this else None
+        return StepPath(
+            B=B, n=n, n_bags=B if lS_o is None else lS_o.shape[1], offsets=lS_o is not None,
+            next_n=next_idx.shape[1] if nxt else 0, hit=hit, phase=phase, top_waited=bool(hit and pf.chained_top),
+            prepared=bool(hit and pf.prepared), nxt=nxt, resolved=self._res is not None and lS_o is None,
+            next_resolved=self._next_res is not None, two_phase=two_phase, chain=chain, side_gather=side_gather,
+            gather_alone=B >= self.gather_alone_min, fused=fused, sorted=None if sv is None else sv.stride,
+            once=bool(self.fuse_once and fused and sv is not None), next_sorted=self._next_sorted is not None,
+            chain_sort=chain and self._next_sorted is None, chained_top=chain and self.defer_top and not self.multi,
+            next_bufs=(1 - phase) if two_phase else 2 + (self.iter & 1), emb_done_seen=self._emb_done is not None,
+            timed=self._gslot is not None, loss_sync=self.loss_sync, resolve_cols=None if pr is None else int(pr["cols"].shape[1]),
+            fwd_marked=bool(pr is not None and attach and fused), attach=attach, join=join,
+            lanes=self.tape_lanes if B < self.tape_lanes_below else 1, wide_gemm=bool(self.wide_gemm),
+            matmul_precision=self.matmul_precision, lr=self.lr, lr_embeds=self.lr_embeds)
+
     def _take(self, idx, res, phase: int, which, st):
         """A batch's (slots, miss_pos, miss_count) into the probe buffers `which`, misses into aux region `phase`, on stream st:
         its take when the window resolved it (res: WindowResolver.batch), else its tag probe."""
         out = self._probe_bufs(idx.shape[1], which)
         if res is None:
             return ops.embbag_probe(self.ctx, idx, stream=st, aux_phase=phase, out=out)
-        ops.embbag_take(self.ctx, idx, res[0], res[1], out[0], aux_phase=phase, stream=st)
+        ops.embbag_take(self.ctx, idx, res.slots, res.src, out[0], aux_phase=phase, stream=st)
         return out
 
-    def _wait_slices(self, cur, nxt, B: int, next_idx):
+    def _hand_over(self, path: StepPath, next_idx, phase: int, st):
+        """The next batch's take (or tag probe) on stream st, misses into aux region `phase`; returns what the next step needs
+        of it.  The caller records `probed` behind whatever else it puts between the take and the next step."""
+        out = self._take(next_idx, self._next_res, phase, path.next_bufs, st)
+        return Handover(ptr=next_idx.data_ptr(), shape=tuple(next_idx.shape), phase=phase, out=(out[0], out[1], out[2]),
+                        probed=self._events["probed"][path.next_bufs], chained_top=path.chained_top, prepared=path.chain_sort,
+                        sorted_ok=path.next_sorted)
+
+    def _wait_slices(self, path: StepPath, cur, nxt):
         """The streams of this batch's and the next batch's takes wait for their slices' sorts (cur / nxt: sorted_views() of
-        the two batches, or None; B, next_idx: as step() has them) -- once per slice sort, told apart by its serial: the slice
-        events are a ring, and an event that comes round again has been recorded by another sort."""
+        the two batches, or None) -- once per slice sort, told apart by its serial: the slice events are a ring, and an event
+        that comes round again has been recorded by another sort."""
         if not self.slice_wait:
             return
-        if nxt is not None and nxt[5] != self._next_waited:
+        if nxt is not None and nxt.serial != self._next_waited:
             # the next batch's take (two aux regions: prefetch stream; chained / single region: side stream) waits for its
             # slice's sort: this step's successor -- gather, interaction backward (the once-only flags), embedding update -- is
             # ordered behind that take.  (Not on both: with two aux regions the `gathered` record THIS step's fused forward
             # waits for sits on the side stream -- a wait for a sort that is still running would hold the training queue.)
-            (self.pref if self.ctx.aux_phases >= 2 and not self._chain(B, next_idx, None) else self.side).wait_event(nxt[4])
-            self._next_waited = nxt[5]
-        if cur is not None and cur[5] != self._cur_waited:
+            (self.pref if path.two_phase else self.side).wait_event(nxt.event)
+            self._next_waited = nxt.serial
+        if cur is not None and cur.serial != self._cur_waited:
             # this batch's take, if no earlier step issued it, runs in line on the side stream; its gather follows that stream
-            self.side.wait_event(cur[4])
-            self._cur_waited = cur[5]
+            self.side.wait_event(cur.event)
+            self._cur_waited = cur.serial
 
     def _reduce_avg(self) -> bool:
         """grad /= W followed by all-reduce(SUM) (main_no_ddp.py:239-244) as ONE all-reduce(AVG): on RCCL, for a
@@ -1382,6 +1528,10 @@ class TrainEngine:
         else:
             assert r is None, "r columns belong to quotient-remainder mode"
         self._r = r
+        if res is not None and not isinstance(res, Resolved):
+            res = Resolved(*res)
+        if next_res is not None and not isinstance(next_res, Resolved):
+            next_res = Resolved(*next_res)
         if self.evict_victim:
             assert not self.multi, "--evict-victim-cache is defined for one rank (every rank would write its own misses' rows)"
             next_idx = next_res = None          # the next batch's take follows this batch's write-back
@@ -1413,39 +1563,49 @@ class TrainEngine:
         if self._pump is not None:
             # the deadlines of a pending merge were computed for the batches FOLLOWING the merge step in its window: a step that
             # is not the expected next batch of that window (another resolver, a jump) gets the whole merge first
-            p, pos = self._pump, (res[3] if (res is not None and len(res) > 3) else None)
+            p, pos = self._pump, (res.pos if res is not None else None)
             if pos is None or pos[0] is not p["rs"] or pos[1] != p["j0"] + (self.iter - p["step0"]):
                 self._pump_finish()
         if self._pump is not None:
             self._pump_wait()       # rows of an earlier merge that THIS step uses have landed
         self._cur_sorted = self._next_sorted = None
-        if lS_o is None and not self.evict_victim:
-            if res is not None and len(res) > 3:
-                self._cur_sorted = res[3][0].sorted_views(res[3][1])
-            if self._next_res is not None and len(next_res) > 3:
-                self._next_sorted = next_res[3][0].sorted_views(next_res[3][1])
+        sliced = lS_o is None and not self.evict_victim
+        if sliced:
+            if res is not None and res.pos is not None:
+                self._cur_sorted = res.pos[0].sorted_views(res.pos[1])
+            if self._next_res is not None and next_res.pos is not None:
+                self._next_sorted = next_res.pos[0].sorted_views(next_res.pos[1])
             pf = self._pref
-            if (self._cur_sorted is not None and pf is not None and pf["ptr"] == lS_i.data_ptr()
-                    and pf["shape"] == tuple(lS_i.shape) and not pf.get("sorted_ok")):
+            if self._cur_sorted is not None and pf is not None and pf.matches(lS_i) and not pf.sorted_ok:
                 # this batch's take was issued by the previous step, BEFORE its slice's sort (a chunk resolved late: short chunks):
                 # nothing orders this step behind that sort -- it sorts its own slots
                 self._cur_sorted = None
-            self._wait_slices(self._cur_sorted, self._next_sorted, B, next_idx)
+        main = S.current_stream(self.dev)
+        path = self._step_path(X, lS_i, lS_o, next_idx)
+        # the addresses-and-strides half of a tape's key: no decision, but baked into the recorded arguments
+        pr = self._pending_resolve if self._mark_this else None
+        layout = (getattr(main, "cuda_stream", 0), X.stride(0), lS_i.stride(0), next_idx.stride(0) if path.nxt else 0,
+                  res.slots.stride(0) if (path.resolved and not path.hit) else 0,
+                  self._next_res.slots.stride(0) if path.next_resolved else 0, r.stride(0) if r is not None else 0,
+                  0 if pr is None else pr["cols"].stride(0))
+        self._step_key = (path, layout)
+        if sliced:
+            self._wait_slices(path, self._cur_sorted, self._next_sorted)
         if res is not None:
             # an in-line take (no prefetched result for this batch) runs on the side stream: behind the chunk's resolve
-            self.side.wait_event(res[2])
-        if self._next_res is not None and next_res[2] is not (res[2] if res is not None else None):
+            self.side.wait_event(res.ready)
+        if self._next_res is not None and next_res.ready is not (res.ready if res is not None else None):
             # the next batch's take may run on the side stream too (single aux region / chained take): behind ITS chunk
-            self.side.wait_event(next_res[2])
-        if self.use_tape and lS_o is None and not self.evict_victim:
-            sgd_done = self._step_taped(X, lS_i, T, next_idx)
+            self.side.wait_event(next_res.ready)
+        if self.use_tape and sliced:
+            sgd_done = self._step_taped(path, layout, X, lS_i, T, next_idx)
         else:
-            sgd_done = self._fwd_bwd(X, lS_i, T, lS_o, gather_events, next_idx)
+            sgd_done = self._fwd_bwd(path, X, lS_i, T, lS_o, next_idx)
         if self.evict_victim:
             # on the side stream, behind the embedding update _fwd_bwd issued there and in front of the next step's take
             if n not in self._vwb_work:
                 self._vwb_work[n] = ops.victim_writeback_work(self.ctx, n)
-            ops.victim_writeback(self.ctx, lS_i, self._last_slots, res[1] if (res is not None and lS_o is None) else None,
+            ops.victim_writeback(self.ctx, lS_i, self._last_slots, res.src if (res is not None and lS_o is None) else None,
                                  self._last_phase, self._vwb_work[n], stream=self.side)
         if self._mark_this:
             self._pending_resolve = None        # issued by this step
@@ -1470,7 +1630,7 @@ class TrainEngine:
             else:
                 ops.scale_div(gb, W)
                 dist.all_reduce(gb, op=dist.ReduceOp.SUM, group=self.pg)
-            if next_idx is None or not (self._side_gather(B) and self.ctx.aux_phases >= 2):
+            if path.join == "emb_done":
                 S.current_stream(self.dev).wait_event(self._events["emb_done"])
             ops.sgd_step2(self.param_flat, self.grad_flat, *self.rng_bot, self.lr)
             sgd_done = True
@@ -1501,8 +1661,9 @@ class TrainEngine:
         self.iter += 1
         return self._buffers(B)["loss"]
 
-    def _fwd_bwd(self, X, lS_i, T, lS_o, gather_events, next_idx=None):
-        """Forward + backward of one iteration up to: all dense gradients in grad_flat, cache rows updated."""
+    def _fwd_bwd(self, path: StepPath, X, lS_i, T, lS_o, next_idx=None):
+        """Forward + backward of one iteration up to: all dense gradients in grad_flat, cache rows updated.  Every branch that
+        depends on the step reads `path`."""
         ctx, cg = self.ctx, self.cg
         B = X.shape[0]
         n = lS_i.shape[1]
@@ -1517,34 +1678,22 @@ class TrainEngine:
         main = S.current_stream(self.dev)
         side = self.side
         ev = self._events
-        two_phase = ctx.aux_phases >= 2
-        # Long batches with the window-resident probe: the next batch's take costs ~10 us stand-alone, so it no longer needs
-        # a stream and an aux region of its own (that pipeline hid 250 us of PCIe reads).  It follows this step's embedding
-        # update in order on the side stream, and ONE event recorded there -- after the take and, on one rank, after the
-        # deferred top-MLP update -- is all the next step's gather waits for: the main queue carries one wait per step
-        # instead of three (probe, top update, embedding update) plus a record, each a 6-8 us bubble (measured).
-        chain = self._chain(B, next_idx, lS_o)
-        if chain:
-            two_phase = False
         if self.defer_top and self.cat:
             # the previous step's top weight gradients read R = the feature block this step's first kernels overwrite
             rec(main.wait_event, ev["top_updated"])
         pref, self._pref = self._pref, None
-        top_waited = prepared = False
-        if pref is not None and pref["ptr"] == lS_i.data_ptr() and pref["shape"] == tuple(lS_i.shape):
-            slots, miss_pos, miss_count, probed = pref["res"]
-            self._phase = pref["phase"]
-            top_waited = bool(pref.get("chained_top"))
-            prepared = bool(pref.get("prepared"))
+        top_waited = path.top_waited
+        self._phase = path.phase
+        if path.hit:
+            (slots, miss_pos, miss_count), probed = pref.out, pref.probed
         else:
             rec(side.wait_stream, main)
-            slots, miss_pos, miss_count = self._take(lS_i, self._res if lS_o is None else None, self._phase, self._phase, side)
+            slots, miss_pos, miss_count = self._take(lS_i, self._res if path.resolved else None, self._phase, self._phase, side)
             probed = ev["probed_inline"]
             rec(probed.record, side)
-        n_bags = B if lS_o is None else lS_o.shape[1]
         self._last_slots, self._last_phase = slots, self._phase          # (ops.victim_writeback reads them behind the step)
 
-        fused = self._fused_gather(lS_o)
+        fused = path.fused
 
         def gather(st):
             if fused:       # the rows are the interaction kernel's operand loads: nothing to launch here
@@ -1552,14 +1701,14 @@ class TrainEngine:
             if self.qr is not None:
                 ops.qr_cached_fwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, feat[:, 1:, :], feat.stride(0), D, stream=st)
                 return
-            if self._gslot is not None:         # bench.py: the roofline kernel's own start / stop timestamps
+            if path.timed:                      # bench.py: the roofline kernel's own start / stop timestamps
                 ops.time_next_gather(ctx, self._gslot[0], self._gslot[1])
-            ops.embbag_fwd(ctx, slots, lS_o, feat[:, 1:, :], feat.stride(0), D, n_bags=n_bags, stream=st)
+            ops.embbag_fwd(ctx, slots, lS_o, feat[:, 1:, :], feat.stride(0), D, n_bags=path.n_bags, stream=st)
 
         # Short local batches: the gather (6 us at 1024) goes to the SIDE stream, beside the bottom MLP's forward -- it
         # needs the probe result and the previous step's embedding update, which ran on that very stream (in order: no
         # event), not the bottom MLP.  Long batches: it is the HBM-roofline kernel and runs alone on the main stream.
-        side_gather = self._side_gather(B)
+        side_gather = path.side_gather
         if side_gather:
             rec(side.wait_event, probed)
             if self.defer_top and not self.cat and not top_waited:
@@ -1584,58 +1733,48 @@ class TrainEngine:
             # the gather runs alone on the main stream (it is the HBM-roofline kernel: nothing competes for bandwidth)
             rec(main.wait_event, probed)
             gather(main)
-        if next_idx is not None and two_phase:
+        if path.nxt and path.two_phase:
             # Software pipelining across iterations: the NEXT batch's tag probe and aux-row fill (~0.25 ms of PCIe
             # reads at c3) start right behind this batch's gather, on their own stream, into the OTHER aux region
             # (this batch still reads and updates its own aux rows).  The other region was last used by the previous
             # batch: its embedding update must have landed (emb_done).
             pst = self.pref
-            if B >= self.gather_alone_min:
+            if path.gather_alone:
                 # long batches: the gather is the HBM-roofline kernel and runs alone; the probe starts behind it
                 ev_g = ev["gathered"]
                 rec(ev_g.record, main)
                 rec(pst.wait_event, ev_g)
             # short batches: every event recorded on the main queue costs a ~6 us bubble there (measured), more than the
             # probe could take from a 6 us gather -- it starts as soon as the other aux region is free
-            if self._emb_done is not None:
-                rec(pst.wait_event, self._emb_done)
-            ph = 1 - self._phase
-            res = self._take(next_idx, self._next_res, ph, ph, pst)
-            evp = ev["probed"][ph]
-            rec(evp.record, pst)
-            self._pref = dict(ptr=next_idx.data_ptr(), shape=tuple(next_idx.shape), phase=ph,
-                              res=(res[0], res[1], res[2], evp), sorted_ok=self._next_sorted is not None)
+            if path.emb_done_seen:
+                rec(pst.wait_event, ev["emb_done"])
+            self._pref = self._hand_over(path, next_idx, 1 - self._phase, pst)
+            rec(self._pref.probed.record, pst)
         # the backward's sort of the slot ids needs nothing but the probe result: run it on the side, under the MLPs
         emb_work = self._emb_work(n)
         if not side_gather:
             rec(side.wait_event, probed)
-        attach = self.attach_events and S.is_hip(self.dev)
-        # sv: this batch's slot lists were sorted with its look-ahead chunk (WindowResolver.ensure_sorted): no sort here, and the
-        # once-only slots can be updated by the interaction backward (it reads the sort's flags)
-        # (the flags of a batch's OWN sort would cost the training queue a wait for the side stream in front of the interaction
-        #  backward: measured 21 us, three times what the folding saves)
-        sv = self._cur_sorted if (lS_o is None and n == B) else None
-        once = bool(self.fuse_once and fused and sv is not None)
-        if sv is None and not prepared:     # (prepared: a chained take sorted this batch's slots right behind itself)
+        attach = path.attach
+        sv = self._cur_sorted if path.sorted is not None else None      # (path.sorted: no sort here)
+        once = path.once
+        if sv is None and not path.prepared:     # (prepared: a chained take sorted this batch's slots right behind itself)
             ops.embbag_bwd_prepare(ctx, slots, emb_work, stream=side)
         if self.defer_top and not self.cat and not top_waited:
             # the previous step's top-MLP update (weight gradients read R / top_y / top_dy, then all-reduce and SGD on
             # the side stream) has to have landed before this step overwrites those buffers and reads the weights
             # (top_waited: the event this step's gather waited for was recorded behind that update)
             rec(main.wait_event, ev["top_updated"])
-        self._fwd_marked = False
         if fused:
-            if self._gslot is not None:         # bench.py: the kernel that does the gather, timed by its own launch
+            if path.timed:                      # bench.py: the kernel that does the gather, timed by its own launch
                 ops.time_next_gather(ctx, self._gslot[0], self._gslot[1])
-            if attach and self._mark_this:
+            if path.fwd_marked:
                 # the placed resolve (prefetch stream) waits for an event that completes WITH this launch
                 ops.event_attach_next(ev["fwd_mark"], main)
-                self._fwd_marked = True
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         elif not self.cat:
             ops.interact_fwd(feat, self.itself, R)
-        if self._mark_this:
-            self._issue_resolve(self._pending_resolve, rec, main, placed=True)
+        if path.resolve_cols is not None:
+            self._issue_resolve(self._pending_resolve, rec, main, placed=path)
         cur = R
         top_acts = [R]
         fused_head = self.fused_head
@@ -1665,7 +1804,7 @@ class TrainEngine:
                              dX[:, :l.in_features], buf["loss"], self._head_scratch,
                              x_act=(self.top[-2][1] if n_top > 1 else 0), kind=self.loss_kind,
                              weights=self.loss_weights, threshold=self.loss_threshold, Zc=buf["Zc"], finish=False)
-            if self.loss_sync:      # partial sums -> loss, running statistics: here, or on the side stream below
+            if path.loss_sync:      # partial sums -> loss, running statistics: here, or on the side stream below
                 ops.head_finish(self._head_scratch, B, buf["loss"], acc=self.stat_acc)
             dY = dX
         else:
@@ -1714,7 +1853,7 @@ class TrainEngine:
             if attach:
                 ops.event_attach_next(ev["interacted"], main)      # completes with the interaction backward's launch
             if once:
-                ops.gather_interact_bwd_sgd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, sv[2], sv[3], self.lr_embeds,
+                ops.gather_interact_bwd_sgd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, sv.once, sv.stride, self.lr_embeds,
                                             x_act=self.bot[-1][1])
             elif fused:
                 ops.gather_interact_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
@@ -1725,7 +1864,7 @@ class TrainEngine:
         if not attach or self.cat:
             rec(ev["interacted"].record, main)
         rec(side.wait_event, ev["interacted"])
-        if fused_head and not self.loss_sync:
+        if fused_head and not path.loss_sync:
             # the head's partial sums -> loss buffer + running statistics, off the training queue.  The next head kernel
             # overwrites the partials only behind the next gather, which is ordered behind this stream's embedding update
             ops.head_finish(self._head_scratch, B, buf["loss"], stream=side, acc=self.stat_acc)
@@ -1737,7 +1876,7 @@ class TrainEngine:
                               stream=side)
             ops.qr_cached_bwd_finish(ctx, self.qr_coll, n, qw, self.lr_embeds, self.Wr, stream=side)
         if sv is not None:
-            ops.embbag_bwd_apply_sorted(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work, sv[0], sv[1], sv[3],
+            ops.embbag_bwd_apply_sorted(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work, sv.keys, sv.meta, sv.stride,
                                         self._phase, once, cg.touched if self.multi else None, stream=side)
         else:
             ops.embbag_bwd_apply(ctx, n, lS_o, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work,
@@ -1745,23 +1884,16 @@ class TrainEngine:
         emb_done = ev["emb_done"]
         rec(emb_done.record, side)
         self._emb_done = emb_done
-        if next_idx is not None and not two_phase:
+        if path.nxt and not path.two_phase:
             # single aux region: the next batch's fill can only follow this batch's embedding update
-            which = 2 + (self.iter & 1)
-            res = self._take(next_idx, self._next_res, 0, which, side)
-            chain_sort = chain and self._next_sorted is None
-            if chain_sort:
+            self._pref = self._hand_over(path, next_idx, 0, side)
+            if path.chain_sort:
                 # ... and the sort of the next batch's slot ids for ITS backward: here it ends well before the step does; issued
                 # at the head of the next step it shared HBM with that step's gather (the roofline kernel)
-                ops.embbag_bwd_prepare(ctx, res[0], emb_work, stream=side)
-            chained_top = chain and sgd_in_wgrad and split is not None
-            if chained_top:
+                ops.embbag_bwd_prepare(ctx, self._pref.out[0], emb_work, stream=side)
+            if path.chained_top:
                 rec(side.wait_event, ev["top_updated"])     # recorded above, behind this step's top-MLP SGD
-            evp = ev["probed"][which]
-            rec(evp.record, side)
-            self._pref = dict(ptr=next_idx.data_ptr(), shape=tuple(next_idx.shape), phase=0,
-                              res=(res[0], res[1], res[2], evp), chained_top=chained_top, prepared=chain_sort,
-                              sorted_ok=self._next_sorted is not None)
+            rec(self._pref.probed.record, side)
         dY = dfeat[:, 0, :]
         for i in reversed(range(1, len(self.bot))):         # layer 0 has no input gradient
             l, act = self.bot[i]
@@ -1779,16 +1911,11 @@ class TrainEngine:
             plan.set_x(0, X)
             ops.mlp_wgrad(plan)
         if self.multi:
-            return False # step() joins AFTER it has issued the gradient all-reduce: the exchange overlaps the embedding update
-        if next_idx is None:
-            rec(main.wait_stream, side)      # full join
-        elif chain:
-            pass                             # the next gather waits for the take's event, recorded behind emb_done
-        elif not (side_gather and two_phase):
-            rec(main.wait_event, emb_done)   # cache rows are updated; the prefetched probe keeps running
-        # else: the next step's gather runs on the side stream, in order behind this embedding update, and its probe waits
-        # for emb_done on its own stream -- nothing on the main stream reads the cache rows before the next full join
-        # (window boundary, row merge, evaluate(), finish()), so the main queue is spared one more wait (6-8 us bubble)
+            return False        # step() joins behind the gradient all-reduce it issues
+        if path.join == "full":
+            rec(main.wait_stream, side)
+        elif path.join == "emb_done":
+            rec(main.wait_event, emb_done)
         return split is not None and sgd_in_wgrad
 
     # ----------------------------------------------------------------------------------------------
@@ -1810,11 +1937,11 @@ class TrainEngine:
             raise RuntimeError("evaluate(): a row merge is still draining; every rank has to call drain_merge() first")
         self.finish()
         pend = self._pref
-        if pend is not None and pend["phase"] == self._phase:
+        if pend is not None and pend.phase == self._phase:
             # the next training batch's take already filled THIS aux region (single-region / chained take: the long-batch
             # default): wait for it, let the test batch overwrite the region, and drop the prefetched result -- the next
             # step() then takes (and sorts) its batch again in line
-            S.current_stream(self.dev).wait_event(pend["res"][3])
+            S.current_stream(self.dev).wait_event(pend.probed)
             self._pref = None
         buf = self._buffers(B)
         feat, R = buf["feat"], buf["R"]
@@ -1866,44 +1993,28 @@ class TrainEngine:
         buf = self._buffers(B)
         return buf["Zc"] if buf["Zc"] is not None else buf["top_y"][-1]
 
-    def _step_taped(self, X, lS_i, T, next_idx):
+    def _step_taped(self, path: StepPath, layout, X, lS_i, T, next_idx):
         """The same launch sequence as _fwd_bwd, replayed from a recording.  At small local batches the ~30 launches
         of a step take less GPU time than the Python around them (argument marshalling, stream lookups): the first
-        step of each control path (batch shape, aux phase, prefetched or in-line probe, next batch handed over or
-        not) runs _fwd_bwd under `_lib.start_recording`, later ones re-issue the recorded (function, arguments)
-        list.  Pointers that change from step to step (X, T, the index tensors) are shared ctypes cells patched before
-        each replay; everything else the step touches is a preallocated buffer with a fixed address."""
+        step of each control path (StepPath) at each layout runs _fwd_bwd under `_lib.start_recording`, later ones re-issue
+        the recorded (function, arguments) list.  Pointers that change from step to step (X, T, the index tensors) are shared
+        ctypes cells patched before each replay; everything else the step touches is a preallocated buffer with a fixed address."""
         import ctypes as C
-        B, n = X.shape[0], lS_i.shape[1]
+        B = path.B
         main = S.current_stream(self.dev)
-        pref = self._pref
-        hit = pref is not None and pref["ptr"] == lS_i.data_ptr() and pref["shape"] == tuple(lS_i.shape)
-        phase = pref["phase"] if hit else self._phase
-        nxt = next_idx is not None
-        key = (B, n, main.cuda_stream, hit, phase, nxt, self._emb_done is not None, X.stride(0), lS_i.stride(0),
-               next_idx.stride(0) if nxt else 0,
-               (self.iter & 1) if (self.ctx.aux_phases < 2 or self._chain(B, next_idx, None)) else 0,
-               bool(hit and pref.get("chained_top")), bool(hit and pref.get("prepared")),
-               self._gslot is not None, self.loss_sync,
-               (int(self._pending_resolve["cols"].shape[1]), self._pending_resolve["cols"].stride(0)) if self._mark_this else None,
-               self.tape_lanes, self.tape_lanes_below, self.attach_events, self.fuse_gather, self.wide_gemm, self.fuse_once,
-               self.matmul_precision,
-               None if self._cur_sorted is None else self._cur_sorted[3], self._next_sorted is not None,
-               self._res[0].stride(0) if (self._res is not None and not hit) else 0,
-               self._next_res[0].stride(0) if self._next_res is not None else 0,
-               self._r.stride(0) if self._r is not None else 0)
+        key = (path, layout)
         tape = self._tapes.get(key)
         if tape is None:
             calls = []
             _lib.start_recording(calls)
             try:
-                included = self._fwd_bwd(X, lS_i, T, None, None, next_idx)
+                included = self._fwd_bwd(path, X, lS_i, T, None, next_idx)
                 if not self.multi and not included:   # no gradient exchange in between: the dense SGD rides on the tape too
                     ops.sgd_step(self.param_flat, self.grad_flat, self.lr)
             finally:
                 _lib.stop_recording()
             # pointer arguments equal to one of the per-step tensors become shared cells
-            cells = {k: C.c_void_p(v) for k, v in self._tape_ptrs(X, T, lS_i, next_idx, hit).items()}
+            cells = {k: C.c_void_p(v) for k, v in self._tape_ptrs(path, X, T, lS_i, next_idx).items()}
             by_value = {c.value: c for c in cells.values()}
             if len(by_value) != len(cells):
                 return not self.multi      # aliased inputs: stay on the untaped path
@@ -1920,17 +2031,15 @@ class TrainEngine:
                 # the same calls as a C-side tape: one library call per step instead of ~45 interpreted ones (0.22 ms of
                 # host time per step, more than the GPU needs at a per-rank batch of 1024)
                 try:
-                    lanes = self.tape_lanes if B < self.tape_lanes_below else 1
-                    native = _lib.NativeTape(prog, cells, main_stream=main.cuda_stream if lanes > 1 else None, max_lanes=lanes)
+                    native = _lib.NativeTape(prog, cells, main_stream=main.cuda_stream if path.lanes > 1 else None,
+                                             max_lanes=path.lanes)
                 except _lib.TapeUnsupported as e:
                     native = None
                     self.tape_fallbacks.append(str(e))      # this control path replays from Python (bench.py reports it)
-            self._tapes[key] = dict(prog=prog, cells=cells, phase=self._phase, native=native,
-                                    pref=None if post is None else (post["phase"], post["res"], post.get("chained_top", False),
-                                                                    post.get("prepared", False)))
+            self._tapes[key] = dict(prog=prog, cells=cells, native=native, pref=None if post is None else post.stored())
             return not self.multi
         cells = tape["cells"]
-        for k, v in self._tape_ptrs(X, T, lS_i, next_idx, hit).items():
+        for k, v in self._tape_ptrs(path, X, T, lS_i, next_idx).items():
             cells[k].value = v
         bufs = self._buffers(B)
         whole_plan, split = self._wplans(bufs)
@@ -1945,31 +2054,28 @@ class TrainEngine:
                 if is_lib and rc:
                     _lib.check(rc)
         # the state _fwd_bwd leaves behind
-        self._phase = tape["phase"]
+        self._phase = path.phase
         self._emb_done = self._events["emb_done"]
-        self._pref = None
-        if tape["pref"] is not None:
-            self._pref = dict(ptr=next_idx.data_ptr(), shape=tuple(next_idx.shape), phase=tape["pref"][0], res=tape["pref"][1],
-                              chained_top=tape["pref"][2], prepared=tape["pref"][3], sorted_ok=self._next_sorted is not None)
+        self._pref = None if tape["pref"] is None else tape["pref"].handed(next_idx)
         return not self.multi
 
-    def _tape_ptrs(self, X, T, lS_i, next_idx, hit: bool) -> dict:
-        """The per-step pointers a recorded step reads, by cell name (_step_taped): the same names for every step of one control
-        path (its tape key fixes which of them exist)."""
+    def _tape_ptrs(self, path: StepPath, X, T, lS_i, next_idx) -> dict:
+        """The per-step pointers a recorded step reads, by cell name (_step_taped): the path says which of them exist."""
         p = {"X": X.data_ptr(), "T": T.data_ptr(), "idx": lS_i.data_ptr()}
-        if next_idx is not None:
+        if path.nxt:
             p["next"] = next_idx.data_ptr()
-        if self._res is not None and not hit:
-            p["ws"], p["wsrc"] = self._res[0].data_ptr(), self._res[1].data_ptr()
-        if self._next_res is not None:
-            p["nws"], p["nwsrc"] = self._next_res[0].data_ptr(), self._next_res[1].data_ptr()
-        if self._cur_sorted is not None:
-            p["skeys"], p["smeta"], p["sonce"] = self._cur_sorted[:3]
-        if self._gslot is not None:
+        if path.resolved and not path.hit:
+            p["ws"], p["wsrc"] = self._res.slots.data_ptr(), self._res.src.data_ptr()
+        if path.next_resolved:
+            p["nws"], p["nwsrc"] = self._next_res.slots.data_ptr(), self._next_res.src.data_ptr()
+        if path.sorted is not None:
+            sv = self._cur_sorted
+            p["skeys"], p["smeta"], p["sonce"] = sv.keys, sv.meta, sv.once
+        if path.timed:
             p["g0"], p["g1"] = self._gslot[0].handle, self._gslot[1].handle
-        if self._r is not None:         # quotient-remainder mode: the batch's remainder columns
+        if self._r is not None:         # quotient-remainder mode (a constant of the engine): the batch's remainder columns
             p["r"] = self._r.data_ptr()
-        if self._mark_this:             # the placed resolve's chunk: index columns, ring slot, the slot's event
+        if path.resolve_cols is not None:       # the placed resolve's chunk: index columns, ring slot, the slot's event
             pr = self._pending_resolve
             p["rcols"], p["rws"] = pr["cols"].data_ptr(), pr["ws"].data_ptr()
             p["rwsrc"], p["rev"] = pr["wsrc"].data_ptr(), int(pr["ev"].cuda_event)
@@ -1990,7 +2096,7 @@ class TrainEngine:
     MERGE_LOOKAHEAD = 64                            # batches ahead the classes reach (the resolver decides how many are known)
 
     def _pump_start(self, U, buf, scale, rop) -> bool:
-        pos = self._res[3] if (self._res is not None and len(self._res) > 3) else None
+        pos = self._res.pos if self._res is not None else None
         if pos is None:
             return False
         rs, j = pos

@@ -147,7 +147,7 @@ def test_chained_take_at_long_batches(golden, name, defer, chunk, delay):
                 torch.cuda._sleep(2_500_000)
         loss = eng.step(X.to(DEV), dev_idx[j], Tt.to(DEV), j=j, next_idx=nxt, res=rs.batch(j % L),
                         next_res=rs.batch(j % L + 1) if nxt is not None else None)
-        chained += int(eng._pref is not None and bool(eng._pref.get("chained_top")) == (defer and eng.world == 1))
+        chained += int(eng._pref is not None and bool(eng._pref.chained_top) == (defer and eng.world == 1))
         rs.ensure(j % L + rs.CH + 2)
         losses.append(loss[0:1].clone())
     eng.finish()

@@ -345,7 +345,7 @@ def test_window_resolver_sorts_slices_ahead_of_their_steps(monkeypatch, CH, SL, 
         r = rs.batch(j)
         if j + 1 < nb:
             rs.batch(j + 1)
-        v = r[3][0].sorted_views(r[3][1])
+        v = r.pos[0].sorted_views(r.pos[1])
         if j in first_sorted:
             assert v is not None and v[2] == j % CH, (j, v)
         else:
@@ -394,18 +394,17 @@ def test_slice_waits_tell_slices_apart_by_serial(monkeypatch):
             self.pref, self.side, self.sort_st = Stream(), Stream(), S._NullStream()
             self._next_waited = self._cur_waited = 0
 
-        def _chain(self, B, next_idx, lS_o):        # two aux regions: the next batch's take is on the prefetch stream
-            return False
-
     B, CH = 8192, 4
     nb = (engine.WindowResolver.RING + 2) * CH
+    # two aux regions: the next batch's take is on the prefetch stream
+    two_regions = engine.StepPath._make([None] * len(engine.StepPath._fields))._replace(two_phase=True)
     eng = Eng()
     rs = engine.WindowResolver(eng, torch.zeros(2, nb * B, dtype=torch.int64), B, chunk=CH)
     assert rs.SL == 2
 
     def step_waits(cur, nxt):           # (the resolver's own waits on the prefetch stream are not the step's)
         np_, ns = len(eng.pref.waits), len(eng.side.waits)
-        eng._wait_slices(cur, nxt, B, None)
+        eng._wait_slices(two_regions, cur, nxt)
         return eng.pref.waits[np_:], eng.side.waits[ns:]
 
     waits, last = [], None

@@ -30,7 +30,8 @@ torch.cuda.synchronize()
 ctx = eng.ctx
 T = win.shape[0]
 for j in (0, 7, 33):
-    ws, wsrc, ev = res.batch(j)
+    r = res.batch(j)
+    ws, wsrc = r.slots, r.src
     idx = win[:, j * B:(j + 1) * B]
     slots = torch.empty(T, B, dtype=torch.int32, device=dev)
     ops.embbag_take(ctx, idx, ws, wsrc, slots, aux_phase=0)
