@@ -88,6 +88,9 @@ PROTOTYPES = {
     "cdlrm_embbag_bwd_prepare_window": (C.c_int, [vp, vp, c_i64, c_i64, c_i32, c_i64, c_i32, c_i32, vp, vp]),
     "cdlrm_embbag_bwd_sorted_views": (C.c_int, [vp, vp, c_i32, c_i64, c_i32, vp, vp, vp]),
     "cdlrm_embbag_bwd_apply_sorted": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, c_f32, vp, vp, vp, c_i64, c_i32, c_i32, vp, vp]),
+    "cdlrm_embbag_bwd_apply_opt": (C.c_int, [vp, vp, c_i64, c_i64, c_i64, vp, c_i64, c_i64, c_f32, vp, vp, c_i32, c_f32, vp, vp, vp]),
+    "cdlrm_embbag_bwd_apply_sorted_opt": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, c_f32, vp, vp, vp, c_i64, c_i32, c_i32, vp, c_i32,
+                                                    c_f32, vp, vp, vp]),
     "cdlrm_embbag_bwd_route": (C.c_int, [c_i32, c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, C.POINTER(EmbBwdRoute)]),
     "cdlrm_qr_embbag_fwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp, vp, vp]),
     "cdlrm_qr_embbag_bwd": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, c_i64, c_i32, c_i32, c_i32, vp, vp, vp]),

@@ -623,6 +623,442 @@ __global__ void __launch_bounds__(256) k_bwd_long(const TableDesc* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Row-wise Adagrad (opt-in: cdlrm_embbag_bwd_apply_opt / _apply_sorted_opt, opt = CDLRM_EMB_OPT_ROWWISE_ADAGRAD).
+// Sibling kernels of k_bwd_chunks / k_bwd_blocks / k_bwd_long: the same sums in the same order (a run's G is bit for bit what
+// the SGD kernels multiply by -lr), and where those write a row these do, per run of a CACHE-PROPER slot s of table t,
+//     i = tags[s];  S[i] += (1/D) sum_d G_d^2;  W[s] -= lr * G / (sqrt(S[i]) + eps)
+// S: one fp32 per TABLE row (state + state_base[t] + i), indexed by the tag of the slot, so it never moves with a row.  A slot
+// is one run and a run has one owning lane group: S[i] is read and written once per launch, without atomics.  Aux slots (misses:
+// transient copies, rewritten by the next forward) are skipped -- no row write, no state update.
+// A lane keeps the NCH = ceil(D4 / LPR) column chunks it owns in registers until the row's sum of squares is known (NCH > 1 only
+// at LPR = 64, D > 256); the sum is reduced over the lane group by a fixed xor butterfly: every lane ends with the same bits.
+// The SGD kernels above are untouched.
+struct AdaArgs {
+    const int64_t* tags;
+    float* state;
+    const int64_t* state_base;      // device [T]: first accumulator of table t
+    float eps;
+};
+
+// the accumulator cell of slot `slot` of table t; -1: an aux slot, or a tag that names no row of the table (an empty way: nothing
+// the batch can have looked up) -- the run is then left alone
+__device__ __forceinline__ int64_t ada_cell(const TableDesc* __restrict__ tab, int t, const AdaArgs& o, uint32_t slot,
+                                            uint32_t aux0, int ways) {
+    if (slot >= aux0) return -1;
+    const uint32_t P = (uint32_t)tab[t].P;          // slot = P * way + set; tags are [P, ways]
+    const uint32_t way = slot / P, set = slot - way * P;
+    const int64_t i = o.tags[tab[t].tag_base + (int64_t)set * ways + way];
+    return (uint64_t)i < (uint64_t)tab[t].n_rows ? o.state_base[t] + i : -1;
+}
+
+// S_new and the rows' step from the run sums g (zero in chunks past D4) -- called by ALL lanes of the group
+template <int LPR, int NCH>
+__device__ __forceinline__ float ada_step(float4 (&w)[NCH], const float4 (&g)[NCH], float s_old, float lr, float eps, int D4) {
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        ss = fmaf(g[k].x, g[k].x, ss); ss = fmaf(g[k].y, g[k].y, ss);
+        ss = fmaf(g[k].z, g[k].z, ss); ss = fmaf(g[k].w, g[k].w, ss);
+    }
+#pragma unroll
+    for (int m = LPR >> 1; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+    const float s_new = s_old + ss / (float)(4 * D4);
+    const float scale = lr / (sqrtf(s_new) + eps);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        w[k].x = fmaf(-scale, g[k].x, w[k].x); w[k].y = fmaf(-scale, g[k].y, w[k].y);
+        w[k].z = fmaf(-scale, g[k].z, w[k].z); w[k].w = fmaf(-scale, g[k].w, w[k].w);
+    }
+    return s_new;
+}
+
+template <int LPR, bool ARANGE, int NCH>
+__global__ void __launch_bounds__(256) k_bwd_chunks_ada(const TableDesc* __restrict__ tab, int D4,
+                                                        float4* __restrict__ weight, const uint64_t* __restrict__ keys,
+                                                        const int32_t* __restrict__ meta,
+                                                        const int64_t* __restrict__ offsets, int64_t n, int64_t n_bags,
+                                                        int64_t ld_off, const float* __restrict__ grad, int64_t ld_bag,
+                                                        int64_t ld_table, float lr, float4* __restrict__ partials,
+                                                        int64_t pstride, int64_t* __restrict__ longlist,
+                                                        int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
+                                                        int32_t* __restrict__ runend, int64_t kstride,
+                                                        int ways, int aux_add, AdaArgs o) {
+    constexpr int KM = (SEG_CH + LPR - 1) / LPR;
+    const int t = blockIdx.y;
+    const int64_t row_base = tab[t].row_base;
+    const int c = threadIdx.x % LPR;
+    const int gpb = blockDim.x / LPR;
+    const int gid = threadIdx.x / LPR;
+    const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
+    const uint64_t* kt = keys + (int64_t)t * kstride;
+    const int32_t* mt = meta + (int64_t)t * kstride;
+    const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
+    const float* g = grad + (int64_t)t * ld_table;
+    const int64_t* off = ARANGE ? nullptr : offsets + (int64_t)t * ld_off;
+    for (int64_t p = (int64_t)blockIdx.x * gpb + gid; p < n; p += (int64_t)gridDim.x * gpb) {
+        const int r0 = mt[p];
+        if (r0 % SEG_CH) continue;
+        const bool head = r0 == 0;
+        uint32_t slot = (uint32_t)(kt[p] >> 32);
+        if (slot >= aux0) slot += aux_add;
+        int jstop = SEG_CH;
+#pragma unroll
+        for (int m = KM - 1; m >= 0; --m) {
+            const int j = c + m * LPR;
+            const int64_t q = p + 1 + j;
+            const bool stop = (j < SEG_CH) && (q >= n || mt[q] == 0);
+            const unsigned long long b = __ballot(stop);
+            const unsigned long long bits = LPR == 64 ? b : ((b >> gshift) & ((1ull << LPR) - 1));
+            if (bits) jstop = m * LPR + (__ffsll((long long)bits) - 1);
+        }
+        const bool more = jstop == SEG_CH;
+        const int len = more ? SEG_CH : jstop + 1;
+        const bool single = head && !more;
+        // tag -> accumulator -> row: issued early, consumed after the sums
+        const int64_t cell = single ? ada_cell(tab, t, o, slot, aux0, ways) : -1;
+        const float s_old = cell >= 0 ? o.state[cell] : 0.f;
+        float4 w[NCH], acc[NCH];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            const int cc = c + k * LPR;
+            acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            w[k] = acc[k];
+            if (cc >= D4) continue;
+            if (cell >= 0) w[k] = weight[(row_base + slot) * D4 + cc];
+            int q = 0;
+            for (; q + 4 <= len; q += 4) {
+                int64_t bag[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int64_t pos = (int64_t)(kt[p + q + u] & 0xffffffffull);
+                    bag[u] = ARANGE ? pos : bag_of(off, n_bags, pos);
+                }
+                float4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(g + bag[u] * ld_bag + cc * 4);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
+            }
+            for (; q < len; ++q) {
+                const int64_t pos = (int64_t)(kt[p + q] & 0xffffffffull);
+                const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
+                const float4 v = *reinterpret_cast<const float4*>(g + bag * ld_bag + cc * 4);
+                acc[k].x += v.x; acc[k].y += v.y; acc[k].z += v.z; acc[k].w += v.w;
+            }
+            if (!single) {
+                const int64_t pi = 2 * (p / SEG_CH) + (head ? 1 : 0);
+                partials[((int64_t)t * pstride + pi) * D4 + cc] = acc[k];
+            }
+        }
+        if (cell >= 0) {        // (uniform over the lane group)
+            const float s_new = ada_step<LPR, NCH>(w, acc, s_old, lr, o.eps, D4);
+#pragma unroll
+            for (int k = 0; k < NCH; ++k)
+                if (c + k * LPR < D4) weight[(row_base + slot) * D4 + c + k * LPR] = w[k];
+            if (c == 0) o.state[cell] = s_new;
+        }
+        if (c == 0) {
+            if (single) {
+                if (touched && cell >= 0) touched[row_base + slot] = 1;
+            } else if (head) {
+                const int li = atomicAdd(longcount, 1);
+                longlist[li] = ((int64_t)t << 40) | p;
+            }
+            if (!single && !more) runend[(int64_t)t * n + (p - r0)] = (int32_t)(p + len);
+        }
+    }
+}
+
+// k_bwd_blocks' two forms (a lone head with RA rows in flight; up to HU heads with four rows each), with the Adagrad epilogue
+template <int LPR, bool ARANGE, int NCH, int HU = 4, int RA = 16>
+__global__ void __launch_bounds__(256) k_bwd_blocks_ada(const TableDesc* __restrict__ tab, int D4,
+                                                        float4* __restrict__ weight, const uint64_t* __restrict__ keys,
+                                                        const int32_t* __restrict__ meta,
+                                                        const int64_t* __restrict__ offsets, int64_t n, int64_t n_bags,
+                                                        int64_t ld_off, const float* __restrict__ grad, int64_t ld_bag,
+                                                        int64_t ld_table, float lr, float4* __restrict__ partials,
+                                                        int64_t pstride, int64_t* __restrict__ longlist,
+                                                        int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
+                                                        int32_t* __restrict__ runend, int64_t kstride, int ways, int aux_add,
+                                                        AdaArgs o) {
+    constexpr int GPB = 256 / LPR;
+    constexpr int SPAN = 2 * SEG_CH;
+    constexpr int NL = SPAN / LPR;
+    static_assert(SEG_CH == 32 && SPAN % LPR == 0, "masks below are 32 / 64 bits wide");
+    __shared__ uint32_t s_pos[GPB][SPAN];
+    __shared__ uint32_t s_slot[GPB][SEG_CH];
+    __shared__ int32_t s_r0[GPB][SEG_CH];
+    const int t = blockIdx.y;
+    const int64_t row_base = tab[t].row_base;
+    const int c = threadIdx.x % LPR;
+    const int gid = threadIdx.x / LPR;
+    const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
+    const uint64_t* kt = keys + (int64_t)t * kstride;
+    const int32_t* mt = meta + (int64_t)t * kstride;
+    const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
+    const float* g = grad + (int64_t)t * ld_table;
+    const int64_t* off = ARANGE ? nullptr : offsets + (int64_t)t * ld_off;
+    const int64_t nblk = (n + SEG_CH - 1) / SEG_CH;
+    for (int64_t blk = (int64_t)blockIdx.x * GPB + gid; blk < nblk; blk += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = blk * SEG_CH;
+        uint64_t S = 0;
+        uint32_t H = 0;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int m = 0; m < NL; ++m) {
+            const int j = c + m * LPR;
+            const int64_t q = p0 + j;
+            const bool in = q < n;
+            const uint64_t key = in ? kt[q] : 0ull;
+            const int32_t r = in ? mt[q] : 0;
+            s_pos[gid][j] = (uint32_t)key;
+            if (j < SEG_CH) {
+                uint32_t slot = (uint32_t)(key >> 32);
+                if (slot >= aux0) slot += aux_add;
+                s_slot[gid][j] = slot;
+                s_r0[gid][j] = r;
+            }
+            const unsigned long long b = __ballot(r == 0);
+            const unsigned long long bits = LPR == 64 ? b : ((b >> gshift) & ((1ull << LPR) - 1));
+            S |= bits << (m * LPR);
+            if (m * LPR < SEG_CH) {
+                const unsigned long long hb = __ballot(in && j < SEG_CH && (r % SEG_CH) == 0);
+                const unsigned long long hbits = LPR == 64 ? hb : ((hb >> gshift) & ((1ull << LPR) - 1));
+                H |= (uint32_t)(hbits << (m * LPR));
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        const int64_t pbucket = (int64_t)t * pstride + 2 * blk;
+        while (H) {
+            const bool alone = (H & (H - 1)) == 0;
+            if (alone) {
+                const int j = __ffs((int)H) - 1;
+                H = 0;
+                const uint64_t rest = S >> (j + 1);
+                const int nxt = rest ? (__ffsll((long long)rest) - 1) : 64;
+                const bool more = nxt >= SEG_CH;
+                const int len = more ? SEG_CH : nxt + 1;
+                const bool head = (S >> j) & 1;
+                const bool single = head && !more;
+                const uint32_t slot = s_slot[gid][j];
+                const int64_t cell = single ? ada_cell(tab, t, o, slot, aux0, ways) : -1;
+                const float s_old = cell >= 0 ? o.state[cell] : 0.f;
+                float4 w[NCH], acc[NCH];
+#pragma unroll
+                for (int k = 0; k < NCH; ++k) {
+                    const int cc = c + k * LPR;
+                    acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    w[k] = acc[k];
+                    if (cc >= D4) continue;
+                    if (cell >= 0) w[k] = weight[(row_base + slot) * D4 + cc];
+                    for (int q = 0; q < len; q += RA) {
+                        float4 v[RA];
+#pragma unroll
+                        for (int u = 0; u < RA; ++u)
+                            if (q + u < len) {
+                                const int64_t pos = s_pos[gid][j + q + u];
+                                const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
+                                v[u] = *reinterpret_cast<const float4*>(g + bag * ld_bag + cc * 4);
+                            }
+#pragma unroll
+                        for (int u = 0; u < RA; ++u)
+                            if (q + u < len) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
+                    }
+                    if (!single) partials[(pbucket + (head ? 1 : 0)) * D4 + cc] = acc[k];
+                }
+                if (cell >= 0) {
+                    const float s_new = ada_step<LPR, NCH>(w, acc, s_old, lr, o.eps, D4);
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k)
+                        if (c + k * LPR < D4) weight[(row_base + slot) * D4 + c + k * LPR] = w[k];
+                    if (c == 0) o.state[cell] = s_new;
+                }
+                if (c == 0) {
+                    const int64_t p = p0 + j;
+                    if (single) {
+                        if (touched && cell >= 0) touched[row_base + slot] = 1;
+                    } else if (head) {
+                        const int li = atomicAdd(longcount, 1);
+                        longlist[li] = ((int64_t)t << 40) | p;
+                    }
+                    if (!single && !more) runend[(int64_t)t * n + (p - s_r0[gid][j])] = (int32_t)(p + len);
+                }
+                continue;
+            }
+            int hj[HU], hlen[HU];
+            bool hhead[HU], hsingle[HU], hmore[HU];
+            uint32_t hslot[HU];
+            int64_t hcell[HU];
+            float hs[HU];
+            int maxlen = 0;
+#pragma unroll
+            for (int u = 0; u < HU; ++u) {
+                hlen[u] = 0; hj[u] = 0; hhead[u] = false; hsingle[u] = false; hmore[u] = false; hslot[u] = 0; hcell[u] = -1;
+                if (H) {
+                    const int j = __ffs((int)H) - 1;
+                    H &= H - 1;
+                    const uint64_t rest = S >> (j + 1);
+                    const int nxt = rest ? (__ffsll((long long)rest) - 1) : 64;
+                    hmore[u] = nxt >= SEG_CH;
+                    hlen[u] = hmore[u] ? SEG_CH : nxt + 1;
+                    hhead[u] = (S >> j) & 1;
+                    hsingle[u] = hhead[u] && !hmore[u];
+                    hj[u] = j;
+                    hslot[u] = s_slot[gid][j];
+                    maxlen = max(maxlen, hlen[u]);
+                    if (hsingle[u]) hcell[u] = ada_cell(tab, t, o, hslot[u], aux0, ways);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < HU; ++u) hs[u] = hcell[u] >= 0 ? o.state[hcell[u]] : 0.f;
+            float4 w[HU][NCH], acc[HU][NCH];
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                const int cc = c + k * LPR;
+#pragma unroll
+                for (int u = 0; u < HU; ++u) {
+                    acc[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    w[u][k] = acc[u][k];
+                }
+                if (cc >= D4) continue;
+#pragma unroll
+                for (int u = 0; u < HU; ++u)
+                    if (hcell[u] >= 0) w[u][k] = weight[(row_base + hslot[u]) * D4 + cc];
+                for (int q = 0; q < maxlen; q += 4) {
+                    float4 v[HU][4];
+#pragma unroll
+                    for (int u = 0; u < HU; ++u)
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk)
+                            if (q + kk < hlen[u]) {
+                                const int64_t pos = s_pos[gid][hj[u] + q + kk];
+                                const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
+                                v[u][kk] = *reinterpret_cast<const float4*>(g + bag * ld_bag + cc * 4);
+                            }
+#pragma unroll
+                    for (int u = 0; u < HU; ++u)
+#pragma unroll
+                        for (int kk = 0; kk < 4; ++kk)
+                            if (q + kk < hlen[u]) {
+                                acc[u][k].x += v[u][kk].x; acc[u][k].y += v[u][kk].y;
+                                acc[u][k].z += v[u][kk].z; acc[u][k].w += v[u][kk].w;
+                            }
+                }
+#pragma unroll
+                for (int u = 0; u < HU; ++u)
+                    if (hlen[u] != 0 && !hsingle[u]) partials[(pbucket + (hhead[u] ? 1 : 0)) * D4 + cc] = acc[u][k];
+            }
+#pragma unroll
+            for (int u = 0; u < HU; ++u) {
+                if (hcell[u] < 0) continue;
+                const float s_new = ada_step<LPR, NCH>(w[u], acc[u], hs[u], lr, o.eps, D4);
+#pragma unroll
+                for (int k = 0; k < NCH; ++k)
+                    if (c + k * LPR < D4) weight[(row_base + hslot[u]) * D4 + c + k * LPR] = w[u][k];
+                if (c == 0) o.state[hcell[u]] = s_new;
+            }
+            if (c == 0) {
+#pragma unroll
+                for (int u = 0; u < HU; ++u) {
+                    if (hlen[u] == 0) continue;
+                    const int64_t p = p0 + hj[u];
+                    if (hsingle[u]) {
+                        if (touched && hcell[u] >= 0) touched[row_base + hslot[u]] = 1;
+                    } else if (hhead[u]) {
+                        const int li = atomicAdd(longcount, 1);
+                        longlist[li] = ((int64_t)t << 40) | p;
+                    }
+                    if (!hsingle[u] && !hmore[u]) runend[(int64_t)t * n + (p - s_r0[gid][hj[u]])] = (int32_t)(p + hlen[u]);
+                }
+            }
+        }
+    }
+}
+
+template <int LPR, int NCH>
+__global__ void __launch_bounds__(256) k_bwd_long_ada(const TableDesc* __restrict__ tab, int D4,
+                                                      float4* __restrict__ weight, const uint64_t* __restrict__ keys,
+                                                      int64_t n, float lr, const float4* __restrict__ partials,
+                                                      int64_t pstride, const int64_t* __restrict__ longlist,
+                                                      int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
+                                                      const int32_t* __restrict__ runend, int64_t kstride,
+                                                      int ways, int aux_add, AdaArgs o) {
+    const int c = threadIdx.x % LPR;
+    const int gpb = blockDim.x / LPR;
+    const int gid = threadIdx.x / LPR;
+    const int cnt = *longcount;
+    // (the list counter is left zero by the last workgroup through: see k_bwd_long)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int through = atomicAdd(longcount + 2, 1);
+        if (through == (int)gridDim.x - 1) {
+            atomicExch(longcount, 0);
+            atomicExch(longcount + 2, 0);
+        }
+    }
+    for (int li = blockIdx.x * gpb + gid; li < cnt; li += gridDim.x * gpb) {
+        const int64_t e = longlist[li];
+        const int t = (int)(e >> 40);
+        const int64_t p0 = e & (((int64_t)1 << 40) - 1);
+        const uint64_t* kt = keys + (int64_t)t * kstride;
+        uint32_t slot = (uint32_t)(kt[p0] >> 32);
+        const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
+        if (slot >= aux0) slot += aux_add;
+        const int64_t cell = ada_cell(tab, t, o, slot, aux0, ways);
+        if (cell < 0) continue;             // an aux slot's run: its partial sums are dropped
+        const float s_old = o.state[cell];
+        const int64_t end = runend[(int64_t)t * n + p0];
+        const int64_t row = tab[t].row_base + slot;
+        float4 w[NCH], acc[NCH];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            const int cc = c + k * LPR;
+            acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            w[k] = acc[k];
+            if (cc >= D4) continue;
+            w[k] = weight[row * D4 + cc];
+            // chunk partials in chunk order, sixteen then four loads in flight: k_bwd_long's order
+            int64_t p = p0;
+            for (; p + 15 * SEG_CH < end; p += 16 * SEG_CH) {
+                float4 v[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const int64_t q = p + u * SEG_CH;
+                    const int64_t pi = 2 * (q / SEG_CH) + (q == p0 ? 1 : 0);
+                    v[u] = partials[((int64_t)t * pstride + pi) * D4 + cc];
+                }
+#pragma unroll
+                for (int u = 0; u < 16; ++u) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
+            }
+            for (; p + 3 * SEG_CH < end; p += 4 * SEG_CH) {
+                float4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int64_t q = p + u * SEG_CH;
+                    const int64_t pi = 2 * (q / SEG_CH) + (q == p0 ? 1 : 0);
+                    v[u] = partials[((int64_t)t * pstride + pi) * D4 + cc];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
+            }
+            for (; p < end; p += SEG_CH) {
+                const int64_t pi = 2 * (p / SEG_CH) + (p == p0 ? 1 : 0);
+                const float4 v = partials[((int64_t)t * pstride + pi) * D4 + cc];
+                acc[k].x += v.x; acc[k].y += v.y; acc[k].z += v.z; acc[k].w += v.w;
+            }
+        }
+        const float s_new = ada_step<LPR, NCH>(w, acc, s_old, lr, o.eps, D4);
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (c + k * LPR < D4) weight[row * D4 + c + k * LPR] = w[k];
+        if (c == 0) {
+            o.state[cell] = s_new;
+            if (touched) touched[row] = 1;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
 static uint64_t align256(uint64_t v) { return (v + 255) & ~(uint64_t)255; }
@@ -831,6 +1267,8 @@ struct BwdApplyArgs {
     uint8_t* touched;
     int64_t aux_total;
     int skip_once, ways, aux_add;
+    int opt;                    // CDLRM_EMB_OPT_*; ROWWISE_ADAGRAD: the *_ada kernels with `ada`
+    AdaArgs ada;
 };
 
 template <auto Kernel>
@@ -866,7 +1304,48 @@ static void bwd_apply_launch_lpr(const BwdApplyPlan& p, const BwdApplyArgs& a, h
     }
     launch_long<L>(dim3((unsigned)p.long_grid), a, s);
 }
+// the same plan with the row-wise Adagrad kernels: a lane holds NCH column chunks of its row
+template <int L, int NCH>
+static void bwd_apply_launch_ada(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+#define ADA_CHUNKS(AR)                                                                                                       \
+    hipLaunchKernelGGL((k_bwd_chunks_ada<L, AR, NCH>), grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, \
+                       a.n, a.n_bags, a.ld_off, a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist,        \
+                       a.longcount, a.touched, a.runend, a.kstride, a.ways, a.aux_add, a.ada)
+#define ADA_BLOCKS(AR)                                                                                                       \
+    hipLaunchKernelGGL((k_bwd_blocks_ada<L, AR, NCH>), grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, \
+                       a.n, a.n_bags, a.ld_off, a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist,        \
+                       a.longcount, a.touched, a.runend, a.kstride, a.ways, a.aux_add, a.ada)
+    if (p.kernel == CDLRM_BWD_APPLY_CHUNKS) {
+        if (p.arange) ADA_CHUNKS(true);
+        else ADA_CHUNKS(false);
+    } else {                    // (the lean form belongs to the `rest` entries, which take no optimizer)
+        if (p.arange) ADA_BLOCKS(true);
+        else ADA_BLOCKS(false);
+    }
+#undef ADA_CHUNKS
+#undef ADA_BLOCKS
+    hipLaunchKernelGGL((k_bwd_long_ada<L, NCH>), dim3((unsigned)p.long_grid), dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.n,
+                       a.lr, a.partials, a.pstride, a.longlist, a.longcount, a.touched, a.runend, a.kstride, a.ways, a.aux_add,
+                       a.ada);
+}
 static int bwd_apply_launch(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
+    if (a.opt == CDLRM_EMB_OPT_ROWWISE_ADAGRAD) {
+        // column chunks per lane: 1 up to D = 256 (LPR >= D4); 2 / 4 at LPR = 64 (bwd_apply has checked D <= 1024)
+        const int nch = (int)cdiv(a.D4, p.lpr);
+        switch (p.lpr) {
+            case 4: bwd_apply_launch_ada<4, 1>(p, a, s); break;
+            case 8: bwd_apply_launch_ada<8, 1>(p, a, s); break;
+            case 16: bwd_apply_launch_ada<16, 1>(p, a, s); break;
+            case 32: bwd_apply_launch_ada<32, 1>(p, a, s); break;
+            default:
+                if (nch <= 1) bwd_apply_launch_ada<64, 1>(p, a, s);
+                else if (nch == 2) bwd_apply_launch_ada<64, 2>(p, a, s);
+                else bwd_apply_launch_ada<64, 4>(p, a, s);
+        }
+        CDLRM_LAUNCH_CHECK();
+        return 0;
+    }
 #define APPLY_CALL(L) bwd_apply_launch_lpr<L>(p, a, s)
     DISPATCH_LPR(p.lpr, APPLY_CALL)
 #undef APPLY_CALL
@@ -930,8 +1409,16 @@ extern "C" int cdlrm_embbag_bwd_once_flags(cdlrm_ctx* ctx, void* work, int64_t n
 // that cdlrm_embbag_bwd_prepare left in `work` itself; the scratch is `work`'s either way
 static int bwd_apply(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off, const float* grad,
                      int64_t ld_bag, int64_t ld_table, float lr, void* work, const uint64_t* keys, const int32_t* meta,
-                     int64_t kstride, int aux_phase, uint8_t* touched, void* stream, int skip_once) {
+                     int64_t kstride, int aux_phase, uint8_t* touched, void* stream, int skip_once, int opt = CDLRM_EMB_OPT_SGD,
+                     float eps = 0.f, float* state = nullptr, const int64_t* state_base = nullptr) {
     CDLRM_REQUIRE(ctx && grad && work, "null argument");
+    CDLRM_REQUIRE(opt == CDLRM_EMB_OPT_SGD || opt == CDLRM_EMB_OPT_ROWWISE_ADAGRAD, "opt: CDLRM_EMB_OPT_*");
+    if (opt != CDLRM_EMB_OPT_SGD) {
+        CDLRM_REQUIRE(!skip_once, "the `rest` apply follows an SGD step of the once-only slots: it takes no optimizer");
+        CDLRM_REQUIRE(state && state_base && eps > 0.f, "row-wise Adagrad needs its state, state_base and eps > 0");
+        CDLRM_REQUIRE(ctx->tags, "cdlrm_ctx_bind_cache first");
+        CDLRM_REQUIRE(ctx->D <= 1024, "row-wise Adagrad: dim <= 1024 (a lane holds its row's column chunks in registers)");
+    }
     CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
     CDLRM_REQUIRE(((uintptr_t)grad & 15) == 0 && ld_bag % 4 == 0 && ld_table % 4 == 0 && ((uintptr_t)work & 255) == 0,
                   "aligned grad rows / work");
@@ -950,7 +1437,8 @@ static int bwd_apply(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t 
     const BwdApplyArgs a = {ctx->d_tab, ctx->D / 4, reinterpret_cast<float4*>(ctx->weight), keys, meta, kstride, offsets, n, n_bags,
                             ld_off, grad, ld_bag, ld_table, lr, at<float4>(work, l.partials), l.pstride,
                             at<int64_t>(work, l.longlist), at<int32_t>(work, l.longcount), at<int32_t>(work, l.runend), touched,
-                            (int64_t)ctx->aux * ctx->aux_phases, skip_once, ctx->ways, aux_phase * ctx->aux};
+                            (int64_t)ctx->aux * ctx->aux_phases, skip_once, ctx->ways, aux_phase * ctx->aux, opt,
+                            {ctx->tags, state, state_base, eps}};
     return bwd_apply_launch(bwd_apply_plan(ctx->T, ctx->D, n, offsets != nullptr, skip_once != 0), a, (hipStream_t)stream);
 }
 
@@ -978,6 +1466,25 @@ extern "C" int cdlrm_embbag_bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const fl
     CDLRM_REQUIRE(aux_phase >= 0 && aux_phase < (ctx->aux_phases > 0 ? ctx->aux_phases : 1), "aux_phase outside the geometry's aux_phases");
     return bwd_apply(ctx, nullptr, n, n, 0, grad, ld_bag, ld_table, lr, work, keys, meta, tstride, aux_phase, touched, stream,
                      rest ? 1 : 0);
+}
+
+// The two applies that take an optimizer: opt = CDLRM_EMB_OPT_SGD launches exactly the sibling's plan (state unused);
+// CDLRM_EMB_OPT_ROWWISE_ADAGRAD the *_ada kernels on the same plan.
+extern "C" int cdlrm_embbag_bwd_apply_opt(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off,
+                                          const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work,
+                                          uint8_t* touched, int32_t opt, float eps, float* state, const int64_t* state_base,
+                                          void* stream) {
+    return bwd_apply(ctx, offsets, n, n_bags, ld_off, grad, ld_bag, ld_table, lr, work, nullptr, nullptr, 0, 0, touched, stream, 0,
+                     opt, eps, state, state_base);
+}
+extern "C" int cdlrm_embbag_bwd_apply_sorted_opt(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table,
+                                                 float lr, void* work, const uint64_t* keys, const int32_t* meta, int64_t tstride,
+                                                 int32_t aux_phase, int32_t rest, uint8_t* touched, int32_t opt, float eps,
+                                                 float* state, const int64_t* state_base, void* stream) {
+    CDLRM_REQUIRE(ctx && keys && meta && tstride >= n, "null argument / tstride");
+    CDLRM_REQUIRE(aux_phase >= 0 && aux_phase < (ctx->aux_phases > 0 ? ctx->aux_phases : 1), "aux_phase outside the geometry's aux_phases");
+    return bwd_apply(ctx, nullptr, n, n, 0, grad, ld_bag, ld_table, lr, work, keys, meta, tstride, aux_phase, touched, stream,
+                     rest ? 1 : 0, opt, eps, state, state_base);
 }
 
 extern "C" int cdlrm_embbag_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, const int64_t* offsets, int64_t n,

@@ -101,6 +101,7 @@ static const std::vector<TapeEntry>& tape_registry() {
         TAPE_FN(cdlrm_embbag_probe), TAPE_FN(cdlrm_embbag_take), TAPE_FN(cdlrm_embbag_fwd), TAPE_FN(cdlrm_embbag_bwd_sgd),
         TAPE_FN(cdlrm_embbag_bwd_prepare), TAPE_FN(cdlrm_embbag_bwd_apply), TAPE_FN(cdlrm_embbag_bwd_apply_rest),
         TAPE_FN(cdlrm_gather_interact_bwd_sgd), TAPE_FN(cdlrm_embbag_bwd_prepare_window), TAPE_FN(cdlrm_embbag_bwd_apply_sorted),
+        TAPE_FN(cdlrm_embbag_bwd_apply_opt), TAPE_FN(cdlrm_embbag_bwd_apply_sorted_opt),
         TAPE_FN(cdlrm_window_resolve),
         TAPE_FN(cdlrm_qr_split), TAPE_FN(cdlrm_qr_cached_fwd), TAPE_FN(cdlrm_qr_cached_bwd), TAPE_FN(cdlrm_qr_cached_bwd_finish),
         TAPE_FN(cdlrm_mark_rows), TAPE_FN(cdlrm_interact_fwd), TAPE_FN(cdlrm_interact_bwd), TAPE_FN(cdlrm_gather_interact_fwd),

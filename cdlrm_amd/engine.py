@@ -694,6 +694,30 @@ class StepPath(NamedTuple):
     matmul_precision: str
     lr: float
     lr_embeds: float
+    embed_optimizer: str = "sgd"    # the cache rows' update: "sgd" or "rowwise_adagrad" 
+    adagrad_eps: float = 0.0
+
+
+EMBED_OPTIMIZERS = ("sgd", "rowwise_adagrad")
+
+
+def check_embed_optimizer(embed_optimizer: str, adagrad_eps: float, *, world_size: int = 1, qr: bool = False,
+                          evict_victim: bool = False):
+    """What row-wise Adagrad refuses, as one ValueError -- raised by TrainEngine before it touches the GPU and
+    turned into the one ERROR: line by the command line."""
+    if embed_optimizer not in EMBED_OPTIMIZERS:
+        raise ValueError("embed_optimizer=%r: one of %s" % (embed_optimizer, ", ".join(EMBED_OPTIMIZERS)))
+    if embed_optimizer == "sgd":
+        return
+    if not float(adagrad_eps) > 0.0:
+        raise ValueError("adagrad_eps=%r: row-wise Adagrad divides by sqrt(S) + eps and S starts at zero: eps > 0" % (adagrad_eps,))
+    if int(world_size) > 1:
+        raise ValueError("row-wise Adagrad runs on one rank: how the accumulators of rows that the ranks' row merge averages "
+                         "are merged is not defined yet (world_size=%d)" % int(world_size))
+    if qr:
+        raise ValueError("row-wise Adagrad with quotient-remainder tables is not defined: the remainder tables take plain SGD steps")
+    if evict_victim:
+        raise ValueError("row-wise Adagrad skips the aux rows of a batch's misses; --evict-victim-cache writes those rows back")
 
 
 class WindowResolver:
@@ -926,7 +950,8 @@ class TrainEngine:
     def __init__(self, cache_group: Embedding_Table_Cache_Group, dlrm: DLRM_Net, host_tables: Embedding_Table_Group,
                  *, lr: float, lr_embeds: float, world_size: int = 1, rank: int = 0, table_agg_freq: int = 1,
                  table_agg_op: str = "mean", process_group=None, loss: str = "bce", loss_weights=(1.0, 1.0),
-                 defer_top_update: bool = False, force_collectives: bool = False, matmul_precision: str = "fp32"):
+                 defer_top_update: bool = False, force_collectives: bool = False, matmul_precision: str = "fp32",
+                 embed_optimizer: str = "sgd", adagrad_eps: float = 1e-10):
         """loss / loss_weights: --loss-function / --loss-weights (main_no_ddp.py:364-372); the --loss-threshold clamp
         is read from `dlrm.loss_threshold`.
         defer_top_update: the top MLP's weight gradients, their all-reduce and their SGD update leave the critical
@@ -940,7 +965,13 @@ class TrainEngine:
         runs its forward, dgrad and weight-gradient GEMMs on the bf16 matrix cores (operands rounded once to bf16 inside the
         kernels, fp32 accumulation, storage and epilogues: DESIGN.md section 4, "bf16 mode") -- or "bf16x3": the same layers
         with every operand split into two bf16 values and three exact products per product, near-fp32 results (DESIGN.md
-        section 4.2).  A plain attribute: set it between steps and the next step / evaluate() follows it."""
+        section 4.2).  A plain attribute: set it between steps and the next step / evaluate() follows it.
+        embed_optimizer: "sgd" (default: the reference's sparse SGD on the cache rows) or "rowwise_adagrad" with adagrad_eps
+        (DESIGN.md section 4.5): one fp32 accumulator per table row in `emb_state`, indexed by table index; one rank, plain
+        tables, no --evict-victim-cache."""
+        check_embed_optimizer(embed_optimizer, adagrad_eps, world_size=world_size,
+                              qr=getattr(cache_group, "qr", None) is not None)
+        self.embed_optimizer, self.adagrad_eps = embed_optimizer, float(adagrad_eps)
         self.cg, self.dlrm, self.host = cache_group, dlrm, host_tables
         self.ctx = cache_group.ctx
         self.dev = cache_group.weight.device
@@ -972,6 +1003,13 @@ class TrainEngine:
         self.Wr = self._r = None
         if self.qr is not None:
             self._init_qr(host_tables)
+        # row-wise Adagrad's accumulators: one fp32 per TABLE row, table k's n_k from state_base[k] on; zero at the start, in HBM
+        # for the whole run.  Plain SGD allocates nothing
+        # (embed_optimizer is a plain attribute like matmul_precision -- tools/ab_step.py switches it between rounds --: a step
+        #  that finds it set without a state allocates one, _step_path)
+        self.emb_state = self.state_base = None
+        if self.embed_optimizer != "sgd":
+            self._alloc_emb_state()
         self.iter = 0
         self.comm = S.new_stream(self.dev) if self.multi else None
         self.side = S.new_stream(self.dev)
@@ -1133,6 +1171,41 @@ class TrainEngine:
             if self.qr["collisions"][k]:
                 E.weight_r.data.copy_(wr[k])
 
+    # ---- row-wise Adagrad's state ---------------------------------------------------------------------------------------
+    def _alloc_emb_state(self):
+        check_embed_optimizer(self.embed_optimizer, self.adagrad_eps, world_size=self.world, qr=self.qr is not None,
+                              evict_victim=bool(getattr(self, "evict_victim", False)))
+        rows = [int(n) for n in self.ctx.table_rows]
+        self._state_off = [sum(rows[:k]) for k in range(len(rows) + 1)]
+        self.emb_state = torch.zeros(self._state_off[-1], dtype=torch.float32, device=self.dev)
+        self.state_base = torch.tensor(self._state_off[:-1], dtype=torch.int64, device=self.dev)
+
+    def emb_state_views(self):
+        """Table k's accumulators: a view of n_k elements of emb_state."""
+        return [self.emb_state[a:b] for a, b in zip(self._state_off[:-1], self._state_off[1:])]
+
+    def emb_state_to_host(self):
+        """[T] CPU tensors, table k's n_k accumulators (--save-model); waits for this rank's last embedding update."""
+        if self._emb_done is not None:
+            S.current_stream(self.dev).wait_event(self._emb_done)
+        return [v.cpu() for v in self.emb_state_views()]
+
+    def load_emb_state(self, per_table):
+        """emb_state <- a list of per-table accumulators (--load-model); None: zeros."""
+        if self._emb_done is not None:
+            S.current_stream(self.dev).wait_event(self._emb_done)
+        if per_table is None:
+            self.emb_state.zero_()
+            return
+        views = self.emb_state_views()
+        if len(per_table) != len(views):
+            raise ValueError("emb_state: %d tables, the model has %d" % (len(per_table), len(views)))
+        for k, (v, h) in enumerate(zip(views, per_table)):
+            h = torch.as_tensor(h, dtype=torch.float32).reshape(-1)
+            if h.numel() != v.numel():
+                raise ValueError("emb_state[%d]: %d accumulators, the table has %d rows" % (k, h.numel(), v.numel()))
+            v.copy_(h)
+
     def qr_split(self, idx, q=None, r=None, stream=None):
         """idx [T, n] -> (q, r) (ops.qr_split; q=idx splits a window rectangle in place): what plan_window / WindowResolver /
         step() / evaluate() take in this mode."""
@@ -1247,6 +1320,8 @@ class TrainEngine:
         """The decisions of the step step() is about to issue (StepPath), from the batch, the hand-over of the previous step, the
         resolver's views and the schedule knobs.  The one place that evaluates them."""
         B, n = X.shape[0], lS_i.shape[1]
+        if self.embed_optimizer != "sgd" and self.emb_state is None:
+            self._alloc_emb_state()
         pf = self._pref
         hit = pf is not None and pf.matches(lS_i)
         phase = pf.phase if hit else self._phase
@@ -1285,13 +1360,15 @@ class TrainEngine:
             prepared=bool(hit and pf.prepared), nxt=nxt, resolved=self._res is not None and lS_o is None,
             next_resolved=self._next_res is not None, two_phase=two_phase, chain=chain, side_gather=side_gather,
             gather_alone=B >= self.gather_alone_min, fused=fused, sorted=None if sv is None else sv.stride,
-            once=bool(self.fuse_once and fused and sv is not None), next_sorted=self._next_sorted is not None,
+            # (row-wise Adagrad: the once-only fold is an SGD step -- the sorted apply takes every slot)
+            once=bool(self.fuse_once and fused and sv is not None and self.embed_optimizer == "sgd"), next_sorted=self._next_sorted is not None,
             chain_sort=chain and self._next_sorted is None, chained_top=chain and self.defer_top and not self.multi,
             next_bufs=(1 - phase) if two_phase else 2 + (self.iter & 1), emb_done_seen=self._emb_done is not None,
             timed=self._gslot is not None, loss_sync=self.loss_sync, resolve_cols=None if pr is None else int(pr["cols"].shape[1]),
             fwd_marked=bool(pr is not None and attach and fused), attach=attach, join=join,
             lanes=self.tape_lanes if B < self.tape_lanes_below else 1, wide_gemm=bool(self.wide_gemm),
-            matmul_precision=self.matmul_precision, lr=self.lr, lr_embeds=self.lr_embeds)
+            matmul_precision=self.matmul_precision, lr=self.lr, lr_embeds=self.lr_embeds,
+            embed_optimizer=self.embed_optimizer, adagrad_eps=self.adagrad_eps if self.embed_optimizer != "sgd" else 0.0)
 
     def _take(self, idx, res, phase: int, which, st):
         """A batch's (slots, miss_pos, miss_count) into the probe buffers `which`, misses into aux region `phase`, on stream st:
@@ -1533,6 +1610,7 @@ class TrainEngine:
         if next_res is not None and not isinstance(next_res, Resolved):
             next_res = Resolved(*next_res)
         if self.evict_victim:
+            check_embed_optimizer(self.embed_optimizer, self.adagrad_eps, evict_victim=True)
             assert not self.multi, "--evict-victim-cache is defined for one rank (every rank would write its own misses' rows)"
             next_idx = next_res = None          # the next batch's take follows this batch's write-back
         self.loss_sync = bool(loss_sync) or not self.fused_head
@@ -1875,7 +1953,16 @@ class TrainEngine:
             ops.qr_cached_bwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, dfeat[:, 1:, :], dfeat.stride(0), D, qw,
                               stream=side)
             ops.qr_cached_bwd_finish(ctx, self.qr_coll, n, qw, self.lr_embeds, self.Wr, stream=side)
-        if sv is not None:
+        if path.embed_optimizer != "sgd":
+            # the same plan, the Adagrad epilogue: S[tags[slot]] and the row, once per looked-up cache-proper slot
+            opt = dict(opt=path.embed_optimizer, eps=path.adagrad_eps, state=self.emb_state, state_base=self.state_base, stream=side)
+            if sv is not None:
+                ops.embbag_bwd_apply_sorted_opt(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work, sv.keys,
+                                                sv.meta, sv.stride, self._phase, False, cg.touched if self.multi else None, **opt)
+            else:
+                ops.embbag_bwd_apply_opt(ctx, n, lS_o, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work,
+                                         cg.touched if self.multi else None, **opt)
+        elif sv is not None:
             ops.embbag_bwd_apply_sorted(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work, sv.keys, sv.meta, sv.stride,
                                         self._phase, once, cg.touched if self.multi else None, stream=side)
         else:

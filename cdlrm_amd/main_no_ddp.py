@@ -140,7 +140,20 @@ def ProcessArgs(argv=None):
                         help="which of a window's new indices get a cache slot: `reference` = a random unprotected way each, "
                              "the latest claimant wins a contested slot (main_no_ddp.py:171-204); `fill` = collision-free and "
                              "ranked by the window's lookup counts (DESIGN.md; draws no random numbers)")
+    parser.add_argument("--embed-optimizer", type=str, default="sgd",
+                        help="the cached embedding rows' update: `sgd` = the reference's sparse SGD; `rowwise-adagrad` = one fp32 "
+                             "accumulator per table row, kept in HBM and indexed by table index (DESIGN.md 4.5)")
+    parser.add_argument("--adagrad-eps", type=float, default=1e-10, help="--embed-optimizer=rowwise-adagrad: std = sqrt(S) + eps")
     args = parser.parse_args(argv)
+    if args.embed_optimizer not in ("sgd", "rowwise-adagrad"):
+        sys.exit("ERROR: --embed-optimizer=%s is not supported (sgd | rowwise-adagrad)" % args.embed_optimizer)
+    from .engine import check_embed_optimizer
+    try:
+        # row-wise Adagrad's refusals (one rank, plain tables, no write-back of aux rows): the engine's own, before anything starts
+        check_embed_optimizer(args.embed_optimizer.replace("-", "_"), args.adagrad_eps, world_size=args.world_size,
+                              qr=args.qr_flag, evict_victim=args.evict_victim_cache)
+    except ValueError as e:
+        sys.exit("ERROR: --embed-optimizer=%s: %s" % (args.embed_optimizer, e))
     # (checked here and not by argparse `choices`: the run ends with the one ERROR: line every other refusal prints)
     if args.insert_policy not in ("reference", "fill"):
         sys.exit("ERROR: --insert-policy=%s is not supported (reference | fill)" % args.insert_policy)
@@ -447,10 +460,17 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                     E.weight.data.copy_(w)
         if world > 1:
             dist.barrier()
+    embed_opt = getattr(args, "embed_optimizer", "sgd").replace("-", "_")
     eng = TrainEngine(cache_group, dlrm, emb_tables, lr=args.learning_rate, lr_embeds=args.lr_embeds, world_size=world,
                       rank=rank, table_agg_freq=args.table_agg_freq, table_agg_op=args.table_agg_op,
                       loss=args.loss_function, loss_weights=loss_ws, defer_top_update=True,
-                      **({} if getattr(args, "matmul_precision", "fp32") == "fp32" else {"matmul_precision": args.matmul_precision}))
+                      **({} if getattr(args, "matmul_precision", "fp32") == "fp32" else {"matmul_precision": args.matmul_precision}),
+                      **({} if embed_opt == "sgd" else {"embed_optimizer": embed_opt, "adagrad_eps": args.adagrad_eps}))
+    if embed_opt != "sgd" and args.load_model:
+        # row-wise Adagrad's accumulators travel with the tables; a checkpoint written by an SGD run has none
+        if ld.get("emb_state") is None:
+            print("--load-model: %s holds no emb_state: the row-wise Adagrad accumulators start at zero" % args.load_model)
+        eng.load_emb_state(ld.get("emb_state"))
     for kv in filter(None, os.environ.get("CDLRM_ENGINE_ATTR", "").split(",")):
         # development (as bench.py --engine-attr): TrainEngine schedule knobs for same-box A/B runs of the CLI, 'name=value,...'
         k_, v_ = kv.split("=")
@@ -719,6 +739,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                         "emb": [(E.weight_q if hasattr(E, "weight_q") else E.weight).data.clone() for E in emb_tables.emb_l],
                         **({} if qr_layout is None else
                            {"emb_r": [E.weight_r.data.clone() if hasattr(E, "weight_r") else None for E in emb_tables.emb_l]}),
+                        **({} if eng.emb_state is None else {"emb_state": eng.emb_state_to_host()}),
                         "ln_emb": [int(n) for n in ln_emb], "m_spa": int(m_spa)}, args.save_model)
         if world > 1:
             dist.barrier()

@@ -367,6 +367,42 @@ def embbag_bwd_apply_sorted(ctx: CacheCtx, n: int, grad: torch.Tensor, ld_bag: i
                                                    stream_ptr(stream)))
 
 
+EMB_OPTS = {"sgd": 0, "rowwise_adagrad": 1}          # include/cdlrm_hip.h: CDLRM_EMB_OPT_*
+
+
+def embbag_bwd_apply_opt(ctx: CacheCtx, n: int, offsets: Optional[torch.Tensor], grad: torch.Tensor, ld_bag: int,
+                         ld_table: int, lr: float, work: torch.Tensor, touched: Optional[torch.Tensor] = None, *,
+                         opt: str = "sgd", eps: float = 0.0, state: Optional[torch.Tensor] = None,
+                         state_base: Optional[torch.Tensor] = None, stream=None):
+    """embbag_bwd_apply with an optimizer for the cache rows: opt "sgd" (the sibling's launches) or "rowwise_adagrad" (state:
+    fp32, one accumulator per table row, table t's from state_base[t] on; state_base: int64 [T] on the device)."""
+    nb = n if offsets is None else offsets.shape[1]
+    _check_emb_state(ctx, state, state_base)
+    check(_lib.lib().cdlrm_embbag_bwd_apply_opt(ctx.handle, ptr(offsets), n, nb, 0 if offsets is None else offsets.stride(0),
+                                                grad.data_ptr(), ld_bag, ld_table, float(lr), work.data_ptr(), ptr(touched),
+                                                EMB_OPTS[opt], float(eps), ptr(state), ptr(state_base), stream_ptr(stream)))
+
+
+def embbag_bwd_apply_sorted_opt(ctx: CacheCtx, n: int, grad: torch.Tensor, ld_bag: int, ld_table: int, lr: float,
+                                work: torch.Tensor, keys: int, meta: int, tstride: int, aux_phase: int, rest: bool,
+                                touched: Optional[torch.Tensor] = None, *, opt: str = "sgd", eps: float = 0.0,
+                                state: Optional[torch.Tensor] = None, state_base: Optional[torch.Tensor] = None, stream=None):
+    """embbag_bwd_apply_sorted with an optimizer for the cache rows (embbag_bwd_apply_opt); rest=True takes "sgd" only."""
+    _check_emb_state(ctx, state, state_base)
+    check(_lib.lib().cdlrm_embbag_bwd_apply_sorted_opt(ctx.handle, n, grad.data_ptr(), ld_bag, ld_table, float(lr), work.data_ptr(),
+                                                       keys, meta, tstride, int(aux_phase), int(bool(rest)), ptr(touched),
+                                                       EMB_OPTS[opt], float(eps), ptr(state), ptr(state_base),
+                                                       stream_ptr(stream)))
+
+
+def _check_emb_state(ctx: CacheCtx, state, state_base):
+    """The kernels index `state` by table index without knowing its length: it must hold every table's rows."""
+    if state is None:
+        return
+    assert state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= sum(int(r) for r in ctx.table_rows)
+    assert state_base is not None and state_base.dtype == torch.int64 and state_base.numel() == ctx.T and state_base.is_contiguous()
+
+
 BWD_ENTRIES = {"apply": 0, "rest": 1, "sorted": 2, "sorted_rest": 3}          # include/cdlrm_hip.h: CDLRM_BWD_ENTRY_*
 BWD_APPLY_KERNELS = {0: None, 1: "chunks", 2: "blocks", 3: "blocks_lean"}      # CDLRM_BWD_APPLY_*
 

@@ -191,6 +191,26 @@ int cdlrm_embbag_bwd_sorted_views(cdlrm_ctx* ctx, void* sorted, int32_t nb, int6
 int cdlrm_embbag_bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table, float lr,
                                   void* work, const uint64_t* keys, const int32_t* meta, int64_t tstride, int32_t aux_phase,
                                   int32_t rest, uint8_t* touched, void* stream);
+/* The two applies with an optimizer for the cache rows.  Arguments: the sibling's, then, in front of the
+ * stream (a launching entry point ends on its stream), opt / eps / state / state_base:
+ *   opt = CDLRM_EMB_OPT_SGD: exactly the sibling's plan and launches; eps, state and state_base are not read.
+ *   opt = CDLRM_EMB_OPT_ROWWISE_ADAGRAD: per run of a cache-proper slot s of table t, with G [D] the run's gradient sum (the
+ *     sum, bit for bit, that the SGD kernels apply) and i = tags[s] the table index resident in s:
+ *         S[i] += (1/D) sum_d G_d^2;   W[s] -= lr * G / (sqrt(S[i]) + eps)
+ *     state: device fp32, one accumulator per TABLE row; table t's at state + state_base[t] (state_base: device int64 [T]),
+ *     table_rows[t] of them.  Read and written once per looked-up slot, by the lane group that owns the run: no atomics, two
+ *     launches on equal inputs give equal bits.  Aux slots (misses) are skipped: no row write, no state update.
+ *     eps > 0; dim <= 1024; rest = 1 (the once-only slots already took an SGD step) is refused. */
+#define CDLRM_EMB_OPT_SGD 0
+#define CDLRM_EMB_OPT_ROWWISE_ADAGRAD 1
+int cdlrm_embbag_bwd_apply_opt(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags,
+                               int64_t ld_off, const float* grad, int64_t ld_bag, int64_t ld_table, float lr,
+                               void* work, uint8_t* touched, int32_t opt, float eps, float* state,
+                               const int64_t* state_base, void* stream);
+int cdlrm_embbag_bwd_apply_sorted_opt(cdlrm_ctx* ctx, int64_t n, const float* grad, int64_t ld_bag, int64_t ld_table, float lr,
+                                      void* work, const uint64_t* keys, const int32_t* meta, int64_t tstride, int32_t aux_phase,
+                                      int32_t rest, uint8_t* touched, int32_t opt, float eps, float* state,
+                                      const int64_t* state_base, void* stream);
 
 /* Which kernels one embedding backward launches (cdlrm_embbag_bwd_route below). */
 #define CDLRM_BWD_ENTRY_APPLY 0         /* cdlrm_embbag_bwd_prepare + cdlrm_embbag_bwd_apply (= cdlrm_embbag_bwd_sgd) */
