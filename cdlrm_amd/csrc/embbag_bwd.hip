@@ -241,7 +241,302 @@ __global__ void __launch_bounds__(256) k_seg_meta(const uint64_t* __restrict__ k
     }
 }
 
-template <int LPR, bool ARANGE>
+// ---------------------------------------------------------------------------------------------
+// The row update: a compile-time policy (`Row`) of the three apply kernels k_bwd_chunks / k_bwd_blocks / k_bwd_long.  The kernels
+// own the run search, the gradient-row sums (their loads in flight and their order of additions: the bit-exactness contract), the
+// partial sums and the long-run list; a Row says what happens to the row of a run whose whole sum G one lane group holds:
+//   SgdRow       W[slot] = fma(-lr, G, W[slot]), column chunk by column chunk: stored as soon as the chunk's sum is known, any D.
+//   AdaRow       row-wise Adagrad (opt-in: cdlrm_embbag_bwd_apply_opt / _apply_sorted_opt, CDLRM_EMB_OPT_ROWWISE_ADAGRAD; DESIGN.md
+//                4.5), per run of a CACHE-PROPER slot s of table t:
+//                    i = tags[s];  S[i] += (1/D) sum_d G_d^2;  W[s] -= lr * G / (sqrt(S[i]) + eps)
+//                S: one fp32 per TABLE row (state + state_base[t] + i), indexed by the tag of the slot, so it never moves with a
+//                row.  A slot is one run and a run has one owning lane group: S[i] is read and written once per launch, without
+//                atomics.  Aux slots (misses: transient copies, rewritten by the next forward) are skipped -- no row write, no state
+//                update.  A lane keeps the NCH = ceil(D4 / LPR) column chunks it owns in registers until the row's sum of squares
+//                is known (NCH > 1 only at LPR = 64, D > 256); the sum is reduced over the lane group by a fixed xor butterfly:
+//                every lane ends with the same bits.
+// (Only k_bwd_chunks takes both: k_bwd_blocks and k_bwd_long take AdaRow, and the SGD update has k_bwd_blocks_sgd and
+//  k_bwd_long_sgd, texts of their own that held their measured speed where the shared bodies did not -- see there.)
+// A kernel's use of a Row r, per run:  r.find, r.read_state;  per column chunk the lane owns (Row::for_chunks): r.load, the sum,
+// r.chunk;  then r.finish and r.flag (the touched rule).
+struct AdaArgs {
+    const int64_t* tags;
+    float* state;
+    const int64_t* state_base;      // device [T]: first accumulator of table t
+    float eps;
+};
+
+// what a row update sees of its table and its lane
+struct RowCtx {
+    const TableDesc* tab;
+    int t, ways, D4, c;
+    uint32_t aux0;                  // first aux slot
+    // aux rows (transient copies of host rows, rewritten by every forward) are never flagged: the cross-rank row merge
+    // leaves them alone, so it cannot collide with the NEXT batch's aux fill running ahead in the other aux region
+    uint32_t first_aux;
+    float lr;
+    AdaArgs o;
+};
+
+template <int LPR_>
+struct SgdRow {
+    static constexpr int LPR = LPR_;
+    static constexpr bool SGD = true;
+    bool upd = false;               // this lane group updates the run's row (the run fits one chunk; k_bwd_long: always)
+    float4 w;
+    __device__ __forceinline__ void find(const RowCtx&, uint32_t, bool single) { upd = single; }
+    __device__ __forceinline__ void read_state(const RowCtx&) {}
+    template <class F>
+    static __device__ __forceinline__ void for_chunks(int c, int D4, F f) {
+        for (int cc = c; cc < D4; cc += LPR) f(0, cc);
+    }
+    __device__ __forceinline__ void load(int, const float4* wp) {
+        if (upd) w = *wp;           // issued early, consumed after the sums
+    }
+    __device__ __forceinline__ void chunk(int, float4* wp, const float4& g, float lr) {
+        if (upd) {
+            w.x = fmaf(-lr, g.x, w.x); w.y = fmaf(-lr, g.y, w.y);
+            w.z = fmaf(-lr, g.z, w.z); w.w = fmaf(-lr, g.w, w.w);
+            *wp = w;
+        }
+    }
+    __device__ __forceinline__ void finish(const RowCtx&, float4*) {}
+    __device__ __forceinline__ bool flag(const RowCtx& x, uint32_t slot) const { return upd && slot < x.first_aux; }
+};
+
+// the accumulator cell of slot `slot` of table t; -1: an aux slot, or a tag that names no row of the table (an empty way: nothing
+// the batch can have looked up) -- the run is then left alone
+__device__ __forceinline__ int64_t ada_cell(const TableDesc* __restrict__ tab, int t, const AdaArgs& o, uint32_t slot,
+                                            uint32_t aux0, int ways) {
+    if (slot >= aux0) return -1;
+    const uint32_t P = (uint32_t)tab[t].P;          // slot = P * way + set; tags are [P, ways]
+    const uint32_t way = slot / P, set = slot - way * P;
+    const int64_t i = o.tags[tab[t].tag_base + (int64_t)set * ways + way];
+    return (uint64_t)i < (uint64_t)tab[t].n_rows ? o.state_base[t] + i : -1;
+}
+
+// S_new and the rows' step from the run sums g (zero in chunks past D4) -- called by ALL lanes of the group
+template <int LPR, int NCH>
+__device__ __forceinline__ float ada_step(float4 (&w)[NCH], const float4 (&g)[NCH], float s_old, float lr, float eps, int D4) {
+    float ss = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        ss = fmaf(g[k].x, g[k].x, ss); ss = fmaf(g[k].y, g[k].y, ss);
+        ss = fmaf(g[k].z, g[k].z, ss); ss = fmaf(g[k].w, g[k].w, ss);
+    }
+#pragma unroll
+    for (int m = LPR >> 1; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
+    const float s_new = s_old + ss / (float)(4 * D4);
+    const float scale = lr / (sqrtf(s_new) + eps);
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        w[k].x = fmaf(-scale, g[k].x, w[k].x); w[k].y = fmaf(-scale, g[k].y, w[k].y);
+        w[k].z = fmaf(-scale, g[k].z, w[k].z); w[k].w = fmaf(-scale, g[k].w, w[k].w);
+    }
+    return s_new;
+}
+
+template <int LPR_, int NCH>
+struct AdaRow {
+    static constexpr int LPR = LPR_;
+    static constexpr bool SGD = false;
+    bool upd = false;               // a cache-proper slot with a valid tag whose run fits one chunk (uniform over the lane group)
+    int64_t cell = -1;
+    float s_old = 0.f;
+    float4 w[NCH], g[NCH];
+    // tag -> accumulator -> row: issued early, consumed after the sums
+    __device__ __forceinline__ void find(const RowCtx& x, uint32_t slot, bool single) {
+        cell = single ? ada_cell(x.tab, x.t, x.o, slot, x.aux0, x.ways) : -1;
+        upd = cell >= 0;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) w[k] = g[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    __device__ __forceinline__ void read_state(const RowCtx& x) { s_old = upd ? x.o.state[cell] : 0.f; }
+    template <class F>
+    static __device__ __forceinline__ void for_chunks(int c, int D4, F f) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (c + k * LPR < D4) f(k, c + k * LPR);
+    }
+    __device__ __forceinline__ void load(int k, const float4* wp) {
+        if (upd) w[k] = *wp;
+    }
+    __device__ __forceinline__ void chunk(int k, float4*, const float4& sum, float) { g[k] = sum; }
+    __device__ __forceinline__ void finish(const RowCtx& x, float4* wrow) {
+        if (!upd) return;
+        const float s_new = ada_step<LPR, NCH>(w, g, s_old, x.lr, x.o.eps, x.D4);
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (x.c + k * LPR < x.D4) wrow[x.c + k * LPR] = w[k];
+        if (x.c == 0) x.o.state[cell] = s_new;
+    }
+    __device__ __forceinline__ bool flag(const RowCtx&, uint32_t) const { return upd; }
+};
+
+// ---- the pieces the apply kernels are made of ----------------------------------------------------------------------------------
+// a ballot over the lanes of one lane group
+template <int LPR>
+__device__ __forceinline__ unsigned long long group_ballot(bool pred, int gshift) {
+    const unsigned long long b = __ballot(pred);
+    return LPR == 64 ? b : ((b >> gshift) & ((1ull << LPR) - 1));
+}
+
+// k_bwd_chunks: the first position after p (within the chunk window) that starts another run, found by the group at once;
+// SEG_CH: the run continues past this chunk
+template <int LPR>
+__device__ __forceinline__ int chunk_extent(const int32_t* __restrict__ mt, int64_t p, int64_t n, int c, int gshift) {
+    constexpr int KM = (SEG_CH + LPR - 1) / LPR;
+    int jstop = SEG_CH;
+#pragma unroll
+    for (int m = KM - 1; m >= 0; --m) {
+        const int j = c + m * LPR;
+        const int64_t q = p + 1 + j;
+        const bool stop = (j < SEG_CH) && (q >= n || mt[q] == 0);
+        const unsigned long long bits = group_ballot<LPR>(stop, gshift);
+        if (bits) jstop = m * LPR + (__ffsll((long long)bits) - 1);
+    }
+    return jstop;
+}
+
+__device__ __forceinline__ void add4(float4& acc, const float4& v) { acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w; }
+
+// gradient row of the lookup at batch position pos, this lane's column chunk (gc: the table's gradient + 4 * chunk)
+template <bool ARANGE>
+__device__ __forceinline__ float4 grad_row(const float* __restrict__ gc, int64_t ld_bag, const int64_t* __restrict__ off,
+                                           int64_t n_bags, int64_t pos) {
+    const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
+    return *reinterpret_cast<const float4*>(gc + bag * ld_bag);
+}
+
+// k_bwd_chunks' sum: the rows of the len sorted keys at kp, in position order, four loads in flight
+template <bool ARANGE>
+__device__ __forceinline__ float4 sum_rows_keys(const uint64_t* __restrict__ kp, int len, const float* __restrict__ gc,
+                                                int64_t ld_bag, const int64_t* __restrict__ off, int64_t n_bags) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int q = 0;
+    for (; q + 4 <= len; q += 4) {
+        int64_t bag[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t pos = (int64_t)(kp[q + u] & 0xffffffffull);
+            bag[u] = ARANGE ? pos : bag_of(off, n_bags, pos);
+        }
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(gc + bag[u] * ld_bag);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) add4(acc, v[u]);
+    }
+    for (; q < len; ++q) add4(acc, grad_row<ARANGE>(gc, ld_bag, off, n_bags, (int64_t)(kp[q] & 0xffffffffull)));
+    return acc;
+}
+
+// k_bwd_blocks, one head in the block: the rows of the len positions at sp (LDS), RA loads in flight
+template <bool ARANGE, int RA>
+__device__ __forceinline__ float4 sum_rows_lone(const uint32_t* sp, int len, const float* __restrict__ gc, int64_t ld_bag,
+                                                const int64_t* __restrict__ off, int64_t n_bags) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = 0; q < len; q += RA) {
+        float4 v[RA];
+#pragma unroll
+        for (int u = 0; u < RA; ++u)
+            if (q + u < len) v[u] = grad_row<ARANGE>(gc, ld_bag, off, n_bags, sp[q + u]);
+#pragma unroll
+        for (int u = 0; u < RA; ++u)
+            if (q + u < len) add4(acc, v[u]);
+    }
+    return acc;
+}
+
+// a chunk head of a block (k_bwd_blocks): position j of the block, len positions of its run inside this chunk
+struct Head {
+    int j, len;                     // len == 0: no head
+    bool head, single, more;        // the chunk starts its run / is the whole run / is not the run's last
+    uint32_t slot;
+};
+__device__ __forceinline__ Head decode_head(uint64_t S, int j, const uint32_t* s_slot) {
+    Head h;
+    const uint64_t rest = S >> (j + 1);
+    const int nxt = rest ? (__ffsll((long long)rest) - 1) : 64;
+    h.more = nxt >= SEG_CH;
+    h.len = h.more ? SEG_CH : nxt + 1;
+    h.head = (S >> j) & 1;
+    h.single = h.head && !h.more;
+    h.j = j;
+    h.slot = s_slot[j];
+    return h;
+}
+
+// k_bwd_blocks, up to HU heads: four rows of each in flight
+template <bool ARANGE, int HU>
+__device__ __forceinline__ void sum_rows_heads(float4 (&acc)[HU], const Head (&h)[HU], int maxlen, const uint32_t* s_pos,
+                                               const float* __restrict__ gc, int64_t ld_bag, const int64_t* __restrict__ off,
+                                               int64_t n_bags) {
+#pragma unroll
+    for (int u = 0; u < HU; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int q = 0; q < maxlen; q += 4) {
+        float4 v[HU][4];
+#pragma unroll
+        for (int u = 0; u < HU; ++u)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (q + k < h[u].len) v[u][k] = grad_row<ARANGE>(gc, ld_bag, off, n_bags, s_pos[h[u].j + q + k]);
+#pragma unroll
+        for (int u = 0; u < HU; ++u)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (q + k < h[u].len) add4(acc[u], v[u][k]);
+    }
+}
+
+// what lane 0 of the group leaves behind for a chunk at sorted position p (r0 positions into its run): the row's touched flag,
+// or the run's entry in the long-run list (its first chunk) and its end (its last chunk)
+__device__ __forceinline__ void book_chunk(int t, int64_t p, const int32_t& r0, int len, bool head, bool single, bool more,
+                                           bool flag, int64_t row, int64_t n, uint8_t* __restrict__ touched,
+                                           int64_t* __restrict__ longlist, int32_t* __restrict__ longcount,
+                                           int32_t* __restrict__ runend) {
+    if (single) {
+        if (touched && flag) touched[row] = 1;
+    } else if (head) {
+        const int li = atomicAdd(longcount, 1);
+        longlist[li] = ((int64_t)t << 40) | p;
+    }
+    // the LAST chunk of a long run knows where the run ends: leave it at the run's head for k_bwd_long (which
+    // would otherwise find it by a 13-step binary search over the keys, one dependent global read per step)
+    if (!single && !more) runend[(int64_t)t * n + (p - r0)] = (int32_t)(p + len);
+}
+
+// k_bwd_long's sum: the chunk partials of the run [p0, end) in chunk order (a fixed order: reproducible), sixteen then four loads
+// in flight (a tiny table's run is thousands of lookups = a hundred partials behind ONE lane group: at four in flight the kernel
+// was its latency chain).  pc: the table's partials + this lane's column chunk
+__device__ __forceinline__ float4 fold_partials(const float4* __restrict__ pc, int D4, int64_t p0, int64_t end) {
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    // at most two chunk heads of long runs share one SEG_CH-aligned bucket of positions: the run's first chunk is the odd one
+    auto partial = [&](int64_t q) { return pc[(2 * (q / SEG_CH) + (q == p0 ? 1 : 0)) * D4]; };
+    int64_t p = p0;
+    for (; p + 15 * SEG_CH < end; p += 16 * SEG_CH) {
+        float4 v[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[u] = partial(p + u * SEG_CH);
+#pragma unroll
+        for (int u = 0; u < 16; ++u) add4(acc, v[u]);
+    }
+    for (; p + 3 * SEG_CH < end; p += 4 * SEG_CH) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = partial(p + u * SEG_CH);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) add4(acc, v[u]);
+    }
+    for (; p < end; p += SEG_CH) add4(acc, partial(p));
+    return acc;
+}
+
+// ---- the apply kernels ---------------------------------------------------------------------------------------------------------
+// A lane group per sorted position; only chunk heads work.
+// (kstride: elements between two tables' sorted lists -- n, or nb * n inside a window's sorted chunk; aux_add: the sorted
+//  chunk holds phase-0 aux slots, the batch trains on aux region aux_add / aux)
+template <class Row, bool ARANGE>
 __global__ void __launch_bounds__(256) k_bwd_chunks(const TableDesc* __restrict__ tab, int D4,
                                                     float4* __restrict__ weight, const uint64_t* __restrict__ keys,
                                                     const int32_t* __restrict__ meta,
@@ -251,89 +546,45 @@ __global__ void __launch_bounds__(256) k_bwd_chunks(const TableDesc* __restrict_
                                                     int64_t pstride, int64_t* __restrict__ longlist,
                                                     int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
                                                     int64_t aux_total, int32_t* __restrict__ runend, int64_t kstride,
-                                                    int ways, int aux_add) {
-    constexpr int KM = (SEG_CH + LPR - 1) / LPR;
+                                                    int ways, int aux_add, AdaArgs o) {
+    constexpr int LPR = Row::LPR;
     const int t = blockIdx.y;
     const int64_t row_base = tab[t].row_base;
-    // aux rows (transient copies of host rows, rewritten by every forward) are never flagged: the cross-rank row merge
-    // leaves them alone, so it cannot collide with the NEXT batch's aux fill running ahead in the other aux region
-    const uint32_t first_aux = (uint32_t)(tab[t].rows - aux_total);
     const int c = threadIdx.x % LPR;
     const int gpb = blockDim.x / LPR;
     const int gid = threadIdx.x / LPR;
     const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
-    // (kstride: elements between two tables' sorted lists -- n, or nb * n inside a window's sorted chunk; aux_add: the sorted
-    //  chunk holds phase-0 aux slots, the batch trains on aux region aux_add / aux)
     const uint64_t* kt = keys + (int64_t)t * kstride;
     const int32_t* mt = meta + (int64_t)t * kstride;
     const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
     const float* g = grad + (int64_t)t * ld_table;
     const int64_t* off = ARANGE ? nullptr : offsets + (int64_t)t * ld_off;
+    const RowCtx x = {tab, t, ways, D4, c, aux0, (uint32_t)(tab[t].rows - aux_total), lr, o};
     for (int64_t p = (int64_t)blockIdx.x * gpb + gid; p < n; p += (int64_t)gridDim.x * gpb) {
         const int r0 = mt[p];
         if (r0 % SEG_CH) continue;               // chunk interior: some other group owns this position
         const bool head = r0 == 0;
         uint32_t slot = (uint32_t)(kt[p] >> 32);
         if (slot >= aux0) slot += aux_add;
-        // first position after p (within the chunk window) that starts another run, found by the group at once
-        int jstop = SEG_CH;                      // SEG_CH: the run continues past this chunk
-#pragma unroll
-        for (int m = KM - 1; m >= 0; --m) {
-            const int j = c + m * LPR;
-            const int64_t q = p + 1 + j;
-            const bool stop = (j < SEG_CH) && (q >= n || mt[q] == 0);
-            const unsigned long long b = __ballot(stop);
-            const unsigned long long bits = LPR == 64 ? b : ((b >> gshift) & ((1ull << LPR) - 1));
-            if (bits) jstop = m * LPR + (__ffsll((long long)bits) - 1);
-        }
+        const int jstop = chunk_extent<LPR>(mt, p, n, c, gshift);
         const bool more = jstop == SEG_CH;
         const int len = more ? SEG_CH : jstop + 1;
         const bool single = head && !more;
-        for (int cc = c; cc < D4; cc += LPR) {
-            float4 w;
-            if (single) w = weight[(row_base + slot) * D4 + cc];     // issued early, consumed after the sums
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-            int q = 0;
-            for (; q + 4 <= len; q += 4) {
-                int64_t bag[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int64_t pos = (int64_t)(kt[p + q + u] & 0xffffffffull);
-                    bag[u] = ARANGE ? pos : bag_of(off, n_bags, pos);
-                }
-                float4 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(g + bag[u] * ld_bag + cc * 4);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
-            }
-            for (; q < len; ++q) {
-                const int64_t pos = (int64_t)(kt[p + q] & 0xffffffffull);
-                const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
-                const float4 v = *reinterpret_cast<const float4*>(g + bag * ld_bag + cc * 4);
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-            if (single) {
-                w.x = fmaf(-lr, acc.x, w.x); w.y = fmaf(-lr, acc.y, w.y);
-                w.z = fmaf(-lr, acc.z, w.z); w.w = fmaf(-lr, acc.w, w.w);
-                weight[(row_base + slot) * D4 + cc] = w;
-            } else {
-                // at most two chunk heads of long runs share one SEG_CH-aligned bucket of positions
-                const int64_t pi = 2 * (p / SEG_CH) + (head ? 1 : 0);
-                partials[((int64_t)t * pstride + pi) * D4 + cc] = acc;
-            }
-        }
-        if (c == 0) {
-            if (single) {
-                if (touched && slot < first_aux) touched[row_base + slot] = 1;
-            } else if (head) {
-                const int li = atomicAdd(longcount, 1);
-                longlist[li] = ((int64_t)t << 40) | p;
-            }
-            // the LAST chunk of a long run knows where the run ends: leave it at the run's head for k_bwd_long (which
-            // would otherwise find it by a 13-step binary search over the keys, one dependent global read per step)
-            if (!single && !more) runend[(int64_t)t * n + (p - r0)] = (int32_t)(p + len);
-        }
+        Row r;
+        r.find(x, slot, single);
+        r.read_state(x);
+        float4* wrow = weight + (row_base + slot) * D4;
+        // at most two chunk heads of long runs share one SEG_CH-aligned bucket of positions
+        float4* prow = partials + ((int64_t)t * pstride + 2 * (p / SEG_CH) + (head ? 1 : 0)) * D4;
+        Row::for_chunks(c, D4, [&](int k, int cc) __attribute__((always_inline)) {
+            r.load(k, wrow + cc);
+            const float4 acc = sum_rows_keys<ARANGE>(kt + p, len, g + cc * 4, ld_bag, off, n_bags);
+            r.chunk(k, wrow + cc, acc, lr);
+            if (!single) prow[cc] = acc;
+        });
+        r.finish(x, wrow);
+        if (c == 0)
+            book_chunk(t, p, r0, len, head, single, more, r.flag(x, slot), row_base + slot, n, touched, longlist, longcount, runend);
     }
 }
 
@@ -342,10 +593,11 @@ __global__ void __launch_bounds__(256) k_bwd_chunks(const TableDesc* __restrict_
 // reads, and a group makes ~9 such trips at c3 -- the kernel is a chain of latencies (52 us alone for 166 MB of traffic).
 // Here a lane group owns a BLOCK of SEG_CH consecutive sorted positions: one coalesced read brings the keys and run distances of
 // the block and of the SEG_CH positions behind it (a chunk that starts in the block ends at most there), run starts and chunk
-// heads become two bit masks (a ballot), and the heads of the block are worked FOUR AT A TIME with four gradient rows each in
-// flight (16 rows when the block holds one head: the inside of a long run).  Two dependent reads per block instead of four per
-// position.
-template <int LPR, bool ARANGE, int HU = 4, int RA = 16>
+// heads become two bit masks (a ballot), and the heads of the block are worked HU AT A TIME with four gradient rows each in
+// flight (RA rows when the block holds one head: the inside of a long run).  Two dependent reads per block instead of four per
+// position.  Instantiated for AdaRow (skip_once, the `rest` entries' switch, is an SGD matter -- k_bwd_blocks_sgd below --; the
+// parameter and aux_total are not read here: launch_blocks passes one argument list to either kernel).
+template <class Row, bool ARANGE, int HU = 4, int RA = 16>
 __global__ void __launch_bounds__(256) k_bwd_blocks(const TableDesc* __restrict__ tab, int D4,
                                                     float4* __restrict__ weight, const uint64_t* __restrict__ keys,
                                                     const int32_t* __restrict__ meta,
@@ -355,7 +607,132 @@ __global__ void __launch_bounds__(256) k_bwd_blocks(const TableDesc* __restrict_
                                                     int64_t pstride, int64_t* __restrict__ longlist,
                                                     int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
                                                     int64_t aux_total, int32_t* __restrict__ runend, int skip_once,
-                                                    int64_t kstride, int ways, int aux_add) {
+                                                    int64_t kstride, int ways, int aux_add, AdaArgs o) {
+    constexpr int LPR = Row::LPR;
+    constexpr int GPB = 256 / LPR;
+    constexpr int SPAN = 2 * SEG_CH;                // positions a block's chunks can reach
+    constexpr int NL = SPAN / LPR;                  // span positions per lane
+    static_assert(SEG_CH == 32 && SPAN % LPR == 0, "masks below are 32 / 64 bits wide");
+    __shared__ uint32_t s_pos[GPB][SPAN];           // low half of the key: the lookup's position in the batch
+    __shared__ uint32_t s_slot[GPB][SEG_CH];
+    __shared__ int32_t s_r0[GPB][SEG_CH];
+    const int t = blockIdx.y;
+    const int64_t row_base = tab[t].row_base;
+    const int c = threadIdx.x % LPR;
+    const int gid = threadIdx.x / LPR;
+    const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
+    const uint64_t* kt = keys + (int64_t)t * kstride;
+    const int32_t* mt = meta + (int64_t)t * kstride;
+    const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
+    const float* g = grad + (int64_t)t * ld_table;
+    const int64_t* off = ARANGE ? nullptr : offsets + (int64_t)t * ld_off;
+    const RowCtx x = {tab, t, ways, D4, c, aux0, (uint32_t)(tab[t].rows - aux_total), lr, o};
+    const int64_t nblk = (n + SEG_CH - 1) / SEG_CH;
+    for (int64_t blk = (int64_t)blockIdx.x * GPB + gid; blk < nblk; blk += (int64_t)gridDim.x * GPB) {
+        const int64_t p0 = blk * SEG_CH;
+        uint64_t S = 0;                              // bit j: position p0 + j starts a run (or lies past the end)
+        uint32_t H = 0;                              // bit j < SEG_CH: position p0 + j is a chunk head
+        __builtin_amdgcn_wave_barrier();             // the previous block's LDS reads are issued before these writes
+#pragma unroll
+        for (int m = 0; m < NL; ++m) {
+            const int j = c + m * LPR;
+            const int64_t q = p0 + j;
+            const bool in = q < n;
+            const uint64_t key = in ? kt[q] : 0ull;
+            const int32_t r = in ? mt[q] : 0;
+            s_pos[gid][j] = (uint32_t)key;
+            if (j < SEG_CH) {
+                uint32_t slot = (uint32_t)(key >> 32);
+                if (slot >= aux0) slot += aux_add;
+                s_slot[gid][j] = slot;
+                s_r0[gid][j] = r;
+            }
+            S |= group_ballot<LPR>(r == 0, gshift) << (m * LPR);
+            if (m * LPR < SEG_CH) H |= (uint32_t)(group_ballot<LPR>(in && j < SEG_CH && (r % SEG_CH) == 0, gshift) << (m * LPR));
+        }
+        __builtin_amdgcn_wave_barrier();
+        float4* pbucket = partials + ((int64_t)t * pstride + 2 * blk) * D4;
+        while (H) {
+            const bool alone = (H & (H - 1)) == 0;
+            if (alone) {
+                // one head: RA gradient rows in flight
+                const Head h = decode_head(S, __ffs((int)H) - 1, s_slot[gid]);
+                H = 0;
+                Row r;
+                r.find(x, h.slot, h.single);
+                r.read_state(x);
+                float4* wrow = weight + (row_base + h.slot) * D4;
+                Row::for_chunks(c, D4, [&](int k, int cc) __attribute__((always_inline)) {
+                    r.load(k, wrow + cc);
+                    const float4 acc = sum_rows_lone<ARANGE, RA>(s_pos[gid] + h.j, h.len, g + cc * 4, ld_bag, off, n_bags);
+                    r.chunk(k, wrow + cc, acc, lr);
+                    if (!h.single) pbucket[(h.head ? 1 : 0) * D4 + cc] = acc;
+                });
+                r.finish(x, wrow);
+                if (c == 0)
+                    book_chunk(t, p0 + h.j, s_r0[gid][h.j], h.len, h.head, h.single, h.more, r.flag(x, h.slot), row_base + h.slot, n,
+                               touched, longlist, longcount, runend);
+                continue;
+            }
+            // up to HU heads, four gradient rows of each in flight
+            Head h[HU];
+            Row r[HU];
+            int maxlen = 0;
+#pragma unroll
+            for (int u = 0; u < HU; ++u) {
+                h[u] = Head{0, 0, false, false, false, 0};
+                if (H) {
+                    h[u] = decode_head(S, __ffs((int)H) - 1, s_slot[gid]);
+                    H &= H - 1;
+                    maxlen = max(maxlen, h[u].len);
+                    r[u].find(x, h[u].slot, h[u].single);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < HU; ++u) r[u].read_state(x);
+            Row::for_chunks(c, D4, [&](int k, int cc) __attribute__((always_inline)) {
+                float4 acc[HU];
+#pragma unroll
+                for (int u = 0; u < HU; ++u) r[u].load(k, weight + (row_base + h[u].slot) * D4 + cc);
+                sum_rows_heads<ARANGE, HU>(acc, h, maxlen, s_pos[gid], g + cc * 4, ld_bag, off, n_bags);
+#pragma unroll
+                for (int u = 0; u < HU; ++u) {
+                    if (h[u].len == 0) continue;
+                    r[u].chunk(k, weight + (row_base + h[u].slot) * D4 + cc, acc[u], lr);
+                    if (!h[u].single) pbucket[(h[u].head ? 1 : 0) * D4 + cc] = acc[u];
+                }
+            });
+#pragma unroll
+            for (int u = 0; u < HU; ++u) r[u].finish(x, weight + (row_base + h[u].slot) * D4);
+            if (c == 0) {
+#pragma unroll
+                for (int u = 0; u < HU; ++u) {
+                    if (h[u].len == 0) continue;
+                    book_chunk(t, p0 + h[u].j, s_r0[gid][h[u].j], h[u].len, h[u].head, h[u].single, h[u].more, r[u].flag(x, h[u].slot),
+                               row_base + h[u].slot, n, touched, longlist, longcount, runend);
+                }
+            }
+        }
+    }
+}
+
+// k_bwd_blocks with the SGD update, in its own text: the shared body above with SgdRow ran the lean <.., true, 1, 8> form 15 %
+// slower alone (47.4 against 41.3 us, profiles/emb_apply_refactor_times.txt), so the SGD kernel keeps the text it was measured
+// and tuned with (bwd_apply_plan) and k_bwd_blocks above is instantiated for AdaRow only.  The same sums in the same order:
+// tests/test_emb_apply_digests.py and test_embbag_bwd_routes.py ("same bits across kernels") hold the two texts together.
+// skip_once: runs of ONE lookup were updated by the interaction backward itself (cdlrm_gather_interact_bwd_sgd).  (The unnamed
+// AdaArgs: launch_blocks' one argument list; not read.)
+template <int LPR, bool ARANGE, int HU = 4, int RA = 16>
+__global__ void __launch_bounds__(256) k_bwd_blocks_sgd(const TableDesc* __restrict__ tab, int D4,
+                                                    float4* __restrict__ weight, const uint64_t* __restrict__ keys,
+                                                    const int32_t* __restrict__ meta,
+                                                    const int64_t* __restrict__ offsets, int64_t n, int64_t n_bags,
+                                                    int64_t ld_off, const float* __restrict__ grad, int64_t ld_bag,
+                                                    int64_t ld_table, float lr, float4* __restrict__ partials,
+                                                    int64_t pstride, int64_t* __restrict__ longlist,
+                                                    int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
+                                                    int64_t aux_total, int32_t* __restrict__ runend, int skip_once,
+                                                    int64_t kstride, int ways, int aux_add, AdaArgs) {
     constexpr int GPB = 256 / LPR;
     constexpr int SPAN = 2 * SEG_CH;                // positions a block's chunks can reach
     constexpr int NL = SPAN / LPR;                  // span positions per lane
@@ -549,14 +926,18 @@ __global__ void __launch_bounds__(256) k_bwd_blocks(const TableDesc* __restrict_
     }
 }
 
+// k_bwd_long with the SGD update, in its own text like k_bwd_blocks_sgd and for the same reason: with SgdRow the shared body below
+// compiled to 152 registers against this text's 202 (3 waves per SIMD against 2) and the SGD applies that end in it ran 1 to
+// 1.5 us over the parent's slowest round (profiles/emb_apply_refactor_times.txt, section B); k_bwd_long below is instantiated for
+// AdaRow only.  (The unnamed AdaArgs: launch_long passes one argument list to either kernel; this one does not read it.)
 template <int LPR>
-__global__ void __launch_bounds__(256) k_bwd_long(const TableDesc* __restrict__ tab, int D4,
+__global__ void __launch_bounds__(256) k_bwd_long_sgd(const TableDesc* __restrict__ tab, int D4,
                                                   float4* __restrict__ weight, const uint64_t* __restrict__ keys,
                                                   int64_t n, float lr, const float4* __restrict__ partials,
                                                   int64_t pstride, const int64_t* __restrict__ longlist,
                                                   int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
                                                   int64_t aux_total, const int32_t* __restrict__ runend, int64_t kstride,
-                                                  int ways, int aux_add) {
+                                                  int ways, int aux_add, AdaArgs) {
     const int c = threadIdx.x % LPR;
     const int gpb = blockDim.x / LPR;
     const int gid = threadIdx.x / LPR;
@@ -622,372 +1003,24 @@ __global__ void __launch_bounds__(256) k_bwd_long(const TableDesc* __restrict__ 
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Row-wise Adagrad (opt-in: cdlrm_embbag_bwd_apply_opt / _apply_sorted_opt, opt = CDLRM_EMB_OPT_ROWWISE_ADAGRAD).
-// Sibling kernels of k_bwd_chunks / k_bwd_blocks / k_bwd_long: the same sums in the same order (a run's G is bit for bit what
-// the SGD kernels multiply by -lr), and where those write a row these do, per run of a CACHE-PROPER slot s of table t,
-//     i = tags[s];  S[i] += (1/D) sum_d G_d^2;  W[s] -= lr * G / (sqrt(S[i]) + eps)
-// S: one fp32 per TABLE row (state + state_base[t] + i), indexed by the tag of the slot, so it never moves with a row.  A slot
-// is one run and a run has one owning lane group: S[i] is read and written once per launch, without atomics.  Aux slots (misses:
-// transient copies, rewritten by the next forward) are skipped -- no row write, no state update.
-// A lane keeps the NCH = ceil(D4 / LPR) column chunks it owns in registers until the row's sum of squares is known (NCH > 1 only
-// at LPR = 64, D > 256); the sum is reduced over the lane group by a fixed xor butterfly: every lane ends with the same bits.
-// The SGD kernels above are untouched.
-struct AdaArgs {
-    const int64_t* tags;
-    float* state;
-    const int64_t* state_base;      // device [T]: first accumulator of table t
-    float eps;
-};
-
-// the accumulator cell of slot `slot` of table t; -1: an aux slot, or a tag that names no row of the table (an empty way: nothing
-// the batch can have looked up) -- the run is then left alone
-__device__ __forceinline__ int64_t ada_cell(const TableDesc* __restrict__ tab, int t, const AdaArgs& o, uint32_t slot,
-                                            uint32_t aux0, int ways) {
-    if (slot >= aux0) return -1;
-    const uint32_t P = (uint32_t)tab[t].P;          // slot = P * way + set; tags are [P, ways]
-    const uint32_t way = slot / P, set = slot - way * P;
-    const int64_t i = o.tags[tab[t].tag_base + (int64_t)set * ways + way];
-    return (uint64_t)i < (uint64_t)tab[t].n_rows ? o.state_base[t] + i : -1;
-}
-
-// S_new and the rows' step from the run sums g (zero in chunks past D4) -- called by ALL lanes of the group
-template <int LPR, int NCH>
-__device__ __forceinline__ float ada_step(float4 (&w)[NCH], const float4 (&g)[NCH], float s_old, float lr, float eps, int D4) {
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-        ss = fmaf(g[k].x, g[k].x, ss); ss = fmaf(g[k].y, g[k].y, ss);
-        ss = fmaf(g[k].z, g[k].z, ss); ss = fmaf(g[k].w, g[k].w, ss);
-    }
-#pragma unroll
-    for (int m = LPR >> 1; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
-    const float s_new = s_old + ss / (float)(4 * D4);
-    const float scale = lr / (sqrtf(s_new) + eps);
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-        w[k].x = fmaf(-scale, g[k].x, w[k].x); w[k].y = fmaf(-scale, g[k].y, w[k].y);
-        w[k].z = fmaf(-scale, g[k].z, w[k].z); w[k].w = fmaf(-scale, g[k].w, w[k].w);
-    }
-    return s_new;
-}
-
-template <int LPR, bool ARANGE, int NCH>
-__global__ void __launch_bounds__(256) k_bwd_chunks_ada(const TableDesc* __restrict__ tab, int D4,
-                                                        float4* __restrict__ weight, const uint64_t* __restrict__ keys,
-                                                        const int32_t* __restrict__ meta,
-                                                        const int64_t* __restrict__ offsets, int64_t n, int64_t n_bags,
-                                                        int64_t ld_off, const float* __restrict__ grad, int64_t ld_bag,
-                                                        int64_t ld_table, float lr, float4* __restrict__ partials,
-                                                        int64_t pstride, int64_t* __restrict__ longlist,
-                                                        int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
-                                                        int32_t* __restrict__ runend, int64_t kstride,
-                                                        int ways, int aux_add, AdaArgs o) {
-    constexpr int KM = (SEG_CH + LPR - 1) / LPR;
-    const int t = blockIdx.y;
-    const int64_t row_base = tab[t].row_base;
-    const int c = threadIdx.x % LPR;
-    const int gpb = blockDim.x / LPR;
-    const int gid = threadIdx.x / LPR;
-    const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
-    const uint64_t* kt = keys + (int64_t)t * kstride;
-    const int32_t* mt = meta + (int64_t)t * kstride;
-    const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
-    const float* g = grad + (int64_t)t * ld_table;
-    const int64_t* off = ARANGE ? nullptr : offsets + (int64_t)t * ld_off;
-    for (int64_t p = (int64_t)blockIdx.x * gpb + gid; p < n; p += (int64_t)gridDim.x * gpb) {
-        const int r0 = mt[p];
-        if (r0 % SEG_CH) continue;
-        const bool head = r0 == 0;
-        uint32_t slot = (uint32_t)(kt[p] >> 32);
-        if (slot >= aux0) slot += aux_add;
-        int jstop = SEG_CH;
-#pragma unroll
-        for (int m = KM - 1; m >= 0; --m) {
-            const int j = c + m * LPR;
-            const int64_t q = p + 1 + j;
-            const bool stop = (j < SEG_CH) && (q >= n || mt[q] == 0);
-            const unsigned long long b = __ballot(stop);
-            const unsigned long long bits = LPR == 64 ? b : ((b >> gshift) & ((1ull << LPR) - 1));
-            if (bits) jstop = m * LPR + (__ffsll((long long)bits) - 1);
-        }
-        const bool more = jstop == SEG_CH;
-        const int len = more ? SEG_CH : jstop + 1;
-        const bool single = head && !more;
-        // tag -> accumulator -> row: issued early, consumed after the sums
-        const int64_t cell = single ? ada_cell(tab, t, o, slot, aux0, ways) : -1;
-        const float s_old = cell >= 0 ? o.state[cell] : 0.f;
-        float4 w[NCH], acc[NCH];
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            const int cc = c + k * LPR;
-            acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            w[k] = acc[k];
-            if (cc >= D4) continue;
-            if (cell >= 0) w[k] = weight[(row_base + slot) * D4 + cc];
-            int q = 0;
-            for (; q + 4 <= len; q += 4) {
-                int64_t bag[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int64_t pos = (int64_t)(kt[p + q + u] & 0xffffffffull);
-                    bag[u] = ARANGE ? pos : bag_of(off, n_bags, pos);
-                }
-                float4 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(g + bag[u] * ld_bag + cc * 4);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
-            }
-            for (; q < len; ++q) {
-                const int64_t pos = (int64_t)(kt[p + q] & 0xffffffffull);
-                const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
-                const float4 v = *reinterpret_cast<const float4*>(g + bag * ld_bag + cc * 4);
-                acc[k].x += v.x; acc[k].y += v.y; acc[k].z += v.z; acc[k].w += v.w;
-            }
-            if (!single) {
-                const int64_t pi = 2 * (p / SEG_CH) + (head ? 1 : 0);
-                partials[((int64_t)t * pstride + pi) * D4 + cc] = acc[k];
-            }
-        }
-        if (cell >= 0) {        // (uniform over the lane group)
-            const float s_new = ada_step<LPR, NCH>(w, acc, s_old, lr, o.eps, D4);
-#pragma unroll
-            for (int k = 0; k < NCH; ++k)
-                if (c + k * LPR < D4) weight[(row_base + slot) * D4 + c + k * LPR] = w[k];
-            if (c == 0) o.state[cell] = s_new;
-        }
-        if (c == 0) {
-            if (single) {
-                if (touched && cell >= 0) touched[row_base + slot] = 1;
-            } else if (head) {
-                const int li = atomicAdd(longcount, 1);
-                longlist[li] = ((int64_t)t << 40) | p;
-            }
-            if (!single && !more) runend[(int64_t)t * n + (p - r0)] = (int32_t)(p + len);
-        }
-    }
-}
-
-// k_bwd_blocks' two forms (a lone head with RA rows in flight; up to HU heads with four rows each), with the Adagrad epilogue
-template <int LPR, bool ARANGE, int NCH, int HU = 4, int RA = 16>
-__global__ void __launch_bounds__(256) k_bwd_blocks_ada(const TableDesc* __restrict__ tab, int D4,
-                                                        float4* __restrict__ weight, const uint64_t* __restrict__ keys,
-                                                        const int32_t* __restrict__ meta,
-                                                        const int64_t* __restrict__ offsets, int64_t n, int64_t n_bags,
-                                                        int64_t ld_off, const float* __restrict__ grad, int64_t ld_bag,
-                                                        int64_t ld_table, float lr, float4* __restrict__ partials,
-                                                        int64_t pstride, int64_t* __restrict__ longlist,
-                                                        int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
-                                                        int32_t* __restrict__ runend, int64_t kstride, int ways, int aux_add,
-                                                        AdaArgs o) {
-    constexpr int GPB = 256 / LPR;
-    constexpr int SPAN = 2 * SEG_CH;
-    constexpr int NL = SPAN / LPR;
-    static_assert(SEG_CH == 32 && SPAN % LPR == 0, "masks below are 32 / 64 bits wide");
-    __shared__ uint32_t s_pos[GPB][SPAN];
-    __shared__ uint32_t s_slot[GPB][SEG_CH];
-    __shared__ int32_t s_r0[GPB][SEG_CH];
-    const int t = blockIdx.y;
-    const int64_t row_base = tab[t].row_base;
-    const int c = threadIdx.x % LPR;
-    const int gid = threadIdx.x / LPR;
-    const int gshift = ((threadIdx.x & 63) / LPR) * LPR;
-    const uint64_t* kt = keys + (int64_t)t * kstride;
-    const int32_t* mt = meta + (int64_t)t * kstride;
-    const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
-    const float* g = grad + (int64_t)t * ld_table;
-    const int64_t* off = ARANGE ? nullptr : offsets + (int64_t)t * ld_off;
-    const int64_t nblk = (n + SEG_CH - 1) / SEG_CH;
-    for (int64_t blk = (int64_t)blockIdx.x * GPB + gid; blk < nblk; blk += (int64_t)gridDim.x * GPB) {
-        const int64_t p0 = blk * SEG_CH;
-        uint64_t S = 0;
-        uint32_t H = 0;
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int m = 0; m < NL; ++m) {
-            const int j = c + m * LPR;
-            const int64_t q = p0 + j;
-            const bool in = q < n;
-            const uint64_t key = in ? kt[q] : 0ull;
-            const int32_t r = in ? mt[q] : 0;
-            s_pos[gid][j] = (uint32_t)key;
-            if (j < SEG_CH) {
-                uint32_t slot = (uint32_t)(key >> 32);
-                if (slot >= aux0) slot += aux_add;
-                s_slot[gid][j] = slot;
-                s_r0[gid][j] = r;
-            }
-            const unsigned long long b = __ballot(r == 0);
-            const unsigned long long bits = LPR == 64 ? b : ((b >> gshift) & ((1ull << LPR) - 1));
-            S |= bits << (m * LPR);
-            if (m * LPR < SEG_CH) {
-                const unsigned long long hb = __ballot(in && j < SEG_CH && (r % SEG_CH) == 0);
-                const unsigned long long hbits = LPR == 64 ? hb : ((hb >> gshift) & ((1ull << LPR) - 1));
-                H |= (uint32_t)(hbits << (m * LPR));
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int64_t pbucket = (int64_t)t * pstride + 2 * blk;
-        while (H) {
-            const bool alone = (H & (H - 1)) == 0;
-            if (alone) {
-                const int j = __ffs((int)H) - 1;
-                H = 0;
-                const uint64_t rest = S >> (j + 1);
-                const int nxt = rest ? (__ffsll((long long)rest) - 1) : 64;
-                const bool more = nxt >= SEG_CH;
-                const int len = more ? SEG_CH : nxt + 1;
-                const bool head = (S >> j) & 1;
-                const bool single = head && !more;
-                const uint32_t slot = s_slot[gid][j];
-                const int64_t cell = single ? ada_cell(tab, t, o, slot, aux0, ways) : -1;
-                const float s_old = cell >= 0 ? o.state[cell] : 0.f;
-                float4 w[NCH], acc[NCH];
-#pragma unroll
-                for (int k = 0; k < NCH; ++k) {
-                    const int cc = c + k * LPR;
-                    acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    w[k] = acc[k];
-                    if (cc >= D4) continue;
-                    if (cell >= 0) w[k] = weight[(row_base + slot) * D4 + cc];
-                    for (int q = 0; q < len; q += RA) {
-                        float4 v[RA];
-#pragma unroll
-                        for (int u = 0; u < RA; ++u)
-                            if (q + u < len) {
-                                const int64_t pos = s_pos[gid][j + q + u];
-                                const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
-                                v[u] = *reinterpret_cast<const float4*>(g + bag * ld_bag + cc * 4);
-                            }
-#pragma unroll
-                        for (int u = 0; u < RA; ++u)
-                            if (q + u < len) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
-                    }
-                    if (!single) partials[(pbucket + (head ? 1 : 0)) * D4 + cc] = acc[k];
-                }
-                if (cell >= 0) {
-                    const float s_new = ada_step<LPR, NCH>(w, acc, s_old, lr, o.eps, D4);
-#pragma unroll
-                    for (int k = 0; k < NCH; ++k)
-                        if (c + k * LPR < D4) weight[(row_base + slot) * D4 + c + k * LPR] = w[k];
-                    if (c == 0) o.state[cell] = s_new;
-                }
-                if (c == 0) {
-                    const int64_t p = p0 + j;
-                    if (single) {
-                        if (touched && cell >= 0) touched[row_base + slot] = 1;
-                    } else if (head) {
-                        const int li = atomicAdd(longcount, 1);
-                        longlist[li] = ((int64_t)t << 40) | p;
-                    }
-                    if (!single && !more) runend[(int64_t)t * n + (p - s_r0[gid][j])] = (int32_t)(p + len);
-                }
-                continue;
-            }
-            int hj[HU], hlen[HU];
-            bool hhead[HU], hsingle[HU], hmore[HU];
-            uint32_t hslot[HU];
-            int64_t hcell[HU];
-            float hs[HU];
-            int maxlen = 0;
-#pragma unroll
-            for (int u = 0; u < HU; ++u) {
-                hlen[u] = 0; hj[u] = 0; hhead[u] = false; hsingle[u] = false; hmore[u] = false; hslot[u] = 0; hcell[u] = -1;
-                if (H) {
-                    const int j = __ffs((int)H) - 1;
-                    H &= H - 1;
-                    const uint64_t rest = S >> (j + 1);
-                    const int nxt = rest ? (__ffsll((long long)rest) - 1) : 64;
-                    hmore[u] = nxt >= SEG_CH;
-                    hlen[u] = hmore[u] ? SEG_CH : nxt + 1;
-                    hhead[u] = (S >> j) & 1;
-                    hsingle[u] = hhead[u] && !hmore[u];
-                    hj[u] = j;
-                    hslot[u] = s_slot[gid][j];
-                    maxlen = max(maxlen, hlen[u]);
-                    if (hsingle[u]) hcell[u] = ada_cell(tab, t, o, hslot[u], aux0, ways);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < HU; ++u) hs[u] = hcell[u] >= 0 ? o.state[hcell[u]] : 0.f;
-            float4 w[HU][NCH], acc[HU][NCH];
-#pragma unroll
-            for (int k = 0; k < NCH; ++k) {
-                const int cc = c + k * LPR;
-#pragma unroll
-                for (int u = 0; u < HU; ++u) {
-                    acc[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    w[u][k] = acc[u][k];
-                }
-                if (cc >= D4) continue;
-#pragma unroll
-                for (int u = 0; u < HU; ++u)
-                    if (hcell[u] >= 0) w[u][k] = weight[(row_base + hslot[u]) * D4 + cc];
-                for (int q = 0; q < maxlen; q += 4) {
-                    float4 v[HU][4];
-#pragma unroll
-                    for (int u = 0; u < HU; ++u)
-#pragma unroll
-                        for (int kk = 0; kk < 4; ++kk)
-                            if (q + kk < hlen[u]) {
-                                const int64_t pos = s_pos[gid][hj[u] + q + kk];
-                                const int64_t bag = ARANGE ? pos : bag_of(off, n_bags, pos);
-                                v[u][kk] = *reinterpret_cast<const float4*>(g + bag * ld_bag + cc * 4);
-                            }
-#pragma unroll
-                    for (int u = 0; u < HU; ++u)
-#pragma unroll
-                        for (int kk = 0; kk < 4; ++kk)
-                            if (q + kk < hlen[u]) {
-                                acc[u][k].x += v[u][kk].x; acc[u][k].y += v[u][kk].y;
-                                acc[u][k].z += v[u][kk].z; acc[u][k].w += v[u][kk].w;
-                            }
-                }
-#pragma unroll
-                for (int u = 0; u < HU; ++u)
-                    if (hlen[u] != 0 && !hsingle[u]) partials[(pbucket + (hhead[u] ? 1 : 0)) * D4 + cc] = acc[u][k];
-            }
-#pragma unroll
-            for (int u = 0; u < HU; ++u) {
-                if (hcell[u] < 0) continue;
-                const float s_new = ada_step<LPR, NCH>(w[u], acc[u], hs[u], lr, o.eps, D4);
-#pragma unroll
-                for (int k = 0; k < NCH; ++k)
-                    if (c + k * LPR < D4) weight[(row_base + hslot[u]) * D4 + c + k * LPR] = w[u][k];
-                if (c == 0) o.state[hcell[u]] = s_new;
-            }
-            if (c == 0) {
-#pragma unroll
-                for (int u = 0; u < HU; ++u) {
-                    if (hlen[u] == 0) continue;
-                    const int64_t p = p0 + hj[u];
-                    if (hsingle[u]) {
-                        if (touched && hcell[u] >= 0) touched[row_base + hslot[u]] = 1;
-                    } else if (hhead[u]) {
-                        const int li = atomicAdd(longcount, 1);
-                        longlist[li] = ((int64_t)t << 40) | p;
-                    }
-                    if (!hsingle[u] && !hmore[u]) runend[(int64_t)t * n + (p - s_r0[gid][hj[u]])] = (int32_t)(p + hlen[u]);
-                }
-            }
-        }
-    }
-}
-
-template <int LPR, int NCH>
-__global__ void __launch_bounds__(256) k_bwd_long_ada(const TableDesc* __restrict__ tab, int D4,
-                                                      float4* __restrict__ weight, const uint64_t* __restrict__ keys,
-                                                      int64_t n, float lr, const float4* __restrict__ partials,
-                                                      int64_t pstride, const int64_t* __restrict__ longlist,
-                                                      int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
-                                                      const int32_t* __restrict__ runend, int64_t kstride,
-                                                      int ways, int aux_add, AdaArgs o) {
+// heads of long runs add their chunks' partial sums and update the row.  Instantiated for AdaRow (SGD: k_bwd_long_sgd above);
+// aux_total is the SGD touched rule's and is not read here (one argument list for launch_long)
+template <class Row>
+__global__ void __launch_bounds__(256) k_bwd_long(const TableDesc* __restrict__ tab, int D4,
+                                                  float4* __restrict__ weight, const uint64_t* __restrict__ keys,
+                                                  int64_t n, float lr, const float4* __restrict__ partials,
+                                                  int64_t pstride, const int64_t* __restrict__ longlist,
+                                                  int32_t* __restrict__ longcount, uint8_t* __restrict__ touched,
+                                                  int64_t aux_total, const int32_t* __restrict__ runend, int64_t kstride,
+                                                  int ways, int aux_add, AdaArgs o) {
+    constexpr int LPR = Row::LPR;
     const int c = threadIdx.x % LPR;
     const int gpb = blockDim.x / LPR;
     const int gid = threadIdx.x / LPR;
     const int cnt = *longcount;
-    // (the list counter is left zero by the last workgroup through: see k_bwd_long)
+    // The list counter lives in the work buffer: cleared by the first kernel of every prepare (k_sort_chunks) AND left zero by
+    // the last workgroup of this kernel to finish -- every workgroup has read it by then --, so a second apply on one prepare
+    // (a benchmark loop) starts from an empty list too.  longcount[2] counts the workgroups that are through.
     __syncthreads();
     if (threadIdx.x == 0) {
         const int through = atomicAdd(longcount + 2, 1);
@@ -1004,57 +1037,21 @@ __global__ void __launch_bounds__(256) k_bwd_long_ada(const TableDesc* __restric
         uint32_t slot = (uint32_t)(kt[p0] >> 32);
         const uint32_t aux0 = (uint32_t)(tab[t].P * ways);
         if (slot >= aux0) slot += aux_add;
-        const int64_t cell = ada_cell(tab, t, o, slot, aux0, ways);
-        if (cell < 0) continue;             // an aux slot's run: its partial sums are dropped
-        const float s_old = o.state[cell];
+        const RowCtx x = {tab, t, ways, D4, c, aux0, 0 /* first_aux: SgdRow's */, lr, o};
+        Row r;
+        r.find(x, slot, true);
+        if (!r.upd) continue;               // (AdaRow) an aux slot's run: its partial sums are dropped
+        r.read_state(x);
         const int64_t end = runend[(int64_t)t * n + p0];
         const int64_t row = tab[t].row_base + slot;
-        float4 w[NCH], acc[NCH];
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            const int cc = c + k * LPR;
-            acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            w[k] = acc[k];
-            if (cc >= D4) continue;
-            w[k] = weight[row * D4 + cc];
-            // chunk partials in chunk order, sixteen then four loads in flight: k_bwd_long's order
-            int64_t p = p0;
-            for (; p + 15 * SEG_CH < end; p += 16 * SEG_CH) {
-                float4 v[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    const int64_t q = p + u * SEG_CH;
-                    const int64_t pi = 2 * (q / SEG_CH) + (q == p0 ? 1 : 0);
-                    v[u] = partials[((int64_t)t * pstride + pi) * D4 + cc];
-                }
-#pragma unroll
-                for (int u = 0; u < 16; ++u) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
-            }
-            for (; p + 3 * SEG_CH < end; p += 4 * SEG_CH) {
-                float4 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int64_t q = p + u * SEG_CH;
-                    const int64_t pi = 2 * (q / SEG_CH) + (q == p0 ? 1 : 0);
-                    v[u] = partials[((int64_t)t * pstride + pi) * D4 + cc];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { acc[k].x += v[u].x; acc[k].y += v[u].y; acc[k].z += v[u].z; acc[k].w += v[u].w; }
-            }
-            for (; p < end; p += SEG_CH) {
-                const int64_t pi = 2 * (p / SEG_CH) + (p == p0 ? 1 : 0);
-                const float4 v = partials[((int64_t)t * pstride + pi) * D4 + cc];
-                acc[k].x += v.x; acc[k].y += v.y; acc[k].z += v.z; acc[k].w += v.w;
-            }
-        }
-        const float s_new = ada_step<LPR, NCH>(w, acc, s_old, lr, o.eps, D4);
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-            if (c + k * LPR < D4) weight[row * D4 + c + k * LPR] = w[k];
-        if (c == 0) {
-            o.state[cell] = s_new;
-            if (touched) touched[row] = 1;
-        }
+        float4* wrow = weight + row * D4;
+        Row::for_chunks(c, D4, [&](int k, int cc) __attribute__((always_inline)) {
+            r.load(k, wrow + cc);
+            const float4 acc = fold_partials(partials + (int64_t)t * pstride * D4 + cc, D4, p0, end);
+            r.chunk(k, wrow + cc, acc, lr);
+        });
+        r.finish(x, wrow);
+        if (c == 0 && touched && r.flag(x, slot)) touched[row] = 1;
     }
 }
 
@@ -1245,7 +1242,7 @@ static BwdApplyPlan bwd_apply_plan(int T, int D, int64_t n, bool has_offsets, bo
     return p;
 }
 
-// what k_bwd_chunks, k_bwd_blocks and k_bwd_long share.  keys / meta: table 0's sorted list, table t's lies kstride elements further
+// what k_bwd_chunks, k_bwd_blocks and k_bwd_long take.  keys / meta: table 0's sorted list, table t's lies kstride elements further
 // (a batch's own sort: n; a window chunk's: nb * n); aux_add: the sorted slots are phase-0 aux slots, the batch trains on aux region
 // aux_add / aux (0 for a batch's own sort: k_take has added the phase); partials .. runend: the scratch of `work`
 struct BwdApplyArgs {
@@ -1267,85 +1264,60 @@ struct BwdApplyArgs {
     uint8_t* touched;
     int64_t aux_total;
     int skip_once, ways, aux_add;
-    int opt;                    // CDLRM_EMB_OPT_*; ROWWISE_ADAGRAD: the *_ada kernels with `ada`
-    AdaArgs ada;
+    int opt;                    // CDLRM_EMB_OPT_*: SgdRow / AdaRow
+    AdaArgs ada;                // (read by the AdaRow kernels only)
 };
 
 template <auto Kernel>
 static void launch_chunks(dim3 grid, const BwdApplyArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(Kernel, grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, a.n, a.n_bags, a.ld_off,
                        a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist, a.longcount, a.touched, a.aux_total,
-                       a.runend, a.kstride, a.ways, a.aux_add);
+                       a.runend, a.kstride, a.ways, a.aux_add, a.ada);
 }
 template <auto Kernel>
 static void launch_blocks(dim3 grid, const BwdApplyArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(Kernel, grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, a.n, a.n_bags, a.ld_off,
                        a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist, a.longcount, a.touched, a.aux_total,
-                       a.runend, a.skip_once, a.kstride, a.ways, a.aux_add);
+                       a.runend, a.skip_once, a.kstride, a.ways, a.aux_add, a.ada);
 }
-template <int L>
+template <auto Kernel>
 static void launch_long(dim3 grid, const BwdApplyArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_bwd_long<L>, grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.n, a.lr, a.partials, a.pstride,
-                       a.longlist, a.longcount, a.touched, a.aux_total, a.runend, a.kstride, a.ways, a.aux_add);
+    hipLaunchKernelGGL(Kernel, grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.n, a.lr, a.partials, a.pstride, a.longlist,
+                       a.longcount, a.touched, a.aux_total, a.runend, a.kstride, a.ways, a.aux_add, a.ada);
 }
 
 // sums + row updates (the plan's apply kernel), then the long runs
+template <class Row>
+static void bwd_apply_launch_row(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+    if (p.kernel == CDLRM_BWD_APPLY_CHUNKS) {
+        if (p.arange) launch_chunks<k_bwd_chunks<Row, true>>(grid, a, s);
+        else launch_chunks<k_bwd_chunks<Row, false>>(grid, a, s);
+    } else if constexpr (Row::SGD) {
+        // (the SGD update's blocks kernel has its own text; the lean form belongs to the `rest` entries, which take no optimizer)
+        constexpr int L = Row::LPR;
+        if (p.kernel == CDLRM_BWD_APPLY_BLOCKS_LEAN) launch_blocks<k_bwd_blocks_sgd<L, true, 1, 8>>(grid, a, s);
+        else if (p.arange) launch_blocks<k_bwd_blocks_sgd<L, true>>(grid, a, s);
+        else launch_blocks<k_bwd_blocks_sgd<L, false>>(grid, a, s);
+    } else {
+        if (p.arange) launch_blocks<k_bwd_blocks<Row, true>>(grid, a, s);
+        else launch_blocks<k_bwd_blocks<Row, false>>(grid, a, s);
+    }
+    if constexpr (Row::SGD) launch_long<k_bwd_long_sgd<Row::LPR>>(dim3((unsigned)p.long_grid), a, s);
+    else launch_long<k_bwd_long<Row>>(dim3((unsigned)p.long_grid), a, s);
+}
 template <int L>
 static void bwd_apply_launch_lpr(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
-    if (p.kernel == CDLRM_BWD_APPLY_CHUNKS) {
-        if (p.arange) launch_chunks<k_bwd_chunks<L, true>>(grid, a, s);
-        else launch_chunks<k_bwd_chunks<L, false>>(grid, a, s);
-    } else if (p.kernel == CDLRM_BWD_APPLY_BLOCKS_LEAN) {
-        launch_blocks<k_bwd_blocks<L, true, 1, 8>>(grid, a, s);
-    } else {
-        if (p.arange) launch_blocks<k_bwd_blocks<L, true>>(grid, a, s);
-        else launch_blocks<k_bwd_blocks<L, false>>(grid, a, s);
+    if (a.opt != CDLRM_EMB_OPT_ROWWISE_ADAGRAD) return bwd_apply_launch_row<SgdRow<L>>(p, a, s);
+    // column chunks per lane: 1 up to D = 256 (LPR >= D4); 2 / 4 at LPR = 64 (bwd_apply has checked D <= 1024)
+    if constexpr (L == 64) {
+        const int nch = (int)cdiv(a.D4, L);
+        if (nch > 2) return bwd_apply_launch_row<AdaRow<L, 4>>(p, a, s);
+        if (nch == 2) return bwd_apply_launch_row<AdaRow<L, 2>>(p, a, s);
     }
-    launch_long<L>(dim3((unsigned)p.long_grid), a, s);
-}
-// the same plan with the row-wise Adagrad kernels: a lane holds NCH column chunks of its row
-template <int L, int NCH>
-static void bwd_apply_launch_ada(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
-    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
-#define ADA_CHUNKS(AR)                                                                                                       \
-    hipLaunchKernelGGL((k_bwd_chunks_ada<L, AR, NCH>), grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, \
-                       a.n, a.n_bags, a.ld_off, a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist,        \
-                       a.longcount, a.touched, a.runend, a.kstride, a.ways, a.aux_add, a.ada)
-#define ADA_BLOCKS(AR)                                                                                                       \
-    hipLaunchKernelGGL((k_bwd_blocks_ada<L, AR, NCH>), grid, dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.meta, a.offsets, \
-                       a.n, a.n_bags, a.ld_off, a.grad, a.ld_bag, a.ld_table, a.lr, a.partials, a.pstride, a.longlist,        \
-                       a.longcount, a.touched, a.runend, a.kstride, a.ways, a.aux_add, a.ada)
-    if (p.kernel == CDLRM_BWD_APPLY_CHUNKS) {
-        if (p.arange) ADA_CHUNKS(true);
-        else ADA_CHUNKS(false);
-    } else {                    // (the lean form belongs to the `rest` entries, which take no optimizer)
-        if (p.arange) ADA_BLOCKS(true);
-        else ADA_BLOCKS(false);
-    }
-#undef ADA_CHUNKS
-#undef ADA_BLOCKS
-    hipLaunchKernelGGL((k_bwd_long_ada<L, NCH>), dim3((unsigned)p.long_grid), dim3(256), 0, s, a.tab, a.D4, a.weight, a.keys, a.n,
-                       a.lr, a.partials, a.pstride, a.longlist, a.longcount, a.touched, a.runend, a.kstride, a.ways, a.aux_add,
-                       a.ada);
+    bwd_apply_launch_row<AdaRow<L, 1>>(p, a, s);
 }
 static int bwd_apply_launch(const BwdApplyPlan& p, const BwdApplyArgs& a, hipStream_t s) {
-    if (a.opt == CDLRM_EMB_OPT_ROWWISE_ADAGRAD) {
-        // column chunks per lane: 1 up to D = 256 (LPR >= D4); 2 / 4 at LPR = 64 (bwd_apply has checked D <= 1024)
-        const int nch = (int)cdiv(a.D4, p.lpr);
-        switch (p.lpr) {
-            case 4: bwd_apply_launch_ada<4, 1>(p, a, s); break;
-            case 8: bwd_apply_launch_ada<8, 1>(p, a, s); break;
-            case 16: bwd_apply_launch_ada<16, 1>(p, a, s); break;
-            case 32: bwd_apply_launch_ada<32, 1>(p, a, s); break;
-            default:
-                if (nch <= 1) bwd_apply_launch_ada<64, 1>(p, a, s);
-                else if (nch == 2) bwd_apply_launch_ada<64, 2>(p, a, s);
-                else bwd_apply_launch_ada<64, 4>(p, a, s);
-        }
-        CDLRM_LAUNCH_CHECK();
-        return 0;
-    }
 #define APPLY_CALL(L) bwd_apply_launch_lpr<L>(p, a, s)
     DISPATCH_LPR(p.lpr, APPLY_CALL)
 #undef APPLY_CALL
@@ -1469,7 +1441,7 @@ extern "C" int cdlrm_embbag_bwd_apply_sorted(cdlrm_ctx* ctx, int64_t n, const fl
 }
 
 // The two applies that take an optimizer: opt = CDLRM_EMB_OPT_SGD launches exactly the sibling's plan (state unused);
-// CDLRM_EMB_OPT_ROWWISE_ADAGRAD the *_ada kernels on the same plan.
+// CDLRM_EMB_OPT_ROWWISE_ADAGRAD the same plan's kernels with the AdaRow update.
 extern "C" int cdlrm_embbag_bwd_apply_opt(cdlrm_ctx* ctx, const int64_t* offsets, int64_t n, int64_t n_bags, int64_t ld_off,
                                           const float* grad, int64_t ld_bag, int64_t ld_table, float lr, void* work,
                                           uint8_t* touched, int32_t opt, float eps, float* state, const int64_t* state_base,

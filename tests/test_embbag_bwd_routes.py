@@ -177,6 +177,8 @@ CASES = [
          anchors=seq(0, LOOP_RUNS) + [(12 * TILE + 1, 3), (8180, 30)] + SHARED_BUCKET(12288) + [(16383, 1)]),
     Case("n16385_d384_cc2", 16385, 384, "apply", "8192x8 c3 m2 seg A / chunks ar l64", pitch="gap",
          anchors=seq(32, EDGE_RUNS) + [(8190, 549), (16384, 1)]),
+    Case("n1025_d1024_cc4", 1025, 1024, "apply", "2048x2 c1 m0 sort A / chunks ar l64",
+         anchors=seq(0, EDGE_RUNS) + seq(512, LOOP_RUNS[:1])),
     Case("n65536_d16", 65536, 16, "sgd", "8192x8 c8 m3 seg B / chunks ar l4", pitch="engine",
          anchors=seq(0, LOOP_RUNS) + [(8180, 30), (16380, 10), (32768 - 1, 2)] + SHARED_BUCKET(40000) + [(10 * TILE - 1, 2)]
          + [(65536 - 65, 65)]),

@@ -1,8 +1,9 @@
 """Row-wise Adagrad for the cached embedding rows on the MI355X:
 
-  1. the kernels behind cdlrm_embbag_bwd_apply_opt / _apply_sorted_opt (k_bwd_chunks_ada, both forms of k_bwd_blocks_ada,
-     k_bwd_long_ada) against a float64 reference on the exact fp32 run sums, which the SGD sibling yields on zeroed rows with
-     lr = -1 (the two entries sum in the same order):
+  1. the kernels behind cdlrm_embbag_bwd_apply_opt / _apply_sorted_opt (k_bwd_chunks, both forms of k_bwd_blocks and k_bwd_long
+     with the AdaRow update, one to four column chunks per lane: D = 16 .. 1024) against a float64 reference on the exact fp32
+     run sums, which the SGD sibling (k_bwd_chunks with the SgdRow update, k_bwd_blocks_sgd, k_bwd_long_sgd: the same sums in
+     the same order) yields on zeroed rows with lr = -1:
          |S - S64| <= (D + 4) u S64,   |W - W64| <= (D/2 + 16) u |lr G / std| + u |W64|        (u = 2^-24)
      aux rows and the accumulators of indices the batch did not look up bit-unchanged, a second launch the same bits, opt = 0
      the sibling's bits;
@@ -159,11 +160,13 @@ KERNEL_CASES = ([(D, 1500, "edges", entry, form, False) for D in (16, 128, 256, 
                  for form in ("chunks", "blocks")]
                 + [(D, 1500, "edges", "apply", form, True) for D in (16, 128, 256, 512) for form in ("chunks", "blocks")]
                 + [(128, n, "random", "apply", form, False) for n in (1, 255, 256, 8193) for form in ("chunks", "blocks")]
-                + [(512, 8193, "random", "sorted", "chunks", False), (16, 255, "random", "apply", "blocks", True)])
+                + [(512, 8193, "random", "sorted", "chunks", False), (16, 255, "random", "apply", "blocks", True)]
+                # D = 1024: four column chunks per lane (NCH = 4 at LPR = 64), the widest row the Adagrad policy takes
+                + [(1024, 1500, "edges", entry, form, False) for entry in ("apply", "sorted") for form in ("chunks", "blocks")])
+KERNEL_IDS = ["d%d_n%d_%s_%s_%s%s" % (c[0], c[1], c[2], c[3], c[4], "_bags" if c[5] else "") for c in KERNEL_CASES]
 
 
-@pytest.mark.parametrize("D,n,kind,entry,form,bags", KERNEL_CASES,
-                         ids=["d%d_n%d_%s_%s_%s%s" % (c[0], c[1], c[2], c[3], c[4], "_bags" if c[5] else "") for c in KERNEL_CASES])
+@pytest.mark.parametrize("D,n,kind,entry,form,bags", KERNEL_CASES, ids=KERNEL_IDS)
 def test_kernels_against_float64(ops, D, n, kind, entry, form, bags):
     c = Case(ops, D, n, kind, bags)
     phase = 1 if entry == "sorted" else 0

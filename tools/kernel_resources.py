@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel resource table of one HIP source, from the compiler's own remarks (no GPU, nothing is run):
 
-    python tools/kernel_resources.py cdlrm_amd/csrc/embbag_bwd.hip [--match _ada] [--out profiles/NAME.txt] [--title TEXT]
+    python tools/kernel_resources.py cdlrm_amd/csrc/embbag_bwd.hip [--match AdaRow] [--out profiles/NAME.txt] [--title TEXT]
 
 compiles the file with -Rpass-analysis=kernel-resource-usage for gfx950 and prints one line per kernel: VGPRs, AGPRs, SGPRs,
 scratch bytes per lane, occupancy in waves per SIMD, static LDS bytes per workgroup.  Exit status 1 if a selected kernel uses
