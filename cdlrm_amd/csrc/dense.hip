@@ -1684,6 +1684,7 @@ extern "C" int cdlrm_interact_fwd(const float* feat, int64_t B, int32_t F, int32
         return ia_with_d4(p.d4, [&](auto d4) {
             return ia_launch<k_interact_fwd_p<decltype(d4)::value>>(p, stream, false, feat, B, F, itself, R, ld_r);
         });
+    CDLRM_REQUIRE(p.lds <= 160 * 1024, "LDS budget");
     return ia_launch<k_interact_fwd>(p, stream, false, feat, B, F, D, itself, R, ld_r);
 }
 
@@ -1720,7 +1721,7 @@ extern "C" int cdlrm_interact_route(int32_t op, int64_t B, int32_t F, int32_t D,
     const IaPlan p = interact_plan(op, B, F, D, itself, ld_r, aligned & 1, aligned & 2);
     // what the entry point of `op` refuses
     if (op == IA_FWD) CDLRM_REQUIRE(ld_r >= width, "alignment / ld_r");
-    if (op == IA_BWD && p.family == CDLRM_IA_GENERIC) CDLRM_REQUIRE(p.lds <= 160 * 1024, "LDS budget");
+    if (op <= IA_BWD && p.family == CDLRM_IA_GENERIC) CDLRM_REQUIRE(p.lds <= 160 * 1024, "LDS budget");
     if (op >= IA_GATHER_FWD) {
         CDLRM_REQUIRE(p.family, "unsupported shape (D in 32/64/128/256, 16 < T + 1 <= 32)");
         CDLRM_REQUIRE(ld_r % 4 == 0 && (aligned & 1) && ld_r >= ((width + 3) & ~3) && (op == IA_GATHER_FWD || (aligned & 2)),

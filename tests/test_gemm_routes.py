@@ -367,9 +367,10 @@ STEP_CONFIGS = {   # layer shapes of bench.py's configurations (c5 = c3's shapes
 }
 
 
-def _record_step(config, Bsz):
+def _record_step(config, Bsz, itself=False, interactions=None):
     """One TrainEngine step on the CPU test double (tests/fake_ops.py, world 1, 26 small tables) with linear_fwd / linear_bwd
-    wrapped: their real arguments."""
+    wrapped: their real arguments.  `interactions` (a list; tests/test_interact_routes.py): interact_fwd / interact_bwd are wrapped
+    too and their arguments appended to it."""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import fake_ops
     import cdlrm_amd.engine as engine
@@ -395,6 +396,19 @@ def _record_step(config, Bsz):
     shim = Ops()
     shim.__dict__.update({k: getattr(fake_ops, k) for k in dir(fake_ops) if not k.startswith("__")})
     shim.linear_fwd, shim.linear_bwd = lf, lb
+    if interactions is not None:
+        def al(t):
+            return t.data_ptr() % 16 == 0
+
+        def xf(feat, its, R, stream=None):
+            interactions.append(("fwd", feat.shape[1], feat.shape[2], int(bool(its)), None, R.stride(0), al(R), True))
+            return fake_ops.interact_fwd(feat, its, R, stream)
+
+        def xb(feat, dR, its, dfeat, stream=None, x_act=0):
+            interactions.append(("bwd", feat.shape[1], feat.shape[2], int(bool(its)), x_act, dR.stride(0), al(dR), al(dfeat)))
+            return fake_ops.interact_bwd(feat, dR, its, dfeat, stream, x_act)
+
+        shim.interact_fwd, shim.interact_bwd = xf, xb
     saved = (engine.ops, Mo.ops, Mo.Embedding_Table_Group.__dict__.get("device_pointers"))
     engine.ops, Mo.ops = shim, shim
     Mo.Embedding_Table_Group.device_pointers = lambda self: self._fake_ptrs
@@ -402,7 +416,7 @@ def _record_step(config, Bsz):
         T, rows, D = 26, 40, cfg["D"]
         ln_emb = np.array([rows] * T)
         nf = T + 1
-        ln_top = np.array([D + nf * (nf - 1) // 2] + cfg["top"])
+        ln_top = np.array([D + (nf * (nf + 1) // 2 if itself else nf * (nf - 1) // 2)] + cfg["top"])
         host = O.init_host_tables([int(x) for x in ln_emb], D)
         eg = Mo.Embedding_Table_Group(D, ln_emb, init="empty_meta")
         for k in range(T):
@@ -412,7 +426,7 @@ def _record_step(config, Bsz):
         np.random.seed(1)
         torch.manual_seed(1)
         cg = Mo.Embedding_Table_Cache_Group(D, ln_emb, 64, Bsz, 4)
-        dl = Mo.DLRM_Net(np.array(cfg["bot"]), ln_top, "dot", False, True, -1, ln_top.size - 2, 0.0)
+        dl = Mo.DLRM_Net(np.array(cfg["bot"]), ln_top, "dot", bool(itself), True, -1, ln_top.size - 2, 0.0)
         eng = engine.TrainEngine(cg, dl, eg, lr=0.1, lr_embeds=0.1)
         pipe = engine.WindowPipeline(cg, eg, Bsz, parity_rng=True)
         rng = np.random.RandomState(0)
