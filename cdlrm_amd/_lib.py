@@ -144,6 +144,8 @@ PROTOTYPES = {
     "cdlrm_mlp_wgrad_work_bytes_ex": (c_u64, [c_i32, c_i64, vp, vp, c_i32]),
     "cdlrm_mlp_wgrad_ex": (C.c_int, [c_i32, vp, vp, vp, vp, vp, vp, c_i64, vp, vp, c_i32, vp, vp]),
     "cdlrm_mlp_wgrad_sgd_ex": (C.c_int, [c_i32, vp, vp, vp, vp, vp, vp, vp, vp, c_f32, c_i64, vp, vp, c_i32, vp, vp]),
+    "cdlrm_mlp_wgrad_opt_ex": (C.c_int, [c_i32, vp, vp, vp, vp, vp, vp, vp, vp, c_f32, c_i64, vp, vp, c_i32, c_i32, c_f32, vp, vp,
+                                         vp, vp]),
     "cdlrm_mlp_wgrad_route": (C.c_int, [c_i32, vp, vp, vp, vp, vp, vp, c_i64, vp, vp, c_i32, c_i32, C.POINTER(GemmRoute)]),
     "cdlrm_bce_fwd_bwd": (C.c_int, [vp, vp, c_i64, vp, vp, c_i32, vp]),
     "cdlrm_loss_fwd_bwd": (C.c_int, [vp, vp, c_i64, c_i32, C.c_float, C.c_float, C.c_float, vp, vp, vp, c_i32, vp]),
@@ -154,6 +156,8 @@ PROTOTYPES = {
     "cdlrm_sgd_step2": (C.c_int, [vp, vp, c_i64, c_i64, c_i64, c_i64, C.c_float, vp]),
     "cdlrm_act_bwd": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, c_i32, c_i32, vp]),
     "cdlrm_sgd_step": (C.c_int, [vp, vp, c_i64, c_f32, vp]),
+    "cdlrm_dense_opt_step": (C.c_int, [vp, vp, vp, c_i64, c_f32, c_i32, c_f32, vp]),
+    "cdlrm_dense_opt_step2": (C.c_int, [vp, vp, vp, c_i64, c_i64, c_i64, c_i64, C.c_float, c_i32, c_f32, vp]),
     "cdlrm_scale_div": (C.c_int, [vp, c_i64, c_f32, vp]),
     "cdlrm_scatter_rows": (C.c_int, [vp, vp, vp, c_i64, c_i32, C.c_int, vp]),
     "cdlrm_blend_rows": (C.c_int, [vp, vp, vp, c_i64, c_i32, vp, vp]),

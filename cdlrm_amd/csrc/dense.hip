@@ -197,15 +197,38 @@ __global__ void __launch_bounds__(256) k_act_grad(const float* __restrict__ Y, i
     }
 }
 
+// The dense optimizers, as what ONE gradient element g does to its parameter p (and, STATE, to its accumulator S): the template
+// parameter of the reductions and of the element-wise kernels below (as SgdRow / AdaRow are of the embedding apply).
+//   SgdStep       p = fma(-lr, g, p)                                   optim.SGD, main_no_ddp.py:375, 415; S is not touched
+//   AdagradStep   S = fma(g, g, S);  p = fma(-lr, g / (sqrt(S) + eps), p)     opt-in (CDLRM_DENSE_OPT_ADAGRAD):
+//                 optim.Adagrad with lr_decay = weight_decay = initial_accumulator_value = 0, one fp32 S per parameter.  The
+//                 quotient is taken of g, not of lr: g = 0 on S = 0 gives 0 / eps = 0 for every eps > 0, never inf * 0.
+struct SgdStep {
+    static constexpr bool STATE = false;
+    float lr;
+    __device__ __forceinline__ float one(float g, float p, float&) const { return fmaf(-lr, g, p); }
+};
+struct AdagradStep {
+    static constexpr bool STATE = true;
+    float lr, eps;
+    __device__ __forceinline__ float one(float g, float p, float& S) const {
+        S = fmaf(g, g, S);
+        return fmaf(-lr, g / (sqrtf(S) + eps), p);
+    }
+};
+
 // Two reductions in one job (dW slabs and the bias-gradient partials of the same layer): logical blocks [0, gxa) work
 // on part A, the rest on part B.  Fixed summation order (slab 0, 1, 2, ...): reproducible; 4 slabs in flight.
-// (pA / pB: the parameters the gradients belong to, updated in the same pass -- p -= lr * g, the dense SGD step -- when the
-//  caller has no exchange between the two: cdlrm_mlp_wgrad_sgd; NULL: gradients only)
+// (pA / pB: the parameters the gradients belong to, updated in the same pass -- Step, the dense optimizer's step -- when the
+//  caller has no exchange between the two: cdlrm_mlp_wgrad_sgd / _opt; NULL: gradients only.  sA / sB: their accumulators,
+//  read by a Step with STATE only)
+template <class Step = SgdStep>
 __device__ __forceinline__ void reduce_slabs_body(int bid, const float* __restrict__ partA, int64_t countA, int splitsA,
                                                   float* __restrict__ outA, int gxa, const float* __restrict__ partB,
                                                   int64_t countB, int splitsB, float* __restrict__ outB,
                                                   float (*red)[64], float* __restrict__ pA = nullptr,
-                                                  float* __restrict__ pB = nullptr, float lr = 0.f, int novec = 0) {
+                                                  float* __restrict__ pB = nullptr, Step st = Step{}, int novec = 0,
+                                                  float* __restrict__ sA = nullptr, float* __restrict__ sB = nullptr) {
     if (bid >= gxa) {
         // part B (bias gradient): few elements, many partials -> 4 lanes per element, each summing every 4th
         // partial, combined in a fixed order through LDS
@@ -219,11 +242,18 @@ __device__ __forceinline__ void reduce_slabs_body(int bid, const float* __restri
         if (sub == 0 && e < countB) {
             const float g = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
             outB[e] = g;
-            if (pB) pB[e] = fmaf(-lr, g, pB[e]);
+            if (pB) {
+                float S = 0.f;
+                if constexpr (Step::STATE) S = sB[e];
+                pB[e] = st.one(g, pB[e], S);
+                if constexpr (Step::STATE) sB[e] = S;
+            }
         }
         return;
     }
-    if (!novec && (countA & 3) == 0 && ((((uintptr_t)partA | (uintptr_t)outA | (uintptr_t)pA) & 15) == 0)) {
+    uintptr_t al = (uintptr_t)partA | (uintptr_t)outA | (uintptr_t)pA;
+    if constexpr (Step::STATE) al |= (uintptr_t)sA;
+    if (!novec && (countA & 3) == 0 && (al & 15) == 0) {
         // 16-byte version (round 4): a thread owns four consecutive elements, eight slabs in flight; per element the same
         // additions in the same order as the scalar loop below (slab 0, 1, 2, ...): bit-identical
         const int64_t n4 = countA >> 2;
@@ -234,6 +264,9 @@ __device__ __forceinline__ void reduce_slabs_body(int bid, const float* __restri
             //  at the end of a launch that sits on the training queue of every step)
             float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
             if (pA) q = reinterpret_cast<const float4*>(pA)[e];
+            float4 S = make_float4(0.f, 0.f, 0.f, 0.f);      // (the state word travels with them too)
+            if constexpr (Step::STATE)
+                if (pA) S = reinterpret_cast<const float4*>(sA)[e];
             __builtin_amdgcn_sched_barrier(0);
             int z = 0;
             for (; z + 8 <= splitsA; z += 8) {
@@ -249,8 +282,9 @@ __device__ __forceinline__ void reduce_slabs_body(int bid, const float* __restri
             }
             reinterpret_cast<float4*>(outA)[e] = s;
             if (pA) {
-                q.x = fmaf(-lr, s.x, q.x); q.y = fmaf(-lr, s.y, q.y); q.z = fmaf(-lr, s.z, q.z); q.w = fmaf(-lr, s.w, q.w);
+                q.x = st.one(s.x, q.x, S.x); q.y = st.one(s.y, q.y, S.y); q.z = st.one(s.z, q.z, S.z); q.w = st.one(s.w, q.w, S.w);
                 reinterpret_cast<float4*>(pA)[e] = q;
+                if constexpr (Step::STATE) reinterpret_cast<float4*>(sA)[e] = S;
             }
         }
         return;
@@ -265,7 +299,12 @@ __device__ __forceinline__ void reduce_slabs_body(int bid, const float* __restri
         }
         for (; z < splitsA; ++z) s += partA[(int64_t)z * countA + e];
         outA[e] = s;
-        if (pA) pA[e] = fmaf(-lr, s, pA[e]);
+        if (pA) {
+            float S = 0.f;
+            if constexpr (Step::STATE) S = sA[e];
+            pA[e] = st.one(s, pA[e], S);
+            if constexpr (Step::STATE) sA[e] = S;
+        }
     }
 }
 
@@ -298,7 +337,25 @@ __global__ void __launch_bounds__(256) k_reduce_group(ReduceGroup grp) {
         if (q < grp.n && blockIdx.x >= grp.first[q]) p = q;
     const ReduceJob& r = grp.j[p];
     reduce_slabs_body((int)(blockIdx.x - grp.first[p]), r.partA, r.countA, r.splits, r.outA, r.gxa, r.partB, r.countB,
-                      r.splits, r.outB, red, r.pA, r.pB, r.lr, r.novec);
+                      r.splits, r.outB, red, r.pA, r.pB, SgdStep{r.lr}, r.novec);
+}
+// ... with the Adagrad step in place of the SGD step (cdlrm_mlp_wgrad_opt_ex): the same jobs, their accumulators beside them.
+// (A kernel of its own, not a run-time branch in k_reduce_group: the SGD kernel keeps its argument block and its registers,
+//  profiles/dense_adagrad_kernel_resources.txt.)
+struct ReduceState {
+    float* sA[GEMM_GROUP_MAX];
+    float* sB[GEMM_GROUP_MAX];
+    float eps;
+};
+__global__ void __launch_bounds__(256) k_reduce_group_adagrad(ReduceGroup grp, ReduceState st) {
+    __shared__ float red[4][64];
+    int p = 0;
+#pragma unroll
+    for (int q = 1; q < GEMM_GROUP_MAX; ++q)
+        if (q < grp.n && blockIdx.x >= grp.first[q]) p = q;
+    const ReduceJob& r = grp.j[p];
+    reduce_slabs_body<AdagradStep>((int)(blockIdx.x - grp.first[p]), r.partA, r.countA, r.splits, r.outA, r.gxa, r.partB, r.countB,
+                                   r.splits, r.outB, red, r.pA, r.pB, AdagradStep{r.lr, st.eps}, r.novec, st.sA[p], st.sB[p]);
 }
 
 // ---- weight gradients: dW = dZ^T X over the batch, db = column sums of dZ -------------------------------------------------
@@ -597,32 +654,54 @@ extern "C" uint64_t cdlrm_mlp_wgrad_work_bytes(int32_t n_layers, int64_t M, cons
 }
 
 __global__ void __launch_bounds__(256) k_sgd(float* __restrict__ p, const float* __restrict__ g, int64_t n, float lr);
+static void dense_adagrad_launch(float* p, const float* g, float* st, int64_t off0, int64_t n0, int64_t off1, int64_t n1, float lr,
+                                 float eps, hipStream_t s);
 
-// the reductions of `jobs` (dW slabs + bias-gradient partials, the SGD step inside where a job carries parameters): one grouped
-// launch per GEMM_GROUP_MAX layers
-static void launch_reduce_jobs(const std::vector<ReduceJob>& jobs, hipStream_t s) {
+// the Adagrad mode of cdlrm_mlp_wgrad_opt_ex: the layers' accumulators (host arrays, as P_w / P_b) and eps
+struct DenseAdagrad {
+    float* const* SW;
+    float* const* Sb;
+    float eps;
+};
+
+// the reductions of `jobs` (dW slabs + bias-gradient partials, the optimizer's step inside where a job carries parameters): one
+// grouped launch per GEMM_GROUP_MAX layers.  ada (with `layer`, the layer of each job): the Adagrad step, else the SGD step
+static void launch_reduce_jobs(const std::vector<ReduceJob>& jobs, hipStream_t s, const DenseAdagrad* ada = nullptr,
+                               const std::vector<int>* layer = nullptr) {
     for (size_t q0 = 0; q0 < jobs.size(); q0 += GEMM_GROUP_MAX) {
         ReduceGroup red;
+        ReduceState st;
         memset(&red, 0, sizeof(red));
+        memset(&st, 0, sizeof(st));
         unsigned rblocks = 0;
         for (size_t q = q0; q < jobs.size() && q < q0 + GEMM_GROUP_MAX; ++q) {
             red.first[red.n] = rblocks;
             red.j[red.n] = jobs[q];
+            if (ada) {
+                st.sA[red.n] = ada->SW[(*layer)[q]];
+                st.sB[red.n] = jobs[q].pB ? ada->Sb[(*layer)[q]] : nullptr;
+            }
             rblocks += (unsigned)(jobs[q].gxa + cdiv(jobs[q].countB, 64));
             red.n++;
         }
         red.first[red.n] = rblocks;
-        hipLaunchKernelGGL(k_reduce_group, dim3(rblocks), dim3(256), 0, s, red);
+        if (ada) {
+            st.eps = ada->eps;
+            hipLaunchKernelGGL(k_reduce_group_adagrad, dim3(rblocks), dim3(256), 0, s, red, st);
+        } else {
+            hipLaunchKernelGGL(k_reduce_group, dim3(rblocks), dim3(256), 0, s, red);
+        }
     }
 }
 
 // All of cdlrm_mlp_wgrad*: build the layout, then either translate it into routes (rout: the route query, one entry per layer,
 // nothing launched, no pointer read) or walk it and launch.  P_w / P_b (both or neither): the layers' parameters, stepped by
-// -lr * gradient in the reduction pass (layers whose gradient needs no reduction: one elementwise launch behind it).
+// -lr * gradient in the reduction pass (layers whose gradient needs no reduction: one elementwise launch behind it) -- or, ada
+// given, by the Adagrad step at the same places.
 static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
                          const int64_t* ld_dz, float* const* dW, float* const* db, int64_t M, const int32_t* N,
                          const int32_t* K, int32_t flags, void* work, void* stream, float* const* P_w, float* const* P_b, float lr,
-                         cdlrm_gemm_route* rout, int n_cu) {
+                         cdlrm_gemm_route* rout, int n_cu, const DenseAdagrad* ada = nullptr) {
     CDLRM_REQUIRE((flags & ~BF16_MODES) == 0, "bad flags");
     CDLRM_REQUIRE(bf16_planes(flags) >= 0, "CDLRM_GEMM_BF16 and CDLRM_GEMM_BF16X3 exclude each other");
     CDLRM_REQUIRE(n_layers >= 0 && (n_layers == 0 || (X && ld_x && dZ && ld_dz && dW && db && N && K)) && M >= 1,
@@ -663,6 +742,7 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
                   "work must be 256-byte aligned");
     std::vector<GemmArgs> probs;
     std::vector<ReduceJob> jobs;
+    std::vector<int> job_layer;
     probs.reserve(p.L.size());
     jobs.reserve(p.L.size());
     // ... and into its slabs, with their reduction queued in `jobs`, where it has any
@@ -671,19 +751,27 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
             const WgradLayer& l = p.L[i];
             if (l.family != f) continue;
             probs.push_back(problem(i));
-            if (l.zs > 1)
+            if (l.zs > 1) {
                 jobs.push_back(wgrad_slabbed(probs.back(), work, l.slabs, l.cs, l.zs, l.gxa, dW[i], db[i], P_w ? P_w[i] : nullptr,
                                              (P_w && P_b) ? P_b[i] : nullptr, lr));
+                job_layer.push_back(i);
+            }
         }
     };
     // the reductions queued so far; then the dense SGD step (W -= lr dW, b -= lr db) of the layers of these families that had no
-    // reduction pass to ride in
+    // reduction pass to ride in (ada: their Adagrad step, launch for launch)
     auto finish = [&](bool bf) -> int {
-        launch_reduce_jobs(jobs, s);
+        launch_reduce_jobs(jobs, s, ada, &job_layer);
         jobs.clear();
+        job_layer.clear();
         for (int i = 0; P_w && i < n_layers; ++i) {
             if ((p.L[i].family == WG_BF16) != bf || p.L[i].zs > 1) continue;
             const int64_t cnt = (int64_t)N[i] * K[i];
+            if (ada) {
+                dense_adagrad_launch(P_w[i], dW[i], ada->SW[i], 0, cnt, 0, 0, lr, ada->eps, s);
+                if (db[i] && P_b && P_b[i]) dense_adagrad_launch(P_b[i], db[i], ada->Sb[i], 0, N[i], 0, 0, lr, ada->eps, s);
+                continue;
+            }
             int64_t gx = cdiv(cnt, 256);
             if (gx > 2048) gx = 2048;
             hipLaunchKernelGGL(k_sgd, dim3((unsigned)gx), dim3(256), 0, s, P_w[i], (const float*)dW[i], cnt, lr);
@@ -762,6 +850,24 @@ extern "C" int cdlrm_mlp_wgrad_sgd_ex(int32_t n_layers, const float* const* X, c
                                       void* work, void* stream) {
     CDLRM_REQUIRE(n_layers == 0 || (W && b), "parameters missing");
     return mlp_wgrad_run(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, W, b, lr, nullptr, 0);
+}
+
+// cdlrm_mlp_wgrad_sgd_ex with the dense optimizer named: opt = CDLRM_DENSE_OPT_SGD launches exactly that call's plan (eps, SW, Sb
+// not read); CDLRM_DENSE_OPT_ADAGRAD the same plan with the Adagrad step wherever the SGD step rides (the reductions' bias part,
+// 16-byte and scalar paths; the element-wise launches of the layers without a reduction).  dW / db are left as by either sibling.
+extern "C" int cdlrm_mlp_wgrad_opt_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                                      const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W,
+                                      float* const* b, float lr, int64_t M, const int32_t* N, const int32_t* K, int32_t flags,
+                                      int32_t opt, float eps, float* const* SW, float* const* Sb, void* work, void* stream) {
+    CDLRM_REQUIRE(opt == CDLRM_DENSE_OPT_SGD || opt == CDLRM_DENSE_OPT_ADAGRAD, "opt: CDLRM_DENSE_OPT_*");
+    if (opt == CDLRM_DENSE_OPT_SGD)
+        return cdlrm_mlp_wgrad_sgd_ex(n_layers, X, ld_x, dZ, ld_dz, dW, db, W, b, lr, M, N, K, flags, work, stream);
+    CDLRM_REQUIRE(n_layers == 0 || (W && b && db && SW && Sb), "parameters or accumulators missing");
+    CDLRM_REQUIRE(eps > 0.f, "eps > 0: the step divides by sqrt(S) + eps and S starts at zero");
+    for (int i = 0; i < n_layers; ++i)
+        CDLRM_REQUIRE(W[i] && SW[i] && (!(b[i] && db[i]) || Sb[i]), "a stepped parameter without its accumulator");
+    const DenseAdagrad ada = {SW, Sb, eps};
+    return mlp_wgrad_run(n_layers, X, ld_x, dZ, ld_dz, dW, db, M, N, K, flags, work, stream, W, b, lr, nullptr, 0, &ada);
 }
 
 // flags = 0
@@ -2276,6 +2382,98 @@ extern "C" int cdlrm_sgd_step(float* param, const float* grad, int64_t n, float 
     int64_t gx = cdiv(n, 256);
     if (gx > 2048) gx = 2048;
     hipLaunchKernelGGL(k_sgd, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, param, grad, n, lr);
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the dense optimizer over flat ranges (opt-in Adagrad): the siblings of cdlrm_sgd_step / cdlrm_sgd_step2 -----
+// One range [lo, lo + n) of the flat buffers as the kernel walks it: `head` scalar elements up to the first 16-byte boundary,
+// `vec` groups of four from there, `tail` scalar elements behind them (head + 4 vec + tail = n).
+struct OptRange {
+    int64_t lo, head, vec, tail;
+};
+// k: the buffers' common offset from a 16-byte boundary in elements, or -1 where they have none (everything scalar)
+static inline OptRange opt_range(int64_t lo, int64_t n, int k) {
+    OptRange r = {lo, n, 0, 0};
+    if (k < 0) return r;
+    const int64_t head = (4 - ((lo + k) & 3)) & 3;
+    if (head >= n) return r;
+    r.head = head;
+    r.vec = (n - head) >> 2;
+    r.tail = (n - head) & 3;
+    return r;
+}
+
+// Work items of a launch in this order: range 0's groups of four, range 1's, range 0's scalar elements, range 1's.  Grid-stride.
+template <class Step>
+__global__ void __launch_bounds__(256) k_dense_opt(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ st,
+                                                   OptRange r0, OptRange r1, Step step) {
+    const int64_t s0 = r0.head + r0.tail, s1 = r1.head + r1.tail;
+    const int64_t total = r0.vec + r1.vec + s0 + s1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t j = i;
+        if (j < r0.vec + r1.vec) {
+            const int64_t e = j < r0.vec ? r0.lo + r0.head + 4 * j : r1.lo + r1.head + 4 * (j - r0.vec);
+            float4 q = *reinterpret_cast<const float4*>(p + e);
+            const float4 d = *reinterpret_cast<const float4*>(g + e);
+            float4 S = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (Step::STATE) S = *reinterpret_cast<const float4*>(st + e);
+            q.x = step.one(d.x, q.x, S.x); q.y = step.one(d.y, q.y, S.y); q.z = step.one(d.z, q.z, S.z); q.w = step.one(d.w, q.w, S.w);
+            *reinterpret_cast<float4*>(p + e) = q;
+            if constexpr (Step::STATE) *reinterpret_cast<float4*>(st + e) = S;
+            continue;
+        }
+        j -= r0.vec + r1.vec;
+        const OptRange& r = j < s0 ? r0 : r1;
+        if (j >= s0) j -= s0;
+        const int64_t e = j < r.head ? r.lo + j : r.lo + r.head + 4 * r.vec + (j - r.head);
+        float S = 0.f;
+        if constexpr (Step::STATE) S = st[e];
+        p[e] = step.one(g[e], p[e], S);
+        if constexpr (Step::STATE) st[e] = S;
+    }
+}
+
+static void dense_adagrad_launch(float* p, const float* g, float* st, int64_t off0, int64_t n0, int64_t off1, int64_t n1, float lr,
+                                 float eps, hipStream_t s) {
+    if (n0 + n1 == 0) return;
+    const uintptr_t a = (uintptr_t)p & 15;
+    const int k = (((uintptr_t)g & 15) == a && ((uintptr_t)st & 15) == a && (a & 3) == 0) ? (int)(a >> 2) : -1;
+    const OptRange r0 = opt_range(off0, n0, k), r1 = opt_range(off1, n1, k);
+    const int64_t items = r0.vec + r1.vec + r0.head + r0.tail + r1.head + r1.tail;
+    int64_t gx = cdiv(items, 256);
+    if (gx > 1024) gx = 1024;       // (four elements per item: the element count cdlrm_sgd_step caps at 2048)
+    hipLaunchKernelGGL(k_dense_opt<AdagradStep>, dim3((unsigned)gx), dim3(256), 0, s, p, g, st, r0, r1, AdagradStep{lr, eps});
+}
+
+static int dense_opt_check(int32_t opt, float eps, const float* state) {
+    CDLRM_REQUIRE(opt == CDLRM_DENSE_OPT_SGD || opt == CDLRM_DENSE_OPT_ADAGRAD, "opt: CDLRM_DENSE_OPT_*");
+    if (opt == CDLRM_DENSE_OPT_SGD) return 0;
+    CDLRM_REQUIRE(state, "Adagrad: the accumulators are missing");
+    CDLRM_REQUIRE(eps > 0.f, "eps > 0: the step divides by sqrt(S) + eps and S starts at zero");
+    return 0;
+}
+
+extern "C" int cdlrm_dense_opt_step2(float* param, const float* grad, float* state, int64_t off0, int64_t n0, int64_t off1,
+                                     int64_t n1, float lr, int32_t opt, float eps, void* stream) {
+    int rc = dense_opt_check(opt, eps, state);
+    if (rc) return rc;
+    if (opt == CDLRM_DENSE_OPT_SGD) return cdlrm_sgd_step2(param, grad, off0, n0, off1, n1, lr, stream);
+    CDLRM_REQUIRE(param && grad && off0 >= 0 && n0 >= 0 && off1 >= 0 && n1 >= 0, "bad argument");
+    // (an element in both ranges would be stepped twice, by two lanes at once)
+    CDLRM_REQUIRE(n0 == 0 || n1 == 0 || off0 + n0 <= off1 || off1 + n1 <= off0, "the two ranges overlap");
+    dense_adagrad_launch(param, grad, state, off0, n0, off1, n1, lr, eps, (hipStream_t)stream);
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cdlrm_dense_opt_step(float* param, const float* grad, float* state, int64_t n, float lr, int32_t opt, float eps,
+                                    void* stream) {
+    int rc = dense_opt_check(opt, eps, state);
+    if (rc) return rc;
+    if (opt == CDLRM_DENSE_OPT_SGD) return cdlrm_sgd_step(param, grad, n, lr, stream);
+    CDLRM_REQUIRE(param && grad && n >= 0, "bad argument");
+    dense_adagrad_launch(param, grad, state, 0, n, 0, 0, lr, eps, (hipStream_t)stream);
     CDLRM_LAUNCH_CHECK();
     return 0;
 }

@@ -110,6 +110,7 @@ static const std::vector<TapeEntry>& tape_registry() {
         TAPE_FN(cdlrm_mlp_wgrad_sgd_ex), TAPE_FN(cdlrm_bce_fwd_bwd),
         TAPE_FN(cdlrm_loss_fwd_bwd), TAPE_FN(cdlrm_head_fwd_bwd), TAPE_FN(cdlrm_head_finish), TAPE_FN(cdlrm_act_bwd),
         TAPE_FN(cdlrm_sgd_step), TAPE_FN(cdlrm_sgd_step2), TAPE_FN(cdlrm_scale_div),
+        TAPE_FN(cdlrm_mlp_wgrad_opt_ex), TAPE_FN(cdlrm_dense_opt_step), TAPE_FN(cdlrm_dense_opt_step2),
         TAPE_FN_AT(cdlrm_ctx_time_next_gather, -1),      // arms the NEXT gather launch: no stream of its own
         TAPE_FN_AT(cdlrm_event_record, 1), TAPE_FN_AT(cdlrm_stream_wait_event, 0), TAPE_FN_AT(cdlrm_event_attach_next, 1),
         TAPE_FN(cdlrm_agg_compact), TAPE_FN(cdlrm_agg_gather), TAPE_FN(cdlrm_agg_scatter),

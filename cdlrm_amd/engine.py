@@ -696,9 +696,25 @@ class StepPath(NamedTuple):
     lr_embeds: float
     embed_optimizer: str = "sgd"    # the cache rows' update: "sgd" or "rowwise_adagrad" 
     adagrad_eps: float = 0.0
+    dense_optimizer: str = "sgd"    # the MLP parameters' update: "sgd" or "adagrad" 
+    dense_adagrad_eps: float = 0.0
 
 
 EMBED_OPTIMIZERS = ("sgd", "rowwise_adagrad")
+DENSE_OPTIMIZERS = ("sgd", "adagrad")
+
+
+def check_dense_optimizer(dense_optimizer: str, dense_adagrad_eps: float):
+    """What the dense optimizer refuses, as one ValueError -- raised by TrainEngine before it touches the GPU and
+    turned into the one ERROR: line by the command line: an unknown name, and an eps that is not > 0.  Nothing else: the
+    accumulators live beside the parameters, so every world size, either embedding optimizer, quotient-remainder tables and the
+    victim write-back are all served."""
+    if dense_optimizer not in DENSE_OPTIMIZERS:
+        raise ValueError("dense_optimizer=%r: one of %s" % (dense_optimizer, ", ".join(DENSE_OPTIMIZERS)))
+    if dense_optimizer == "sgd":
+        return
+    if not float(dense_adagrad_eps) > 0.0:
+        raise ValueError("dense_adagrad_eps=%r: Adagrad divides by sqrt(S) + eps and S starts at zero: eps > 0" % (dense_adagrad_eps,))
 
 
 def check_embed_optimizer(embed_optimizer: str, adagrad_eps: float, *, world_size: int = 1, qr: bool = False,
@@ -951,7 +967,8 @@ class TrainEngine:
                  *, lr: float, lr_embeds: float, world_size: int = 1, rank: int = 0, table_agg_freq: int = 1,
                  table_agg_op: str = "mean", process_group=None, loss: str = "bce", loss_weights=(1.0, 1.0),
                  defer_top_update: bool = False, force_collectives: bool = False, matmul_precision: str = "fp32",
-                 embed_optimizer: str = "sgd", adagrad_eps: float = 1e-10):
+                 embed_optimizer: str = "sgd", adagrad_eps: float = 1e-10, dense_optimizer: str = "sgd",
+                 dense_adagrad_eps: float = 1e-10):
         """loss / loss_weights: --loss-function / --loss-weights (main_no_ddp.py:364-372); the --loss-threshold clamp
         is read from `dlrm.loss_threshold`.
         defer_top_update: the top MLP's weight gradients, their all-reduce and their SGD update leave the critical
@@ -968,10 +985,15 @@ class TrainEngine:
         section 4.2).  A plain attribute: set it between steps and the next step / evaluate() follows it.
         embed_optimizer: "sgd" (default: the reference's sparse SGD on the cache rows) or "rowwise_adagrad" with adagrad_eps
         (DESIGN.md section 4.5): one fp32 accumulator per table row in `emb_state`, indexed by table index; one rank, plain
-        tables, no --evict-victim-cache."""
+        tables, no --evict-victim-cache.
+        dense_optimizer: "sgd" (default: the reference's optim.SGD on the MLP parameters) or "adagrad" with dense_adagrad_eps
+        (DESIGN.md section 4.6): element-wise Adagrad, one fp32 accumulator per parameter in `dense_state` (param_flat's layout),
+        stepped where the SGD step runs; every world size.  A plain attribute like matmul_precision."""
         check_embed_optimizer(embed_optimizer, adagrad_eps, world_size=world_size,
                               qr=getattr(cache_group, "qr", None) is not None)
+        check_dense_optimizer(dense_optimizer, dense_adagrad_eps)
         self.embed_optimizer, self.adagrad_eps = embed_optimizer, float(adagrad_eps)
+        self.dense_optimizer, self.dense_adagrad_eps = dense_optimizer, float(dense_adagrad_eps)
         self.cg, self.dlrm, self.host = cache_group, dlrm, host_tables
         self.ctx = cache_group.ctx
         self.dev = cache_group.weight.device
@@ -1010,6 +1032,11 @@ class TrainEngine:
         self.emb_state = self.state_base = None
         if self.embed_optimizer != "sgd":
             self._alloc_emb_state()
+        # the dense Adagrad's accumulators: param_flat's layout, zero at the start; allocated in that mode only, here or by the
+        # first step that finds the attribute set (_step_path)
+        self.dense_state = None
+        if self.dense_optimizer != "sgd":
+            self._alloc_dense_state()
         self.iter = 0
         self.comm = S.new_stream(self.dev) if self.multi else None
         self.side = S.new_stream(self.dev)
@@ -1206,6 +1233,59 @@ class TrainEngine:
                 raise ValueError("emb_state[%d]: %d accumulators, the table has %d rows" % (k, h.numel(), v.numel()))
             v.copy_(h)
 
+    # ---- the dense Adagrad's state ----------------------------------------------------------------------------------------
+    def _alloc_dense_state(self):
+        check_dense_optimizer(self.dense_optimizer, self.dense_adagrad_eps)
+        self.dense_state = torch.zeros_like(self.param_flat)
+        base = self.param_flat.data_ptr()
+        es = self.param_flat.element_size()
+
+        def beside(t):          # the accumulators of a parameter view: the same elements of dense_state
+            off = (t.data_ptr() - base) // es
+            return self.dense_state[off:off + t.numel()].view(t.shape)
+
+        # per layer, as self.W / l.bias.data name the parameters (the padded weight storage included)
+        self.SW = {l: beside(W) for l, W in self.W.items()}
+        self.Sb = {l: beside(l.bias.data) for l in self.W}
+
+    def _dense_step(self, path: StepPath):
+        """The dense optimizer's step over the whole flat buffer, on the current stream."""
+        if path.dense_optimizer == "sgd":
+            ops.sgd_step(self.param_flat, self.grad_flat, self.lr)
+        else:
+            ops.dense_opt_step(self.param_flat, self.grad_flat, self.dense_state, self.lr, *self._dense_opt(path))
+
+    def _dense_step2(self, path: StepPath, rng, **kw):
+        """... over one sub-network's weights and biases (rng_bot / rng_top); kw: stream."""
+        if path.dense_optimizer == "sgd":
+            ops.sgd_step2(self.param_flat, self.grad_flat, *rng, self.lr, **kw)
+        else:
+            ops.dense_opt_step2(self.param_flat, self.grad_flat, self.dense_state, *rng, self.lr, *self._dense_opt(path), **kw)
+
+    def _dense_opt(self, path: StepPath):
+        """ops.mlp_wgrad's `opt` for this step."""
+        return (path.dense_optimizer, path.dense_adagrad_eps)
+
+    def dense_state_to_host(self):
+        """One flat CPU tensor, param_flat's layout (--save-model); behind a deferred top-MLP update."""
+        if self.defer_top and self.iter > 0:
+            S.current_stream(self.dev).wait_event(self._events["top_updated"])
+        return self.dense_state.cpu()
+
+    def load_dense_state(self, flat):
+        """dense_state <- a flat tensor of param_flat's layout (--load-model); None: zeros."""
+        if self.defer_top and self.iter > 0:
+            S.current_stream(self.dev).wait_event(self._events["top_updated"])
+        if self.dense_state is None:
+            self._alloc_dense_state()
+        if flat is None:
+            self.dense_state.zero_()
+            return
+        h = torch.as_tensor(flat, dtype=torch.float32).reshape(-1)
+        if h.numel() != self.dense_state.numel():
+            raise ValueError("dense_state: %d accumulators, the MLPs have %d parameters" % (h.numel(), self.dense_state.numel()))
+        self.dense_state.copy_(h)
+
     def qr_split(self, idx, q=None, r=None, stream=None):
         """idx [T, n] -> (q, r) (ops.qr_split; q=idx splits a window rectangle in place): what plan_window / WindowResolver /
         step() / evaluate() take in this mode."""
@@ -1322,6 +1402,8 @@ class TrainEngine:
         B, n = X.shape[0], lS_i.shape[1]
         if self.embed_optimizer != "sgd" and self.emb_state is None:
             self._alloc_emb_state()
+        if self.dense_optimizer != "sgd" and self.dense_state is None:
+            self._alloc_dense_state()
         pf = self._pref
         hit = pf is not None and pf.matches(lS_i)
         phase = pf.phase if hit else self._phase
@@ -1368,7 +1450,9 @@ class TrainEngine:
             fwd_marked=bool(pr is not None and attach and fused), attach=attach, join=join,
             lanes=self.tape_lanes if B < self.tape_lanes_below else 1, wide_gemm=bool(self.wide_gemm),
             matmul_precision=self.matmul_precision, lr=self.lr, lr_embeds=self.lr_embeds,
-            embed_optimizer=self.embed_optimizer, adagrad_eps=self.adagrad_eps if self.embed_optimizer != "sgd" else 0.0)
+            embed_optimizer=self.embed_optimizer, adagrad_eps=self.adagrad_eps if self.embed_optimizer != "sgd" else 0.0,
+            dense_optimizer=self.dense_optimizer,
+            dense_adagrad_eps=self.dense_adagrad_eps if self.dense_optimizer != "sgd" else 0.0)
 
     def _take(self, idx, res, phase: int, which, st):
         """A batch's (slots, miss_pos, miss_count) into the probe buffers `which`, misses into aux region `phase`, on stream st:
@@ -1437,6 +1521,12 @@ class TrainEngine:
         key = "wgrad_" + self.matmul_precision
         if key not in buf:
             buf[key] = self._build_wplans(buf, self.matmul_precision)
+        split = buf[key][1]
+        if self.dense_state is not None and split is not None and not hasattr(split[0], "S_w"):
+            # the accumulators beside the parameters _build_wplans set; once per plan (a tape holds the arrays' addresses)
+            layers, nb = buf["wgrad_args"][2], len(self.bot)
+            split[0].set_state([self.SW[l] for l in layers[:nb]], [self.Sb[l] for l in layers[:nb]])
+            split[1].set_state([self.SW[l] for l in layers[nb:]], [self.Sb[l] for l in layers[nb:]])
         return buf[key]
 
     def _build_wplans(self, buf, precision):
@@ -1701,7 +1791,7 @@ class TrainEngine:
                 else:
                     ops.scale_div(gt, W, stream=wst)             # layer.weight.grad /= world (:239); biases untouched
                     dist.all_reduce(gt, op=dist.ReduceOp.SUM, group=self.pg)
-                ops.sgd_step2(self.param_flat, self.grad_flat, *self.rng_top, self.lr, stream=wst)
+                self._dense_step2(path, self.rng_top, stream=wst)
                 self._events["top_updated"].record(wst)
             if avg:
                 dist.all_reduce(gb, op=dist.ReduceOp.AVG, group=self.pg)
@@ -1710,7 +1800,7 @@ class TrainEngine:
                 dist.all_reduce(gb, op=dist.ReduceOp.SUM, group=self.pg)
             if path.join == "emb_done":
                 S.current_stream(self.dev).wait_event(self._events["emb_done"])
-            ops.sgd_step2(self.param_flat, self.grad_flat, *self.rng_bot, self.lr)
+            self._dense_step2(path, self.rng_bot)
             sgd_done = True
         elif self.multi:
             gw = self.grad_flat[:self.n_weight]
@@ -1723,7 +1813,7 @@ class TrainEngine:
             # all-reduce (the reference overlaps optimizer_embeds.step() with it the same way, :412-414)
             S.current_stream(self.dev).wait_event(self._events["emb_done"])
         if not sgd_done:
-            ops.sgd_step(self.param_flat, self.grad_flat, self.lr)
+            self._dense_step(path)
         # ---- periodic cache-row merge (main_no_ddp.py:417-423) ----
         if j is None:
             j = self.iter
@@ -1872,6 +1962,8 @@ class TrainEngine:
         whole_plan, split = self._wplans(buf)
         wst = self.wst
         sgd_in_wgrad = self.defer_top and not self.multi      # one rank: the dense SGD rides in the weight gradients' reduction pass
+        # ... or the dense Adagrad's step does, at the same places (cdlrm_mlp_wgrad_opt_ex); SGD: the calls stay what they were
+        dopt = {"opt": self._dense_opt(path)} if (sgd_in_wgrad and path.dense_optimizer != "sgd") else {}
 
         n_top = len(self.top)
         if fused_head:
@@ -1918,7 +2010,7 @@ class TrainEngine:
             if not (attach and n_top - (1 if fused_head else 0) > 0):
                 rec(ev["top_dz"].record, main)
             rec(wst.wait_event, ev["top_dz"])
-            ops.mlp_wgrad(split[1], stream=wst, lr=self.lr if sgd_in_wgrad else None)
+            ops.mlp_wgrad(split[1], stream=wst, lr=self.lr if sgd_in_wgrad else None, **dopt)
             if not self.defer_top:
                 rec(ev["wgrad_done"].record, wst)
             elif not self.multi:
@@ -1990,7 +2082,7 @@ class TrainEngine:
             dY = dX
         if split is not None:
             split[0].set_x(0, X)
-            ops.mlp_wgrad(split[0], lr=self.lr if sgd_in_wgrad else None)
+            ops.mlp_wgrad(split[0], lr=self.lr if sgd_in_wgrad else None, **dopt)
             if not self.defer_top:
                 rec(main.wait_event, ev["wgrad_done"])
         else:
@@ -2097,7 +2189,7 @@ class TrainEngine:
             try:
                 included = self._fwd_bwd(path, X, lS_i, T, None, next_idx)
                 if not self.multi and not included:   # no gradient exchange in between: the dense SGD rides on the tape too
-                    ops.sgd_step(self.param_flat, self.grad_flat, self.lr)
+                    self._dense_step(path)
             finally:
                 _lib.stop_recording()
             # pointer arguments equal to one of the per-step tensors become shared cells

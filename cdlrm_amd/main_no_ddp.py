@@ -144,7 +144,16 @@ def ProcessArgs(argv=None):
                         help="the cached embedding rows' update: `sgd` = the reference's sparse SGD; `rowwise-adagrad` = one fp32 "
                              "accumulator per table row, kept in HBM and indexed by table index (DESIGN.md 4.5)")
     parser.add_argument("--adagrad-eps", type=float, default=1e-10, help="--embed-optimizer=rowwise-adagrad: std = sqrt(S) + eps")
+    parser.add_argument("--dense-optimizer", type=str, default="sgd",
+                        help="the MLP parameters' update: `sgd` = the reference's optim.SGD; `adagrad` = element-wise Adagrad, one "
+                             "fp32 accumulator per parameter, stepped where the SGD step runs (DESIGN.md 4.6)")
+    parser.add_argument("--dense-adagrad-eps", type=float, default=1e-10, help="--dense-optimizer=adagrad: std = sqrt(S) + eps")
     args = parser.parse_args(argv)
+    from .engine import check_dense_optimizer
+    try:
+        check_dense_optimizer(args.dense_optimizer, args.dense_adagrad_eps)
+    except ValueError as e:
+        sys.exit("ERROR: --dense-optimizer=%s: %s" % (args.dense_optimizer, e))
     if args.embed_optimizer not in ("sgd", "rowwise-adagrad"):
         sys.exit("ERROR: --embed-optimizer=%s is not supported (sgd | rowwise-adagrad)" % args.embed_optimizer)
     from .engine import check_embed_optimizer
@@ -461,11 +470,18 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         if world > 1:
             dist.barrier()
     embed_opt = getattr(args, "embed_optimizer", "sgd").replace("-", "_")
+    dense_opt = getattr(args, "dense_optimizer", "sgd")
     eng = TrainEngine(cache_group, dlrm, emb_tables, lr=args.learning_rate, lr_embeds=args.lr_embeds, world_size=world,
                       rank=rank, table_agg_freq=args.table_agg_freq, table_agg_op=args.table_agg_op,
                       loss=args.loss_function, loss_weights=loss_ws, defer_top_update=True,
                       **({} if getattr(args, "matmul_precision", "fp32") == "fp32" else {"matmul_precision": args.matmul_precision}),
-                      **({} if embed_opt == "sgd" else {"embed_optimizer": embed_opt, "adagrad_eps": args.adagrad_eps}))
+                      **({} if embed_opt == "sgd" else {"embed_optimizer": embed_opt, "adagrad_eps": args.adagrad_eps}),
+                      **({} if dense_opt == "sgd" else {"dense_optimizer": dense_opt, "dense_adagrad_eps": args.dense_adagrad_eps}))
+    if dense_opt != "sgd" and args.load_model:
+        # the dense Adagrad's accumulators travel with the MLPs; a checkpoint written by an SGD run has none
+        if ld.get("dense_state") is None:
+            print("--load-model: %s holds no dense_state: the dense Adagrad accumulators start at zero" % args.load_model)
+        eng.load_dense_state(ld.get("dense_state"))
     if embed_opt != "sgd" and args.load_model:
         # row-wise Adagrad's accumulators travel with the tables; a checkpoint written by an SGD run has none
         if ld.get("emb_state") is None:
@@ -740,6 +756,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                         **({} if qr_layout is None else
                            {"emb_r": [E.weight_r.data.clone() if hasattr(E, "weight_r") else None for E in emb_tables.emb_l]}),
                         **({} if eng.emb_state is None else {"emb_state": eng.emb_state_to_host()}),
+                        **({} if eng.dense_state is None else {"dense_state": eng.dense_state_to_host()}),
                         "ln_emb": [int(n) for n in ln_emb], "m_spa": int(m_spa)}, args.save_model)
         if world > 1:
             dist.barrier()

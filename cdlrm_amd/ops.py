@@ -854,12 +854,37 @@ class WgradPlan:
         self.P_b = PA(*[ptr(b) for b in bs])
         self._params = (list(Ws), list(bs))
 
+    def set_state(self, SWs, Sbs):
+        """The accumulators of the parameters set_params named (same shapes), for mlp_wgrad(..., lr=, opt=("adagrad", eps))."""
+        import ctypes as C
+        assert len(SWs) == self.n and len(Sbs) == self.n
+        for i, (s, w) in enumerate(zip(SWs, self._params[0])):
+            assert s.is_contiguous() and s.shape == w.shape and s.dtype == torch.float32
+        for s, b in zip(Sbs, self._params[1]):
+            assert (s is None) == (b is None) and (s is None or s.numel() == b.numel())
+        PA = C.c_void_p * self.n
+        self.S_w = PA(*[s.data_ptr() for s in SWs])
+        self.S_b = PA(*[ptr(s) for s in Sbs])
+        self._state = (list(SWs), list(Sbs))
 
-def mlp_wgrad(plan: WgradPlan, stream=None, lr: Optional[float] = None):
+
+DENSE_OPTS = {"sgd": 0, "adagrad": 1}     # CDLRM_DENSE_OPT_*
+
+
+def mlp_wgrad(plan: WgradPlan, stream=None, lr: Optional[float] = None, opt=None):
     """dW[i] = dZ[i]^T X[i], db[i] = column sums of dZ[i] for every layer of the plan (one grouped launch at small M).
-    lr given (and plan.set_params called): W[i] -= lr * dW[i], b[i] -= lr * db[i] in the same launches."""
+    lr given (and plan.set_params called): W[i] -= lr * dW[i], b[i] -= lr * db[i] in the same launches.
+    opt = (name, eps) with lr (and plan.set_state called): the step of that dense optimizer (DENSE_OPTS) in their place."""
     flags = PRECISIONS[plan.precision]          # 0: exactly cdlrm_mlp_wgrad / cdlrm_mlp_wgrad_sgd
-    if lr is None:
+    if opt is not None:
+        assert lr is not None, "the optimizer's step rides with lr"
+        name, eps = opt
+        adagrad = DENSE_OPTS[name] != 0
+        check(_lib.lib().cdlrm_mlp_wgrad_opt_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
+                                                plan.P_b, float(lr), plan.M, plan.N, plan.K, flags, DENSE_OPTS[name], float(eps),
+                                                plan.S_w if adagrad else None, plan.S_b if adagrad else None,
+                                                plan.work.data_ptr(), stream_ptr(stream)))
+    elif lr is None:
         check(_lib.lib().cdlrm_mlp_wgrad_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.M, plan.N,
                                             plan.K, flags, plan.work.data_ptr(), stream_ptr(stream)))
     else:
@@ -934,6 +959,29 @@ def sgd_step2(param: torch.Tensor, grad: torch.Tensor, off0: int, n0: int, off1:
     assert 0 <= off0 and off0 + n0 <= param.numel() and 0 <= off1 and off1 + n1 <= param.numel()
     check(_lib.lib().cdlrm_sgd_step2(param.data_ptr(), grad.data_ptr(), int(off0), int(n0), int(off1), int(n1), float(lr),
                                      stream_ptr(stream)))
+
+
+def _check_dense_state(param, grad, state, opt):
+    assert param.is_contiguous() and grad.is_contiguous() and param.numel() == grad.numel()
+    if DENSE_OPTS[opt] != 0:
+        assert state is not None and state.is_contiguous() and state.dtype == torch.float32 and state.numel() == param.numel()
+
+
+def dense_opt_step(param: torch.Tensor, grad: torch.Tensor, state: Optional[torch.Tensor], lr: float, opt: str, eps: float,
+                   stream=None):
+    """sgd_step with the dense optimizer named (DENSE_OPTS): "adagrad" steps `state` (param's layout) and param."""
+    _check_dense_state(param, grad, state, opt)
+    check(_lib.lib().cdlrm_dense_opt_step(param.data_ptr(), grad.data_ptr(), ptr(state), param.numel(), float(lr),
+                                          DENSE_OPTS[opt], float(eps), stream_ptr(stream)))
+
+
+def dense_opt_step2(param: torch.Tensor, grad: torch.Tensor, state: Optional[torch.Tensor], off0: int, n0: int, off1: int,
+                    n1: int, lr: float, opt: str, eps: float, stream=None):
+    """sgd_step2 with the dense optimizer named: two disjoint ranges of the flat buffers in one launch."""
+    _check_dense_state(param, grad, state, opt)
+    assert 0 <= off0 and off0 + n0 <= param.numel() and 0 <= off1 and off1 + n1 <= param.numel()
+    check(_lib.lib().cdlrm_dense_opt_step2(param.data_ptr(), grad.data_ptr(), ptr(state), int(off0), int(n0), int(off1),
+                                           int(n1), float(lr), DENSE_OPTS[opt], float(eps), stream_ptr(stream)))
 
 
 def scale_div(x: torch.Tensor, divisor: float, stream=None):

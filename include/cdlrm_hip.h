@@ -652,6 +652,22 @@ int cdlrm_mlp_wgrad_ex(int32_t n_layers, const float* const* X, const int64_t* l
 int cdlrm_mlp_wgrad_sgd_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
                            const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W, float* const* b,
                            float lr, int64_t M, const int32_t* N, const int32_t* K, int32_t flags, void* work, void* stream);
+/* The dense optimizer (opt-in; a departure: the reference builds optimizer_mlps as optim.SGD, main_no_ddp.py:375,
+ * and steps it at main_no_ddp.py:415).  CDLRM_DENSE_OPT_ADAGRAD is element-wise Adagrad -- optim.Adagrad with lr_decay = 0,
+ * weight_decay = 0, initial_accumulator_value = 0 -- with one fp32 accumulator S per parameter, kept by the caller beside the
+ * parameter, zero at the start:   S += g * g;   p -= lr * g / (sqrt(S) + eps)   (eps > 0; g = 0 on S = 0 leaves p unchanged). */
+#define CDLRM_DENSE_OPT_SGD 0
+#define CDLRM_DENSE_OPT_ADAGRAD 1
+/* cdlrm_mlp_wgrad_sgd_ex with the optimizer named: its arguments, then opt, eps and the layers' accumulators SW[i] [N[i], K[i]],
+ * Sb[i] [N[i]] (host arrays like W / b; Sb[i] may be NULL where the bias is not stepped) in front of work and stream.
+ *   opt = CDLRM_DENSE_OPT_SGD: exactly cdlrm_mlp_wgrad_sgd_ex's plan and launches; eps, SW and Sb are not read.
+ *   opt = CDLRM_DENSE_OPT_ADAGRAD: the same plan, the Adagrad step wherever the SGD step rides -- inside the slab reduction, or
+ *   as an element-wise launch behind a layer whose gradient needs no reduction.  dW / db are left bit for bit as by
+ *   cdlrm_mlp_wgrad_ex: the optimizer does not change the gradient. */
+int cdlrm_mlp_wgrad_opt_ex(int32_t n_layers, const float* const* X, const int64_t* ld_x, const float* const* dZ,
+                           const int64_t* ld_dz, float* const* dW, float* const* db, float* const* W, float* const* b,
+                           float lr, int64_t M, const int32_t* N, const int32_t* K, int32_t flags, int32_t opt, float eps,
+                           float* const* SW, float* const* Sb, void* work, void* stream);
 /* The plan of cdlrm_mlp_wgrad_ex with the same arguments, without the launches (no pointer is read, no device touched): out[i] is
  * layer i's weight-gradient GEMM -- family, tile where the family has one, splits (slab count), vec_a / vec_b -- from the same
  * decision code.  n_cu as for cdlrm_linear_fwd_route. */
@@ -707,6 +723,15 @@ int cdlrm_act_bwd(float* dX, int64_t lddx, const float* X, int64_t ldx, int64_t 
  * sub-network's weights and its biases: the bottom and the top MLP are updated at different points of the step). */
 int cdlrm_sgd_step2(float* param, const float* grad, int64_t off0, int64_t n0, int64_t off1, int64_t n1, float lr,
                     void* stream);
+
+/* cdlrm_sgd_step / cdlrm_sgd_step2 with the optimizer named (CDLRM_DENSE_OPT_*, above; departs from main_no_ddp.py:375, 415 in
+ * the Adagrad mode only): `state` has param's layout.  opt = CDLRM_DENSE_OPT_SGD is exactly the sibling (state and eps not read,
+ * state may be NULL); CDLRM_DENSE_OPT_ADAGRAD steps state and param over the range(s) and touches nothing outside them -- 16-byte
+ * accesses where a range's start and length allow, scalar heads and tails elsewhere.  The two ranges of _step2 must not overlap. */
+int cdlrm_dense_opt_step(float* param, const float* grad, float* state, int64_t n, float lr, int32_t opt, float eps,
+                         void* stream);
+int cdlrm_dense_opt_step2(float* param, const float* grad, float* state, int64_t off0, int64_t n0, int64_t off1, int64_t n1,
+                          float lr, int32_t opt, float eps, void* stream);
 
 /* x /= divisor (aggregate_gradients: layer.weight.grad /= world_size, main_no_ddp.py:239, 244). */
 int cdlrm_scale_div(float* x, int64_t n, float divisor, void* stream);
