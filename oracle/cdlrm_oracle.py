@@ -506,8 +506,9 @@ class OracleTrainer:
                  world_size=1, lr=0.1, lr_embeds=0.3, lookahead=2, table_agg_freq=1,
                  table_agg_op="mean", loss="bce", itself=False, op="dot", seed=123,
                  average_on_writeback=False, host_tables=None, cache_init="normal", loss_weights=None,
-                 loss_threshold=0.0, evict_victim_cache=False):
+                 loss_threshold=0.0, evict_victim_cache=False, dtype=torch.float32):
         self.ln_emb = [int(n) for n in ln_emb]
+        self.dtype = dtype      # of host tables, cache rows, MLPs, X and T; float64 runs the same sequence in double precision
         self.W = world_size
         self.lr, self.lr_embeds = lr, lr_embeds
         self.L, self.agg_freq, self.agg_op = lookahead, table_agg_freq, table_agg_op
@@ -528,7 +529,8 @@ class OracleTrainer:
         # main process (main_no_ddp.py:509-512, 621)
         np.random.seed(seed)
         torch.manual_seed(seed)
-        self.host = host_tables if host_tables is not None else init_host_tables(self.ln_emb, m_spa)
+        cast = lambda ts: [t.to(dtype) for t in ts]
+        self.host = cast(host_tables if host_tables is not None else init_host_tables(self.ln_emb, m_spa))
         self.P, self.cache_sizes, rows = cache_geometry(self.ln_emb, cache_size, num_ways, mini_batch_size)
         self.occ = new_occupancy_tables(self.cache_sizes, num_ways)
         self.weights, self.bot, self.top = [], [], []
@@ -538,11 +540,11 @@ class OracleTrainer:
             np.random.seed(seed)
             torch.manual_seed(seed)
             if cache_init == "normal":
-                self.weights.append([torch.randn(n_rows, m_spa) for n_rows in rows])
+                self.weights.append(cast([torch.randn(n_rows, m_spa) for n_rows in rows]))
             else:
-                self.weights.append([torch.zeros(n_rows, m_spa) for n_rows in rows])
-            self.bot.append(init_mlp(ln_bot))
-            self.top.append(init_mlp(ln_top))
+                self.weights.append(cast([torch.zeros(n_rows, m_spa) for n_rows in rows]))
+            self.bot.append(tuple(cast(ts) for ts in init_mlp(ln_bot)))
+            self.top.append(tuple(cast(ts) for ts in init_mlp(ln_top)))
         self.touched = [[] for _ in range(self.W)]
         self.losses: List[float] = []
 
@@ -565,66 +567,91 @@ class OracleTrainer:
             return dlrm_forward(X, ly, self.bot[0], self.top[0], self.op, self.itself, self.loss_threshold)
 
     def step(self, j, X, lS_o, lS_i, T):
-        """One iteration of main_no_ddp.py:387-423 for all emulated ranks.  Returns per-rank losses."""
-        Wn, lbs = self.W, self.lbs
-        rank_loss, grads_w = [], []
-        params = []
+        """One iteration of main_no_ddp.py:387-423 for all emulated ranks.  Returns per-rank losses.
+
+        The sequence is fixed here; a trainer that restates another mode replaces the phases it changes (the methods
+        below, in call order) and nothing else."""
+        Wn = self.W
+        X, T = X.to(self.dtype), T.to(self.dtype)
+        leaf = lambda ts: [t.detach().requires_grad_(True) for t in ts]
+        rank_loss, params = [], []
         for r in range(Wn):
-            Xr = X[r * lbs:(r + 1) * lbs]
-            if Wn == 1:         # whole batch: multi-hot / ragged bags pass through as they are
-                Ir = [lS_i[k] for k in range(len(self.ln_emb))]
-                Or = [lS_o[k] for k in range(len(self.ln_emb))]
-            else:               # the rank slice of the Criteo layout (one lookup per sample)
-                Ir = [lS_i[k][r * lbs:(r + 1) * lbs] for k in range(len(self.ln_emb))]
-                # lS_o[:, :local_batch_size] (:390).  When world does not divide the batch the reference's last rank gets
-                # lbs offsets for fewer lookups -- an empty trailing bag, [lbs, D] pooled rows beside a shorter X -- and
-                # raises in interact_features' cat (model_no_ddp.py:276).  Defined here (and in the engine) as the natural
-                # extension: the last rank trains on its short slice, one bag per lookup it has.
-                Or = [lS_o[k][:Ir[k].numel()] for k in range(len(self.ln_emb))]
-            Tr = T[r * lbs:(r + 1) * lbs]
+            Xr, Or, Ir, Tr, carry = self.rank_slice(r, X, lS_o, lS_i, T)
             ly, cg = cache_forward(self.occ, self.weights[r], self.cache_sizes, Or, Ir, self.host)
-            ly = [v.detach().requires_grad_(True) for v in ly]
-            bw = [w.detach().requires_grad_(True) for w in self.bot[r][0]]
-            bb = [b.detach().requires_grad_(True) for b in self.bot[r][1]]
-            tw = [w.detach().requires_grad_(True) for w in self.top[r][0]]
-            tb = [b.detach().requires_grad_(True) for b in self.top[r][1]]
-            Z = dlrm_forward(Xr, ly, (bw, bb), (tw, tb), self.op, self.itself, self.loss_threshold)
+            rows = leaf(ly)
+            feats, extra = self.features(r, rows, carry)
+            p = tuple(leaf(ts) for ts in self.bot[r] + self.top[r])         # (bot W, bot b, top W, top b)
+            Z = dlrm_forward(Xr, feats, p[:2], p[2:], self.op, self.itself, self.loss_threshold)
             E = loss_fn(Z, Tr, self.loss_kind, self.loss_ws)
             E.backward()
             rank_loss.append(float(E.detach()))
-            params.append((bw, bb, tw, tb))
-            # embedding SGD (optimizer_embeds.step, :413)
-            for k in range(len(self.ln_emb)):
-                embbag_bwd_sgd(self.weights[r][k], cg[k].long(), Or[k], ly[k].grad, self.lr_embeds)
+            params.append(p)
+            self.update_embeddings(r, cg, Or, rows, extra)      # optimizer_embeds.step, :413
             self.touched[r].append(list(cg))      # per-table lists (ragged for multi-hot bags)
             if self.evict_victim:
-                for k in range(len(self.ln_emb)):
-                    first_aux = int(self.cache_sizes[k]) * self.ways
-                    sl = cg[k].long()
-                    pos = torch.nonzero(sl >= first_aux).flatten()
-                    for p in pos.tolist():          # position order: the last occurrence of an index wins
-                        self.host[k][int(Ir[k][p])] = self.weights[r][k][int(sl[p])]
-        # aggregate_gradients (:234-247): weight grads averaged, bias grads NOT reduced
-        for li in range(len(params[0][0])):
-            g = sum(params[r][0][li].grad / Wn for r in range(Wn))
-            for r in range(Wn):
-                params[r][0][li].grad = g.clone()
-        for li in range(len(params[0][2])):
-            g = sum(params[r][2][li].grad / Wn for r in range(Wn))
-            for r in range(Wn):
-                params[r][2][li].grad = g.clone()
+                self.victim_writeback(r, cg, Ir)
+        self.average_weight_grads(params)
         for r in range(Wn):
-            bw, bb, tw, tb = params[r]
-            self.bot[r] = ([(w - self.lr * w.grad).detach() for w in bw],
-                           [(b - self.lr * b.grad).detach() for b in bb])
-            self.top[r] = ([(w - self.lr * w.grad).detach() for w in tw],
-                           [(b - self.lr * b.grad).detach() for b in tb])
+            new = [[self.dense_step(r, part, li, t) for li, t in enumerate(ts)] for part, ts in enumerate(params[r])]
+            self.bot[r], self.top[r] = (new[0], new[1]), (new[2], new[3])
         # table aggregation (:417-423)
         if j > 0 and j % self.agg_freq == 0:
-            if Wn > 1 or True:
-                for k in range(len(self.ln_emb)):
-                    touched = [torch.cat([t[k] for t in self.touched[r]]) for r in range(Wn)]
-                    table_aggregate([self.weights[r][k] for r in range(Wn)], touched, self.agg_op)
+            self.merge_rows()
             self.touched = [[] for _ in range(Wn)]
         self.losses.append(rank_loss)
         return rank_loss
+
+    def rank_slice(self, r, X, lS_o, lS_i, T):
+        """-> (Xr, Or, Ir, Tr, carry): rank r's dense rows, per-table offsets and indices (what cache_forward looks up),
+        targets, and whatever `features` needs beside the pooled rows (nothing here)."""
+        lbs, nt = self.lbs, len(self.ln_emb)
+        if self.W == 1:         # whole batch: multi-hot / ragged bags pass through as they are
+            Ir = [lS_i[k] for k in range(nt)]
+            Or = [lS_o[k] for k in range(nt)]
+        else:                   # the rank slice of the Criteo layout (one lookup per sample)
+            Ir = [lS_i[k][r * lbs:(r + 1) * lbs] for k in range(nt)]
+            # lS_o[:, :local_batch_size] (:390).  When world does not divide the batch the reference's last rank gets
+            # lbs offsets for fewer lookups -- an empty trailing bag, [lbs, D] pooled rows beside a shorter X -- and
+            # raises in interact_features' cat (model_no_ddp.py:276).  Defined here (and in the engine) as the natural
+            # extension: the last rank trains on its short slice, one bag per lookup it has.
+            Or = [lS_o[k][:Ir[k].numel()] for k in range(nt)]
+        return X[r * lbs:(r + 1) * lbs], Or, Ir, T[r * lbs:(r + 1) * lbs], None
+
+    def features(self, r, rows, carry):
+        """-> (what dlrm_forward takes as the embedding features, further leaf tensors of the graph for update_embeddings).
+        `rows`: the pooled cache rows as leaves, per table."""
+        return rows, None
+
+    def update_embeddings(self, r, cg, Or, rows, extra):
+        """Rank r's embedding parameters take their step, table by table; rows[k].grad is dL/d(pooled rows)."""
+        for k in range(len(self.ln_emb)):
+            self.update_table(r, k, cg[k].long(), Or[k], rows[k].grad)
+
+    def update_table(self, r, k, slots, offsets, grad_out):
+        embbag_bwd_sgd(self.weights[r][k], slots, offsets, grad_out, self.lr_embeds)
+
+    def victim_writeback(self, r, cg, Ir):
+        for k in range(len(self.ln_emb)):
+            first_aux = int(self.cache_sizes[k]) * self.ways
+            sl = cg[k].long()
+            pos = torch.nonzero(sl >= first_aux).flatten()
+            for p in pos.tolist():          # position order: the last occurrence of an index wins
+                self.host[k][int(Ir[k][p])] = self.weights[r][k][int(sl[p])]
+
+    def average_weight_grads(self, params):
+        """aggregate_gradients (:234-247): weight grads averaged, bias grads NOT reduced."""
+        Wn = self.W
+        for part in (0, 2):
+            for li in range(len(params[0][part])):
+                g = sum(params[r][part][li].grad / Wn for r in range(Wn))
+                for r in range(Wn):
+                    params[r][part][li].grad = g.clone()
+
+    def dense_step(self, r, part, li, p):
+        """-> the new value of rank r's dense parameter p (leaf with .grad): entry li of part 0..3 = bot W, bot b, top W, top b."""
+        return (p - self.lr * p.grad).detach()
+
+    def merge_rows(self):
+        for k in range(len(self.ln_emb)):
+            touched = [torch.cat([t[k] for t in self.touched[r]]) for r in range(self.W)]
+            table_aggregate([self.weights[r][k] for r in range(self.W)], touched, self.agg_op)

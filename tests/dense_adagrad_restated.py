@@ -9,10 +9,11 @@ the ranks; biases: the rank's own, un-reduced):
 torch.optim.Adagrad with lr_decay = 0, weight_decay = 0, initial_accumulator_value = 0.  S is one fp32 per parameter, per rank,
 zero at the start.  g = 0 on S = 0 leaves p unchanged (0 / eps).
 
-`DenseAdagradTrainer` is `OracleTrainer` whose `step` is the oracle's own sequence -- cache_forward, dlrm_forward, loss_fn,
-embbag_bwd_sgd, the weight-only gradient average, table_aggregate -- with the dense update replaced; nothing here imports the
-package under test.  `kernel_reference` / `kernel_bounds` are the float64 reference and the bounds the kernel tests hold the HIP
-kernels to (and the host tests hold the wrong variants to: they must fail them).
+`DenseAdagradTrainer` is `OracleTrainer` with one phase of its step replaced: `dense_step`, the update of one dense parameter
+behind the weight-only gradient average.  `BothAdagradTrainer` composes it with the row-wise Adagrad of the cached embedding
+rows (tests/rowwise_adagrad_restated.py), the engine's dense_optimizer="adagrad" with embed_optimizer="rowwise_adagrad".
+Nothing here imports the package under test.  `kernel_reference` / `kernel_bounds` are the float64 reference and the bounds
+the kernel tests hold the HIP kernels to (and the host tests hold the wrong variants to: they must fail them).
 """
 import os
 import sys
@@ -24,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 from oracle import cdlrm_oracle as O  # noqa: E402
+from rowwise_adagrad_restated import RowwiseAdagradTrainer, criteo_batches  # noqa: E402
 
 U = 2.0 ** -24
 VARIANTS = ("contract", "no_accumulate", "eps_inside", "rowwise_mean")
@@ -42,87 +44,32 @@ def adagrad_update(p, S, g, lr, eps, variant="contract"):
 
 
 class DenseAdagradTrainer(O.OracleTrainer):
-    """OracleTrainer whose MLP parameters take Adagrad steps; `state[r]`: rank r's accumulators, (bot W, bot b, top W, top b)
-    lists shaped like the parameters.  dtype=torch.float64 runs the same sequence in double precision."""
+    """OracleTrainer whose MLP parameters take Adagrad steps: the dense_step phase replaced, with rank r's accumulators beside
+    the parameters (dense_state).  dtype=torch.float64 runs the same sequence in double precision."""
 
-    def __init__(self, *a, dense_adagrad_eps=1e-10, variant="contract", dtype=torch.float32, **kw):
+    def __init__(self, *a, dense_adagrad_eps=1e-10, dense_variant="contract", **kw):
         super().__init__(*a, **kw)
-        assert variant in VARIANTS
-        self.eps, self.variant, self.dtype = float(dense_adagrad_eps), variant, dtype
-        cast = lambda ts: [t.to(dtype) for t in ts]
-        self.host = cast(self.host)
-        self.weights = [cast(w) for w in self.weights]
-        self.bot = [(cast(w), cast(b)) for w, b in self.bot]
-        self.top = [(cast(w), cast(b)) for w, b in self.top]
-        zeros = lambda ts: [torch.zeros_like(t) for t in ts]
-        self.state = [(zeros(self.bot[r][0]), zeros(self.bot[r][1]), zeros(self.top[r][0]), zeros(self.top[r][1]))
-                      for r in range(self.W)]
+        assert dense_variant in VARIANTS
+        self._dense_eps, self._dense_variant = float(dense_adagrad_eps), dense_variant
+        # [r][part][li] like the parameters: part 0..3 = bot W, bot b, top W, top b
+        self._dense_S = [[[torch.zeros_like(t) for t in ts] for ts in self.bot[r] + self.top[r]] for r in range(self.W)]
 
-    def step(self, j, X, lS_o, lS_i, T):
-        Wn, lbs, nt = self.W, self.lbs, len(self.ln_emb)
-        X, T = X.to(self.dtype), T.to(self.dtype)
-        rank_loss, params = [], []
-        for r in range(Wn):
-            Xr = X[r * lbs:(r + 1) * lbs]
-            if Wn == 1:
-                Ir = [lS_i[k] for k in range(nt)]
-                Or = [lS_o[k] for k in range(nt)]
-            else:
-                Ir = [lS_i[k][r * lbs:(r + 1) * lbs] for k in range(nt)]
-                Or = [lS_o[k][:Ir[k].numel()] for k in range(nt)]
-            Tr = T[r * lbs:(r + 1) * lbs]
-            ly, cg = O.cache_forward(self.occ, self.weights[r], self.cache_sizes, Or, Ir, self.host)
-            ly = [v.detach().requires_grad_(True) for v in ly]
-            leaf = lambda ts: [t.detach().requires_grad_(True) for t in ts]
-            bw, bb, tw, tb = leaf(self.bot[r][0]), leaf(self.bot[r][1]), leaf(self.top[r][0]), leaf(self.top[r][1])
-            Z = O.dlrm_forward(Xr, ly, (bw, bb), (tw, tb), self.op, self.itself, self.loss_threshold)
-            E = O.loss_fn(Z, Tr, self.loss_kind, self.loss_ws)
-            E.backward()
-            rank_loss.append(float(E.detach()))
-            params.append((bw, bb, tw, tb))
-            for k in range(nt):
-                O.embbag_bwd_sgd(self.weights[r][k], cg[k].long(), Or[k], ly[k].grad, self.lr_embeds)
-            self.touched[r].append(list(cg))
-            if self.evict_victim:
-                for k in range(nt):
-                    first_aux = int(self.cache_sizes[k]) * self.ways
-                    sl = cg[k].long()
-                    for p in torch.nonzero(sl >= first_aux).flatten().tolist():
-                        self.host[k][int(Ir[k][p])] = self.weights[r][k][int(sl[p])]
-        # weight gradients averaged over the ranks, bias gradients not reduced
-        for part in (0, 2):
-            for li in range(len(params[0][part])):
-                g = sum(params[r][part][li].grad / Wn for r in range(Wn))
-                for r in range(Wn):
-                    params[r][part][li].grad = g.clone()
-        # the dense update: Adagrad, per rank, on that rank's accumulators
-        for r in range(Wn):
-            new = []
-            for part in range(4):
-                ps, Ss = [], []
-                for p, S in zip(params[r][part], self.state[r][part]):
-                    p2, S2 = adagrad_update(p.detach(), S, p.grad, self.lr, self.eps, self.variant)
-                    ps.append(p2.detach())
-                    Ss.append(S2.detach())
-                new.append((ps, Ss))
-            self.bot[r] = (new[0][0], new[1][0])
-            self.top[r] = (new[2][0], new[3][0])
-            self.state[r] = tuple(n[1] for n in new)
-        if j > 0 and j % self.agg_freq == 0:
-            for k in range(nt):
-                touched = [torch.cat([t[k] for t in self.touched[r]]) for r in range(Wn)]
-                O.table_aggregate([self.weights[r][k] for r in range(Wn)], touched, self.agg_op)
-            self.touched = [[] for _ in range(Wn)]
-        self.losses.append(rank_loss)
-        return rank_loss
+    def dense_step(self, r, part, li, p):
+        p2, S2 = adagrad_update(p.detach(), self._dense_S[r][part][li], p.grad, self.lr, self._dense_eps, self._dense_variant)
+        self._dense_S[r][part][li] = S2.detach()
+        return p2.detach()
 
     def dense_params(self, r=0):
         """Rank r's dense parameters as one flat vector: all weights (bottom, then top), then all biases."""
         return torch.cat([t.reshape(-1) for t in self.bot[r][0] + self.top[r][0] + self.bot[r][1] + self.top[r][1]])
 
     def dense_state(self, r=0):
-        s = self.state[r]
+        s = self._dense_S[r]
         return torch.cat([t.reshape(-1) for t in s[0] + s[2] + s[1] + s[3]])
+
+
+class BothAdagradTrainer(RowwiseAdagradTrainer, DenseAdagradTrainer):
+    """Row-wise Adagrad on the cached rows (update_table) and element-wise Adagrad on the MLPs (dense_step) in one step; one rank."""
 
 
 # ---- what the kernel tests compare with -------------------------------------------------------------------------------------
@@ -174,21 +121,23 @@ def engine_shapes(ln_emb=LN_EMB, m_spa=ENGINE_CASE["m_spa"]):
 
 def engine_batches(ln_emb=LN_EMB, B=ENGINE_CASE["B"], nbatch=ENGINE_CASE["steps"], seed=ENGINE_CASE["batch_seed"]):
     """[(X [B, 13], idx int64 [T, B], T [B, 1])]: Zipf indices scattered over each table, table 2 drawing from five indices."""
-    from rowwise_adagrad_restated import criteo_batches
     return criteo_batches(ln_emb, 13, B, nbatch, seed, heavy=(2,) if len(ln_emb) > 2 else ())
 
 
 def run_restated(batches, *, dtype=torch.float32, world_size=1, variant="contract", eps=1e-10, ln_emb=LN_EMB, refill_seed=900,
-                 **over):
+                 embed="sgd", **over):
     """The restated trainer over `batches` as the engine tests drive the engine: a refill every L batches (torch seed
-    refill_seed + j in front of each), one step per batch.  Returns the trainer."""
+    refill_seed + j in front of each), one step per batch.  embed="rowwise_adagrad": the composed trainer, the rows' eps
+    1e-10.  Returns the trainer."""
     c = dict(ENGINE_CASE)
     c.update(over)
     ln_bot, ln_top = engine_shapes(ln_emb, c["m_spa"])
-    tr = DenseAdagradTrainer(ln_emb, c["m_spa"], ln_bot, ln_top, cache_size=c["cache_size"], num_ways=c["ways"],
-                             mini_batch_size=c["B"], world_size=world_size, lr=c["lr"], lr_embeds=c["lr_embeds"],
-                             lookahead=c["L"], table_agg_freq=c.get("table_agg_freq", 10 ** 9), seed=c["seed"],
-                             dense_adagrad_eps=eps, variant=variant, dtype=dtype)
+    assert embed in ("sgd", "rowwise_adagrad")
+    cls, kw = (DenseAdagradTrainer, {}) if embed == "sgd" else (BothAdagradTrainer, dict(adagrad_eps=1e-10))
+    tr = cls(ln_emb, c["m_spa"], ln_bot, ln_top, cache_size=c["cache_size"], num_ways=c["ways"],
+             mini_batch_size=c["B"], world_size=world_size, lr=c["lr"], lr_embeds=c["lr_embeds"],
+             lookahead=c["L"], table_agg_freq=c.get("table_agg_freq", 10 ** 9), seed=c["seed"],
+             dense_adagrad_eps=eps, dense_variant=variant, dtype=dtype, **kw)
     B = c["B"]
     lS_o = torch.arange(B).repeat(len(ln_emb), 1)
     torch.set_num_threads(1)

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from oracle import cdlrm_oracle as O
+from rowwise_adagrad_restated import criteo_batches  # noqa: F401  (the batch stream the host and the GPU tests share)
 
 
 def collisions_of(ln_emb, c, threshold):
@@ -100,73 +101,33 @@ class QRCachedTrainer(O.OracleTrainer):
             E = [compose(ly[k], self.Wr[0][k], rem[k], self.qr_op) for k in range(T)]
             return O.dlrm_forward(X, E, self.bot[0], self.top[0], self.op, self.itself, self.loss_threshold)
 
-    def step(self, j, X, lS_o, lS_i, T):
-        Wn, lbs, nt = self.W, self.lbs, len(self.ln_full)
-        q_all, r_all = self.split(lS_i)
-        rank_loss, params = [], []
-        for r in range(Wn):
-            sl = slice(r * lbs, (r + 1) * lbs)
-            Xr, Tr = X[sl], T[sl]
-            Ir = [q_all[k][sl] for k in range(nt)]
-            Rr = [r_all[k][sl] for k in range(nt)]
-            Or = [lS_o[k][:Ir[k].numel()] for k in range(nt)]
-            for k in range(nt):     # one lookup per bag
-                assert torch.equal(Or[k].long(), torch.arange(Ir[k].numel()))
-            ly, cg = O.cache_forward(self.occ, self.weights[r], self.cache_sizes, Or, Ir, self.host)
-            rows = [v.detach().requires_grad_(True) for v in ly]
-            wr = [None if w is None else w.detach().requires_grad_(True) for w in self.Wr[r]]
-            E = [compose(rows[k], wr[k], Rr[k], self.qr_op) for k in range(nt)]
-            bw = [w.detach().requires_grad_(True) for w in self.bot[r][0]]
-            bb = [b.detach().requires_grad_(True) for b in self.bot[r][1]]
-            tw = [w.detach().requires_grad_(True) for w in self.top[r][0]]
-            tb = [b.detach().requires_grad_(True) for b in self.top[r][1]]
-            Z = O.dlrm_forward(Xr, E, (bw, bb), (tw, tb), self.op, self.itself, self.loss_threshold)
-            L = O.loss_fn(Z, Tr, self.loss_kind, self.loss_ws)
-            L.backward()
-            rank_loss.append(float(L.detach()))
-            params.append((bw, bb, tw, tb))
-            # both factors were read above; now the two embedding parameters take their local SGD step
-            for k in range(nt):
-                O.embbag_bwd_sgd(self.weights[r][k], cg[k].long(), Or[k], rows[k].grad, self.lr_embeds)
-                if wr[k] is not None:
-                    self.Wr[r][k] = (wr[k] - self.lr_embeds * wr[k].grad).detach()
-            self.touched[r].append(list(cg))
-            if self.evict_victim:
-                for k in range(nt):
-                    first_aux = int(self.cache_sizes[k]) * self.ways
-                    s = cg[k].long()
-                    for p in torch.nonzero(s >= first_aux).flatten().tolist():
-                        self.host[k][int(Ir[k][p])] = self.weights[r][k][int(s[p])]
-        # dense parameters: weight gradients averaged over the ranks, bias gradients not (as OracleTrainer.step)
-        for grp in (0, 2):
-            for li in range(len(params[0][grp])):
-                g = sum(params[r][grp][li].grad / Wn for r in range(Wn))
-                for r in range(Wn):
-                    params[r][grp][li].grad = g.clone()
-        for r in range(Wn):
-            bw, bb, tw, tb = params[r]
-            self.bot[r] = ([(w - self.lr * w.grad).detach() for w in bw], [(b - self.lr * b.grad).detach() for b in bb])
-            self.top[r] = ([(w - self.lr * w.grad).detach() for w in tw], [(b - self.lr * b.grad).detach() for b in tb])
-        if j > 0 and j % self.agg_freq == 0:
-            for k in range(nt):
-                touched = [torch.cat([t[k] for t in self.touched[r]]) for r in range(Wn)]
-                O.table_aggregate([self.weights[r][k] for r in range(Wn)], touched, self.agg_op)
-                if self.coll[k]:    # Wr: a table all of whose rows every rank touched
-                    every = [torch.arange(self.coll[k], dtype=torch.int32) for _ in range(Wn)]
-                    O.table_aggregate([self.Wr[r][k] for r in range(Wn)], every, self.agg_op)
-            self.touched = [[] for _ in range(Wn)]
-        self.losses.append(rank_loss)
-        return rank_loss
 
+    # the phases of OracleTrainer.step that differ: the slice carries the remainders, the pooled quotient rows are composed
+    # with Wr, Wr takes its local SGD step beside the cache rows and is merged with them
 
-def criteo_batches(ln_emb, m_den, B, nbatch, seed, alpha=1.2):
-    """The batch stream the host and the GPU tests share: (X, lS_i [T, B] unsplit, T)."""
-    rng = np.random.RandomState(seed)
-    out = []
-    for _ in range(nbatch):
-        X = torch.from_numpy(rng.rand(B, m_den).astype(np.float32))
-        idx = torch.stack([torch.from_numpy((rng.zipf(alpha, size=B).astype(np.int64) * 2654435761 % int(n)).astype(np.int64))
-                           for n in ln_emb])
-        T = torch.from_numpy(np.round(rng.rand(B, 1)).astype(np.float32))
-        out.append((X, idx, T))
-    return out
+    def rank_slice(self, r, X, lS_o, lS_i, T):
+        nt = len(self.ln_full)
+        sl = slice(r * self.lbs, (r + 1) * self.lbs)
+        q, rem = self.split(lS_i)
+        Ir = [q[k][sl] for k in range(nt)]
+        Or = [lS_o[k][:Ir[k].numel()] for k in range(nt)]
+        for k in range(nt):     # one lookup per bag
+            assert torch.equal(Or[k].long(), torch.arange(Ir[k].numel()))
+        return X[sl], Or, Ir, T[sl], [rem[k][sl] for k in range(nt)]
+
+    def features(self, r, rows, Rr):
+        wr = [None if w is None else w.detach().requires_grad_(True) for w in self.Wr[r]]
+        return [compose(rows[k], wr[k], Rr[k], self.qr_op) for k in range(len(rows))], wr
+
+    def update_embeddings(self, r, cg, Or, rows, wr):
+        super().update_embeddings(r, cg, Or, rows, wr)
+        for k, w in enumerate(wr):
+            if w is not None:
+                self.Wr[r][k] = (w - self.lr_embeds * w.grad).detach()
+
+    def merge_rows(self):
+        super().merge_rows()
+        for k, c in enumerate(self.coll):
+            if c:               # Wr: a table all of whose rows every rank touched
+                every = [torch.arange(c, dtype=torch.int32) for _ in range(self.W)]
+                O.table_aggregate([self.Wr[r][k] for r in range(self.W)], every, self.agg_op)

@@ -11,8 +11,8 @@ Aux slots (the batch's misses) are skipped: no row write, no state update -- the
 reference semantics already drop a missed row's update.  S is one fp32 per TABLE row, starts at zero, and is keyed by index: a row
 that is evicted and re-inserted finds its accumulator where it left it.
 
-`RowwiseAdagradTrainer` is `OracleTrainer` with the embedding update replaced by `rowwise_adagrad_update`; nothing here imports
-the package under test.  `kernel_reference` / `kernel_bounds` are the float64 reference and the bounds the kernel tests hold
+`RowwiseAdagradTrainer` is `OracleTrainer` with one phase of its step replaced: `update_table`, the step of rank r's table k,
+which is `rowwise_adagrad_update` here; nothing here imports the package under test.  `kernel_reference` / `kernel_bounds` are the float64 reference and the bounds the kernel tests hold
 the HIP kernels to (and the host tests hold wrong variants of the update to: they must fail them).
 """
 import os
@@ -63,28 +63,19 @@ def rowwise_adagrad_update(weight, state, occ, P, slots, offsets, grad_out, lr, 
 
 
 class RowwiseAdagradTrainer(O.OracleTrainer):
-    """OracleTrainer (one rank) whose embedding update is row-wise Adagrad; `state[k]`: table k's n_k accumulators."""
+    """OracleTrainer (one rank, no victim write-back: as the engine refuses) whose update_table phase is row-wise Adagrad;
+    `state[k]`: table k's n_k accumulators, in the trainer's dtype."""
 
     def __init__(self, *a, adagrad_eps=1e-10, variant="rowwise", **kw):
         super().__init__(*a, **kw)
         assert self.W == 1 and not self.evict_victim
         self.eps, self.variant = float(adagrad_eps), variant
         D = self.weights[0][0].shape[1]
-        self.state = [torch.zeros((n, D) if variant == "elementwise" else (n,), dtype=torch.float32) for n in self.ln_emb]
+        self.state = [torch.zeros((n, D) if variant == "elementwise" else (n,), dtype=self.dtype) for n in self.ln_emb]
 
-    def step(self, j, X, lS_o, lS_i, T):
-        table_of = {id(w): k for k, w in enumerate(self.weights[0])}
-
-        def update(weight, slots, offsets, grad_out, lr):
-            k = table_of[id(weight)]
-            rowwise_adagrad_update(weight, self.state[k], self.occ[k], int(self.cache_sizes[k]), slots, offsets, grad_out, lr,
-                                   self.eps, variant=self.variant)
-
-        sgd, O.embbag_bwd_sgd = O.embbag_bwd_sgd, update
-        try:
-            return super().step(j, X, lS_o, lS_i, T)
-        finally:
-            O.embbag_bwd_sgd = sgd
+    def update_table(self, r, k, slots, offsets, grad_out):
+        rowwise_adagrad_update(self.weights[r][k], self.state[k], self.occ[k], int(self.cache_sizes[k]), slots, offsets, grad_out,
+                               self.lr_embeds, self.eps, variant=self.variant)
 
 
 # ---- what the kernel tests compare with -------------------------------------------------------------------------------------
@@ -120,16 +111,16 @@ def kernel_check(S, W, S0, W0, G, lr, eps, what=""):
     return float((dS / np.maximum(bS, 1e-300)).max()), float((dW / np.maximum(bW, 1e-300)).max())
 
 
-def criteo_batches(ln_emb, n_dense, B, nbatch, seed, heavy=()):
-    """[(X [B, n_dense], idx int64 [T, B], T [B, 1])]: Zipf indices scattered over each table; tables in `heavy` draw from
-    five indices only (long runs of one slot)."""
+def criteo_batches(ln_emb, n_dense, B, nbatch, seed, heavy=(), alpha=1.2):
+    """[(X [B, n_dense], idx int64 [T, B], T [B, 1])]: Zipf(alpha) indices scattered over each table; tables in `heavy` draw
+    from five indices only (long runs of one slot).  The stream the host and the GPU tests of a mode share."""
     rng = np.random.RandomState(seed)
     out = []
     for _ in range(nbatch):
         X = torch.from_numpy(rng.rand(B, n_dense).astype(np.float32))
         cols = []
         for k, n in enumerate(ln_emb):
-            z = rng.zipf(1.2, size=B).astype(np.int64)
+            z, n = rng.zipf(alpha, size=B).astype(np.int64), int(n)
             cols.append(torch.from_numpy((z % 5) * 7 % n if k in heavy else z * 2654435761 % n))
         T = torch.from_numpy(np.round(rng.rand(B, 1)).astype(np.float32))
         out.append((X, torch.stack(cols), T))

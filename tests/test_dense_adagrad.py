@@ -6,8 +6,8 @@
   2. cdlrm_mlp_wgrad_opt_ex on a layer set that reaches the reduction's bias part, 16-byte path and scalar path and the
      element-wise launches, in fp32, bf16 and bf16x3: gradients the bits of cdlrm_mlp_wgrad_ex, parameters and accumulators
      within the bounds of float64 Adagrad on those gradients;
-  3. TrainEngine(dense_optimizer="adagrad") per step against float64 on its own grad_flat, against the restated trainer, on two
-     ranks, through Run / --save-model / --load-model, and the default's golden tapes.
+  3. TrainEngine(dense_optimizer="adagrad") per step against float64 on its own grad_flat, against the restated trainer, with
+     row-wise Adagrad on the embedding rows against the two restated trainers composed, on two ranks, through Run / --save-model / --load-model, and the default's golden tapes.
 """
 import os
 import re
@@ -328,20 +328,29 @@ def _layers(dl):
     return _linears(dl.bot_l) + _linears(dl.top_l)
 
 
+def _within_the_share(what, got, ref):
+    """At most 0.5 % of the elements outside rtol 2e-5 / atol 1e-6."""
+    assert got.shape == ref.shape, what
+    out = np.abs(got - ref) > 1e-6 + 2e-5 * np.abs(ref)
+    print("%s outside rtol 2e-5 / atol 1e-6: %d of %d" % (what, int(out.sum()), out.size))
+    assert out.mean() <= 0.005, what
+
+
+def _dense_within_the_share(eng, dl, tr):
+    ls = _layers(dl)
+    got_p = torch.cat([l.weight.data.reshape(-1) for l in ls] + [l.bias.data.reshape(-1) for l in ls]).cpu().numpy()
+    got_S = torch.cat([eng.SW[l][:, :l.in_features].reshape(-1) for l in ls] + [eng.Sb[l].reshape(-1) for l in ls]).cpu().numpy()
+    _within_the_share("parameters", got_p, tr.dense_params().numpy())
+    _within_the_share("accumulators", got_S, tr.dense_state().numpy())
+
+
 def test_engine_matches_the_restated_trainer(ops):
     run = engine_run()
     tr, eng, dl = restated()[0], run["eng"], run["dl"]
     want = np.array([l[0] for l in tr.losses])
     print("max relative loss difference %.3g" % float(np.max(np.abs(run["losses"] - want) / np.abs(want))))
     np.testing.assert_allclose(run["losses"], want, rtol=1e-5)
-    ls = _layers(dl)
-    got_p = torch.cat([l.weight.data.reshape(-1) for l in ls] + [l.bias.data.reshape(-1) for l in ls]).cpu().numpy()
-    got_S = torch.cat([eng.SW[l][:, :l.in_features].reshape(-1) for l in ls] + [eng.Sb[l].reshape(-1) for l in ls]).cpu().numpy()
-    for what, got, ref in (("parameters", got_p, tr.dense_params().numpy()), ("accumulators", got_S, tr.dense_state().numpy())):
-        assert got.shape == ref.shape
-        out = np.abs(got - ref) > 1e-6 + 2e-5 * np.abs(ref)
-        print("%s outside rtol 2e-5 / atol 1e-6: %d of %d" % (what, int(out.sum()), out.size))
-        assert out.mean() <= 0.005, what
+    _dense_within_the_share(eng, dl, tr)
     assert float(eng.dense_state.max()) > 0
     # (the pad column of the first top layer's weight storage: zero gradient, zero state, never moved)
     from cdlrm_amd.model_no_ddp import _linears
@@ -374,6 +383,21 @@ def test_with_rowwise_adagrad_on_the_embedding_rows(ops):
     assert all(t["native"] is not None for t in eng._tapes.values())
     assert np.isfinite(both["losses"]).all() and float(eng.dense_state.max()) > 0 and float(eng.emb_state.max()) > 0
     assert both["losses"][0] == engine_run()["losses"][0] and not np.array_equal(both["losses"], engine_run()["losses"])
+    # against the two restated trainers composed (R.BothAdagradTrainer), by the criteria of the single-mode engine tests
+    if "both" not in _runs:
+        _runs["both"] = R.run_restated(restated()[1], embed="rowwise_adagrad")
+    tr, cg = _runs["both"], both["cg"]
+    want = np.array([l[0] for l in tr.losses])
+    print("max relative loss difference %.3g" % float(np.max(np.abs(both["losses"] - want) / np.abs(want))))
+    np.testing.assert_allclose(both["losses"], want, rtol=1e-5)
+    _dense_within_the_share(eng, both["dl"], tr)
+    state = eng.emb_state_to_host()
+    for k in range(len(R.LN_EMB)):
+        assert torch.equal(cg.occupancy_tables[k].cpu(), tr.occ[k]), k
+        nrow = R.ENGINE_CASE["ways"] * cg.cache_sizes[k]
+        _within_the_share("table %d cache-proper rows" % k, cg.emb_l[k].weight[:nrow].detach().cpu().numpy(),
+                          tr.weights[0][k][:nrow].numpy())
+        _within_the_share("table %d row-wise accumulators" % k, state[k].numpy(), tr.state[k].numpy())
 
 
 def test_sgd_default_issues_the_golden_tapes(ops):

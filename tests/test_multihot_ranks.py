@@ -239,60 +239,24 @@ def _ragged_oracle_class():
     from oracle import cdlrm_oracle as O
 
     class BagRangeOracle(O.OracleTrainer):
-        """The oracle's trainer with one change: rank r's slice is the bag range of engine.rank_bag_slice (the lookups of
-        samples [r * lbs, min(B, (r + 1) * lbs)), offsets rebased) instead of the one-lookup-per-sample cut."""
+        """The oracle's trainer with one phase of its step replaced, rank_slice: rank r's slice is the bag range of
+        engine.rank_bag_slice (the lookups of samples [r * lbs, min(B, (r + 1) * lbs)), offsets rebased) instead of the
+        one-lookup-per-sample cut."""
 
         def __init__(self, *a, batch_size, **kw):
             super().__init__(*a, **kw)
             self.lbs = math.ceil(batch_size / self.W)
 
-        def step(self, j, X, lS_o, lS_i, T):
-            Wn, lbs = self.W, self.lbs
-            rank_loss, params = [], []
+        def rank_slice(self, r, X, lS_o, lS_i, T):
             B = X.shape[0]
-            for r in range(Wn):
-                s0, s1 = min(B, r * lbs), min(B, (r + 1) * lbs)
-                Xr = X[s0:s1]
-                Ir, Or = [], []
-                for k in range(len(self.ln_emb)):
-                    a = int(lS_o[k][s0])
-                    e = int(lS_o[k][s1]) if s1 < B else int(lS_i[k].numel())
-                    Ir.append(lS_i[k][a:e])
-                    Or.append(lS_o[k][s0:s1] - a)
-                Tr = T[s0:s1]
-                ly, cg = O.cache_forward(self.occ, self.weights[r], self.cache_sizes, Or, Ir, self.host)
-                ly = [v.detach().requires_grad_(True) for v in ly]
-                bw = [w.detach().requires_grad_(True) for w in self.bot[r][0]]
-                bb = [b.detach().requires_grad_(True) for b in self.bot[r][1]]
-                tw = [w.detach().requires_grad_(True) for w in self.top[r][0]]
-                tb = [b.detach().requires_grad_(True) for b in self.top[r][1]]
-                Z = O.dlrm_forward(Xr, ly, (bw, bb), (tw, tb), self.op, self.itself, self.loss_threshold)
-                E = O.loss_fn(Z, Tr, self.loss_kind, self.loss_ws)
-                E.backward()
-                rank_loss.append(float(E.detach()))
-                params.append((bw, bb, tw, tb))
-                for k in range(len(self.ln_emb)):
-                    O.embbag_bwd_sgd(self.weights[r][k], cg[k].long(), Or[k], ly[k].grad, self.lr_embeds)
-                self.touched[r].append(list(cg))
-            for li in range(len(params[0][0])):
-                g = sum(params[r][0][li].grad / Wn for r in range(Wn))
-                for r in range(Wn):
-                    params[r][0][li].grad = g.clone()
-            for li in range(len(params[0][2])):
-                g = sum(params[r][2][li].grad / Wn for r in range(Wn))
-                for r in range(Wn):
-                    params[r][2][li].grad = g.clone()
-            for r in range(Wn):
-                bw, bb, tw, tb = params[r]
-                self.bot[r] = ([(w - self.lr * w.grad).detach() for w in bw], [(b - self.lr * b.grad).detach() for b in bb])
-                self.top[r] = ([(w - self.lr * w.grad).detach() for w in tw], [(b - self.lr * b.grad).detach() for b in tb])
-            if j > 0 and j % self.agg_freq == 0:
-                for k in range(len(self.ln_emb)):
-                    touched = [torch.cat([t[k] for t in self.touched[r]]) for r in range(Wn)]
-                    O.table_aggregate([self.weights[r][k] for r in range(Wn)], touched, self.agg_op)
-                self.touched = [[] for _ in range(Wn)]
-            self.losses.append(rank_loss)
-            return rank_loss
+            s0, s1 = min(B, r * self.lbs), min(B, (r + 1) * self.lbs)
+            Ir, Or = [], []
+            for k in range(len(self.ln_emb)):
+                a = int(lS_o[k][s0])
+                e = int(lS_o[k][s1]) if s1 < B else int(lS_i[k].numel())
+                Ir.append(lS_i[k][a:e])
+                Or.append(lS_o[k][s0:s1] - a)
+            return X[s0:s1], Or, Ir, T[s0:s1], None
 
     return BagRangeOracle
 
