@@ -112,7 +112,9 @@ static int cdlrm_grant_dynamic_lds(size_t lds) {
 //      (sixteen for a lone head) in flight instead of one head x four (eight): bit-identical.
 //      -DCDLRM_DEV builds ONLY (timing experiments that SKIP work; the shipped library refuses them): 1 = no embedding
 //      update, 2 = no slot sort
-//   7: bits: 1 = the epilogues before round 5 (operands fetched behind, not ahead of, their use) -- bit-identical to the default
+//   7: bits: 1 = the epilogues before round 5 (operands fetched behind, not ahead of, their use) -- bit-identical to the default;
+//      2 = the split-M weight gradients of a long-batch cdlrm_mlp_wgrad* call as one launch per layer, never as one grouped
+//      launch (k_wgrad_long; the rule: wgrad_long_group, dense.hip) -- bit-identical to the default
 // No key makes the shipped library skip work: a number measured with any of them set is a number for the same arithmetic.
 extern CDLRM_HIDDEN_DATA int g_cdlrm_debug[8];
 

@@ -519,7 +519,8 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
 //     one slab count for all of them, then ONE grouped reduction
 //   long batches:
 //     WG_SPLIT   per layer one split-M GEMM (gemm_plan picks the kernel: tiled, or LDS-free for degenerate shapes) into the
-//                layer's own slabs, then ONE grouped reduction of all layers
+//                layer's own slabs, then ONE grouped reduction of all layers.  The GEMMs of a call whose layers are all on the
+//                LDS-DMA or the LDS-free kernel go out as ONE launch where wgrad_long_group's rule admits it (c3's bottom MLP)
 //   flags & CDLRM_GEMM_BF16 or CDLRM_GEMM_BF16X3 (gemm_bf16.h; the same layout, one or two operand planes), any batch:
 //     WG_BF16    the layers the shape rule admits (bf16_layer_ok) as one grouped bf16 launch on 64x64 tiles with one slab length
 //                (bf16_wgrad_kchunk), then one grouped reduction of their slabs.  The other layers (the 13-wide input, the 1-wide
@@ -532,7 +533,10 @@ extern "C" int cdlrm_linear_bwd_route(const float* X, int64_t ld_x, const float*
 //  split-M slabs.  Parity-green, 12.5 / 11.4 us stand-alone with their reductions at M = 8192 -- and a TIE in the step against
 //  the LDS-free MFMA kernel they were to replace: 0.6125 against 0.6113 ms (13-wide), 0.6148 against 0.6146 (1-wide), same box,
 //  same process, tools/ab_step.py.  Where these launches sit -- the end of the backward, three queues deep -- a kernel's
-//  duration is set by what runs beside it (30 us in the trace for either version), not by its own instruction mix.  Removed.)
+//  duration is set by what runs beside it (30 us in the trace for either version), not by its own instruction mix.  Removed.
+//  Both experiments left the thin layer a launch of its OWN on the training queue, which nothing of the same call may overtake:
+//  45 us of queue time at c3.  What helps is taking that serial slot away, not a faster kernel in it: the layer's blocks now
+//  ride in the grid of the call's MFMA tiles -- k_wgrad_long, wgrad_long_group below: 0.5226 against 0.5345 ms per c3 step.)
 enum { WG_DIRECT, WG_TILED, WG_SPLIT, WG_BF16, WG_FAMILIES };
 struct WgradLayer {
     int family;
@@ -694,6 +698,47 @@ static void launch_reduce_jobs(const std::vector<ReduceJob>& jobs, hipStream_t s
     }
 }
 
+// Whether the WG_SPLIT launches of one long-batch fp32 call go out as ONE grouped launch (k_wgrad_long, gemm_glds.h), and that
+// launch.  g[i] / plan[i]: the layers' problems with the plans gemm_plan made for them -- routes, tiles, slabs and grids are
+// the per-layer ones; only the number of launches that carry them changes.  A call is grouped when
+//   * every plan is CDLRM_ROUTE_GEMM2 (tn = 1, no dynamic LDS) or CDLRM_ROUTE_DIRECT, at least one of each, the LDS-free ones in
+//     ONE variant of their body as launch_wgrad_mixed requires -- here the aligned loader with one batch of loads per wave
+//     (mode 0: slabs of up to 256 rows, a thin layer's up to M = 32768), the variant k_wgrad_long is built on;
+//   * each family has at most GEMM_GROUP_MAX layers;
+//   * the LDS-DMA workgroups total at most 4 per CU: c3's bottom call (512 + 256 of them) and not the top call's 1536 -- that
+//     launch held every workgroup slot of the chip for 250 us on a side queue while the training queue's GEMMs waited for slots
+//     (round 3, the note at k_gemm2); the top call keeps its per-layer launches;
+//   * the LDS-free workgroups total at most 2 per CU (c3's 512).  In the group each of them holds a 48 KB LDS slot where its own
+//     kernel holds 17 KB, and the kernels of the other two queues get what is left: c5's bottom call (2048 of them, 8 per CU,
+//     on the two-batch variant) ran the step at 3.97 ms grouped against 3.68 per layer (profiles/wgrad_long_group_ab.txt) and
+//     keeps its per-layer launches.  Between 2 and 8 per CU nothing is measured.
+// cdlrm_debug_set(7, 2): never (the per-layer launches; bit-identical).  Returns 1 when it launched, 0: launch layer by layer.
+static int wgrad_long_group(const GemmArgs* g, const GemmPlan* plan, int n, int n_cu, hipStream_t s) {
+    if (g_cdlrm_debug[7] & 2) return 0;
+    GemmGroup dgrp, tgrp;
+    memset(&dgrp, 0, sizeof(dgrp));
+    memset(&tgrp, 0, sizeof(tgrp));
+    uint64_t dblocks = 0, tblocks = 0;
+    unsigned tm2 = 0;
+    for (int i = 0; i < n; ++i) {
+        const cdlrm_gemm_route& r = plan[i].r;
+        const bool direct = r.family == CDLRM_ROUTE_DIRECT && r.aligned && r.mode == 0;
+        if (!direct && !(r.family == CDLRM_ROUTE_GEMM2 && r.tn == 1 && plan[i].lds == 0)) return 0;
+        GemmGroup& grp = direct ? dgrp : tgrp;
+        uint64_t& blocks = direct ? dblocks : tblocks;
+        if (grp.n == GEMM_GROUP_MAX) return 0;
+        if (!direct && r.tm == 2) tm2 |= 1u << grp.n;
+        grp.first[grp.n] = (unsigned)blocks;
+        grp.g[grp.n++] = g[i];
+        blocks += (uint64_t)plan[i].grid.x * plan[i].grid.y * plan[i].grid.z;
+    }
+    if (dgrp.n < 1 || tgrp.n < 1 || tblocks > 4 * (uint64_t)n_cu || dblocks > 2 * (uint64_t)n_cu) return 0;
+    dgrp.first[dgrp.n] = (unsigned)dblocks;
+    tgrp.first[tgrp.n] = (unsigned)tblocks;
+    launch_wgrad_long(dgrp, (unsigned)dblocks, tgrp, (unsigned)tblocks, tm2, s);
+    return 1;
+}
+
 // All of cdlrm_mlp_wgrad*: build the layout, then either translate it into routes (rout: the route query, one entry per layer,
 // nothing launched, no pointer read) or walk it and launch.  P_w / P_b (both or neither): the layers' parameters, stepped by
 // -lr * gradient in the reduction pass (layers whose gradient needs no reduction: one elementwise launch behind it) -- or, ada
@@ -815,13 +860,18 @@ static int mlp_wgrad_run(int32_t n_layers, const float* const* X, const int64_t*
             }
         } else {
             stage(WG_SPLIT);
-            size_t q = 0;
-            for (int i = 0; i < n_layers; ++i) {
-                if (p.L[i].family != WG_SPLIT) continue;
-                GemmArgs& g = probs[q++];
-                const GemmPlan gp = gemm_plan<false, false>(g, p.L[i].zs, 0, gemm_device_cus());
-                int rc = gemm_launch<false, false>(gp, g, s);
-                if (rc) return rc;
+            std::vector<GemmPlan> plans;
+            plans.reserve(probs.size());
+            for (int i = 0; i < n_layers; ++i)
+                if (p.L[i].family == WG_SPLIT)
+                    plans.push_back(gemm_plan<false, false>(probs[plans.size()], p.L[i].zs, 0, gemm_device_cus()));
+            // one grouped launch where the call is one wgrad_long_group takes (an all-fp32 call: beside a bf16 group only the
+            // LDS-free layers are left here), else a launch per layer
+            if (flags || !wgrad_long_group(probs.data(), plans.data(), (int)plans.size(), gemm_device_cus(), s)) {
+                for (size_t q = 0; q < plans.size(); ++q) {
+                    int rc = gemm_launch<false, false>(plans[q], probs[q], s);
+                    if (rc) return rc;
+                }
             }
         }
         int rc = finish(false);

@@ -486,3 +486,74 @@ static void launch_gemm2(const GemmArgs& g, int tm, int tn, dim3 grid, size_t dy
     else if (tm == 1 && tn == 2) CDLRM_LAUNCH_EV((k_gemm2<A_KC, B_KC, 1, 2>), grid, dim3(256), dyn, s, g);
     else CDLRM_LAUNCH_EV((k_gemm2<A_KC, B_KC, 1, 1>), grid, dim3(256), dyn, s, g);
 }
+
+// The split-M weight gradients of ONE long-batch call (cdlrm_mlp_wgrad* above WGRAD_DIRECT_MAX_M) as one launch: the thin
+// layers' LDS-free blocks (a 13-wide input, a 1-wide output: latency-bound, next to no MFMA work) and the LDS-DMA tiles of the
+// other layers in one grid, as k_wgrad_mixed (gemm.h) does for the short batches.  Launched one after the other on one queue,
+// a thin layer's kernel holds that queue until its last workgroup has ended while the matrix pipe idles, and every launch
+// boundary adds a lock-step store tail.  Same problems, same tiles, same slabs as the per-layer launches (a tile's k order does
+// not depend on the launch it runs in): bit-identical.  Which calls take it: wgrad_long_group (dense.hip).
+//   dgrp: the CDLRM_ROUTE_DIRECT problems, all on the aligned loader with one batch of loads per wave (direct_body's MODE 0:
+//   101 + 32 registers; the two-batch forms need 159 + 32 and more, which would leave two blocks per CU for the tiles as well);
+//   tgrp: the CDLRM_ROUTE_GEMM2 problems on (64 * TM) x 64 tiles, TM = 2 for problem p where bit p of tm2 is set, else 1 (the
+//   plan's tn is 1 for every split weight gradient).
+// Every block reserves the largest body's LDS, the 128x64 tile's 48 KB: three blocks per CU, as k_gemm2<.., 2, 1> alone -- and a
+// thin block holds 48 KB where its own kernel holds 17.
+// Block order, after xcd_remap (each XCD then gets the same mix): one thin block per two tiles, what is left of either kind
+// behind them.  Measured against thin blocks first / last in the c3 step (profiles/wgrad_long_group_ab.txt): 0.5226 against
+// 0.5279 / 0.5296 ms, per-layer launches 0.5345.
+__global__ void __launch_bounds__(256) k_wgrad_long(GemmGroup dgrp, GemmGroup tgrp, unsigned n_direct, unsigned tm2) {
+    constexpr int RED_FLOATS = 4 * 32 * 33 + 4 * 32, TILE_FLOATS = 2 * 64 * (2 + 1) * G2_BK;
+    static_assert(RED_FLOATS <= TILE_FLOATS, "the LDS-free body's reduction buffers fit in the tile stages");
+    // ONE LDS object, as in k_gemm2
+    __shared__ __attribute__((aligned(1024))) float lds[TILE_FLOATS];
+    const unsigned wgid = xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned n_tiles = gridDim.x - n_direct;
+    const unsigned ni = min(n_direct, n_tiles / 2);     // trios of one thin block and two tiles
+    bool thin;
+    unsigned w;         // index among the blocks of its kind
+    if (wgid < 3 * ni) {
+        const unsigned trio = wgid / 3, r = wgid % 3;
+        thin = r == 0;
+        w = thin ? trio : 2 * trio + r - 1;
+    } else {
+        const unsigned rem = wgid - 3 * ni, left = n_direct - ni;
+        thin = rem < left;
+        w = thin ? ni + rem : 2 * ni + rem - left;
+    }
+    if (thin) {
+        int p = 0;
+#pragma unroll
+        for (int q = 1; q < GEMM_GROUP_MAX; ++q)
+            if (q < dgrp.n && w >= dgrp.first[q]) p = q;
+        const GemmArgs& g = dgrp.g[p];
+        const unsigned local = w - dgrp.first[p];
+        const unsigned gx = (unsigned)((g.N + 31) / 32), gy = (unsigned)((g.M + 31) / 32);
+        float (*red)[32][33] = reinterpret_cast<float (*)[32][33]>(lds);
+        float (*csr)[32] = reinterpret_cast<float (*)[32]>(lds + 4 * 32 * 33);
+        direct_body<false, false, false, false, 0, true>(g, local % gx, (local / gx) % gy, local / (gx * gy), red, csr);
+    } else {
+        int p = 0;
+#pragma unroll
+        for (int q = 1; q < GEMM_GROUP_MAX; ++q)
+            if (q < tgrp.n && w >= tgrp.first[q]) p = q;
+        const GemmArgs& g = tgrp.g[p];
+        const unsigned local = w - tgrp.first[p];
+        const unsigned gx = (unsigned)((g.N + 63) / 64);
+        if ((tm2 >> p) & 1) {       // uniform: a problem's tile is one of the two for all its workgroups
+            const unsigned gy = (unsigned)((g.M + 127) / 128);
+            gemm2_tile_body<false, false, 2, 1>(g, local % gx, (local / gx) % gy, local / (gx * gy), lds);
+        } else {
+            const unsigned gy = (unsigned)((g.M + 63) / 64);
+            gemm2_tile_body<false, false, 1, 1>(g, local % gx, (local / gx) % gy, local / (gx * gy), lds);
+        }
+    }
+}
+
+// No completion event can be pending at this launch: only cdlrm_linear_bwd and cdlrm_interact_bwd open a CdlrmStopScope
+// (common.h), and outside one no launch site takes an attached event -- the per-layer launches of these calls (launch_gemm2's
+// CDLRM_LAUNCH_EV) never carried one either.
+static inline void launch_wgrad_long(const GemmGroup& dgrp, unsigned dblocks, const GemmGroup& tgrp, unsigned tblocks, unsigned tm2,
+                                     hipStream_t s) {
+    hipLaunchKernelGGL(k_wgrad_long, dim3(dblocks + tblocks), dim3(256), 0, s, dgrp, tgrp, dblocks, tm2);
+}

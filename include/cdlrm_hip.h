@@ -57,7 +57,8 @@ int cdlrm_abi_version(void);
  * config.debug).  All zero unless a tool sets them.  No key skips work in the shipped library (the two timing experiments that
  * do -- key 6, bits 1 and 2 -- are compiled in by -DCDLRM_DEV only and refused here otherwise); variants are bit-identical
  * except the GEMM kernel selectors of key 6, whose kernels differ in contraction order (equal to fp32 rounding); grid sizes
- * only change placement.  The list of keys: csrc/common.h. */
+ * only change placement.  cdlrm_debug_set(7, 2): the weight gradients of a long-batch cdlrm_mlp_wgrad* call as one launch
+ * per layer instead of the grouped launch (bit-identical).  The list of keys: csrc/common.h. */
 int cdlrm_debug_set(int32_t key, int32_t value);
 const char* cdlrm_last_error(void);
 
