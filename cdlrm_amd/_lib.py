@@ -60,6 +60,10 @@ class InteractRoute(C.Structure):
     _fields_ = [("family", c_i32), ("d4", c_i32), ("ns", c_i32), ("reserved", c_i32), ("grid", c_i64), ("lds_bytes", c_i64)]
 
 
+class HeadRoute(C.Structure):
+    _fields_ = [("vec", c_i32), ("tail", c_i32), ("one", c_i32), ("finish_launch", c_i32), ("grid", c_i64), ("passes", c_i64)]
+
+
 # name -> (restype, argtypes); every symbol include/cdlrm_hip.h declares
 PROTOTYPES = {
     "cdlrm_abi_version": (C.c_int, []),
@@ -153,6 +157,7 @@ PROTOTYPES = {
     "cdlrm_head_fwd_bwd": (C.c_int, [vp, c_i64, vp, vp, vp, c_i64, c_i32, c_i32, C.c_float, C.c_float, C.c_float, c_i32,
                                      vp, vp, vp, vp, c_i64, vp, vp, c_i32, vp]),
     "cdlrm_head_finish": (C.c_int, [vp, c_i64, vp, vp, vp]),
+    "cdlrm_head_route": (C.c_int, [c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, C.POINTER(HeadRoute)]),
     "cdlrm_sgd_step2": (C.c_int, [vp, vp, c_i64, c_i64, c_i64, c_i64, C.c_float, vp]),
     "cdlrm_act_bwd": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, c_i32, c_i32, vp]),
     "cdlrm_sgd_step": (C.c_int, [vp, vp, c_i64, c_f32, vp]),

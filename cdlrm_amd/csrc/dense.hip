@@ -2345,6 +2345,37 @@ static int64_t head_grid(int64_t B) {
     return gx > HEAD_MAX_BLOCKS ? HEAD_MAX_BLOCKS : gx;     // B > 16384: more passes
 }
 
+// What a head call launches -- a pure function of its shape, its pitches, the alignment of Y / w / dY and `finish`.
+// cdlrm_head_fwd_bwd launches what it says, cdlrm_head_route() reports it.
+struct HeadPlan {
+    bool vec;           // k_head<true, .>: float4 accesses to Y, w and dY
+    bool tail;          // k_head<., true>: the last workgroup to arrive sums the partials (no k_head_finish launch)
+    bool one;           // vec && K <= 256: a row is one float4 per lane, kept in registers for the dY pass
+    int64_t grid;       // workgroups of 4 waves x 4 rows
+    int64_t passes;     // rows a wave walks / 4: ceil(B / (16 * grid))
+};
+
+static HeadPlan head_plan(int64_t B, int K, int64_t ldy, int64_t lddy, bool aligned_y, bool aligned_w, bool aligned_dy,
+                          bool has_dy, bool finish) {
+    HeadPlan p{};
+    p.grid = head_grid(B);
+    p.vec = K % 4 == 0 && ldy % 4 == 0 && (!has_dy || lddy % 4 == 0) && aligned_y && aligned_w && (!has_dy || aligned_dy);
+    p.tail = finish && p.grid <= HEAD_TAIL_BLOCKS;
+    p.one = p.vec && K <= 256;
+    p.passes = cdiv(B, 16 * p.grid);
+    return p;
+}
+
+extern "C" int cdlrm_head_route(int64_t B, int32_t K, int64_t ldy, int64_t lddy, int32_t aligned, int32_t has_dY,
+                                int32_t finish, struct cdlrm_head_route* out) {
+    CDLRM_REQUIRE(out && B >= 1 && K >= 1, "bad argument");
+    const HeadPlan p = head_plan(B, K, ldy, lddy, aligned & 1, aligned & 2, aligned & 4, has_dY != 0, finish != 0);
+    out->vec = p.vec; out->tail = p.tail; out->one = p.one;
+    out->finish_launch = finish && !p.tail;
+    out->grid = p.grid; out->passes = p.passes;
+    return 0;
+}
+
 extern "C" int cdlrm_head_fwd_bwd(const float* Y, int64_t ldy, const float* w, const float* bias, const float* target,
                                   int64_t B, int32_t K, int32_t kind, float w0, float w1, float threshold,
                                   int32_t x_act, float* Z, float* Zc, float* dZ, float* dY, int64_t lddy,
@@ -2353,9 +2384,9 @@ extern "C" int cdlrm_head_fwd_bwd(const float* Y, int64_t ldy, const float* w, c
     CDLRM_REQUIRE(kind >= 0 && kind <= 2 && x_act >= 0 && x_act <= 2, "bad loss kind / activation");
     LossCfg c;
     c.kind = kind; c.w0 = w0; c.w1 = w1; c.thr = threshold;
-    const int64_t gx = head_grid(B);
-    const bool vec = K % 4 == 0 && ldy % 4 == 0 && (!dY || lddy % 4 == 0) && (((uintptr_t)Y | (uintptr_t)w | (uintptr_t)dY) & 15) == 0;
-    const bool tail = finish && gx <= HEAD_TAIL_BLOCKS;
+    const HeadPlan p = head_plan(B, K, ldy, lddy, aligned16(Y), aligned16(w), aligned16(dY), dY != nullptr, finish != 0);
+    const int64_t gx = p.grid;
+    const bool vec = p.vec, tail = p.tail;
 #define HEAD_CALL(V_, T_)                                                                                      \
     hipLaunchKernelGGL((k_head<V_, T_>), dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, Y, ldy, w, bias, target, B, \
                        (int)K, c, (int)x_act, Z, Zc, dZ, dY, lddy, loss_out, scratch)

@@ -941,6 +941,18 @@ def head_fwd_bwd(Y: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor],
                                         loss_buf.data_ptr(), scratch.data_ptr(), 1 if finish else 0, stream_ptr(stream)))
 
 
+def head_route(B: int, K: int, ldy: int, lddy: int, aligned: int = 7, has_dY: bool = True, finish: bool = True) -> dict:
+    """What one head_fwd_bwd call launches, from the same decision code, without launching it.  aligned: bit 0 = Y is 16-byte
+    aligned, bit 1 = w, bit 2 = dY (has_dY False: lddy and bit 2 are not looked at).  path: "one" (a float4 per lane, K <= 256),
+    "multi" (float4 trips of 256 columns) or "scalar"; tail: the launch completes loss_buf itself; finish_launch: head_finish is
+    launched behind it; grid workgroups of 16 rows, passes = ceil(B / (16 * grid)).  No device is touched."""
+    out = _lib.HeadRoute()
+    check(_lib.raw().cdlrm_head_route(int(B), int(K), int(ldy), int(lddy), int(aligned), int(bool(has_dY)), int(bool(finish)),
+                                      C.byref(out)))
+    return {"path": "one" if out.one else "multi" if out.vec else "scalar", "vec": bool(out.vec), "tail": bool(out.tail),
+            "finish_launch": bool(out.finish_launch), "grid": out.grid, "passes": out.passes}
+
+
 def head_finish(scratch: torch.Tensor, B: int, loss_buf: torch.Tensor, stream=None, acc: Optional[torch.Tensor] = None):
     """acc: float64 [2] on the device, += [correct predictions, loss * B] of this batch."""
     assert acc is None or (acc.dtype == torch.float64 and acc.numel() >= 2 and acc.is_contiguous())

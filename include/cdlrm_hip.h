@@ -711,6 +711,19 @@ int cdlrm_head_fwd_bwd(const float* Y, int64_t ldy, const float* w, const float*
                        float* Z, float* Zc, float* dZ, float* dY, int64_t lddy, float* loss_out, float* scratch,
                        int32_t finish, void* stream);
 int cdlrm_head_finish(const float* scratch, int64_t B, float* loss_out, double* acc, void* stream);
+struct cdlrm_head_route {       /* (a struct tag: the query below has the name) */
+    int32_t vec;                /* 1: float4 accesses to Y, w and dY (K, both pitches multiples of 4, all three 16-byte aligned) */
+    int32_t tail;               /* 1: the last workgroup to arrive completes loss_out in the same launch (finish, B <= 2048) */
+    int32_t one;                /* 1: vec and K <= 256 -- a row is one float4 per lane; 0 with vec: several trips over K */
+    int32_t finish_launch;      /* 1: cdlrm_head_fwd_bwd launches cdlrm_head_finish itself (finish, no tail) */
+    int64_t grid;               /* workgroups of 256 lanes: 4 waves x 4 rows, at most 1024 */
+    int64_t passes;             /* ceil(B / (16 * grid)): 4-row groups a wave walks */
+};
+/* The plan of one cdlrm_head_fwd_bwd call without the launch: the call's B, K, ldy, lddy and finish; aligned: bit 0 = Y is 16-byte
+ * aligned, bit 1 = w is, bit 2 = dY is; has_dY: dY != NULL (0: lddy and bit 2 are not looked at).  The answer comes out of the
+ * same decision code the launching call runs.  No device is touched. */
+int cdlrm_head_route(int64_t B, int32_t K, int64_t ldy, int64_t lddy, int32_t aligned, int32_t has_dY, int32_t finish,
+                     struct cdlrm_head_route* out);
 
 /* p -= lr * g over a flat fp32 buffer (optim.SGD without momentum, main_no_ddp.py:375, 415). */
 int cdlrm_sgd_step(float* param, const float* grad, int64_t n, float lr, void* stream);
