@@ -172,6 +172,8 @@ PROTOTYPES = {
     "cdlrm_bags_rank_slice": (C.c_int, [vp, c_i64, vp, c_i32, c_i32, c_i32, vp, c_i64, c_i64, c_i64, c_i64, vp, vp, vp]),
     "cdlrm_dayfile_window": (C.c_int, [vp, vp, vp, c_i64, c_i32, c_i32, c_i64, vp, vp, c_i64, c_i64, vp, vp]),
     "cdlrm_dayfile_tile": (C.c_int, []),
+    "cdlrm_rows_window": (C.c_int, [vp, vp, vp, c_i64, vp, c_i64, c_i32, c_i32, c_i64, vp, vp, c_i64, c_i64, vp, vp]),
+    "cdlrm_rows_tile": (C.c_int, []),
     "cdlrm_binfile_window": (C.c_int, [vp, c_i64, c_i32, c_i32, c_i64, vp, vp, c_i64, c_i64, vp, vp]),
     "cdlrm_binfile_tile": (C.c_int, []),
     "cdlrm_tape_create": (vp, [c_i32]),

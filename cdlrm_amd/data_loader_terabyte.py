@@ -18,7 +18,9 @@ out -- a step gets views, no copy, no launch.
 The MLPerf binary files (`--mlperf-bin-loader`; data_loader_terabyte.py:195-275) are read by `CriteoBinDataset` / `BinLoader`
 on the host and `DeviceBinLoader` on the device: one file per split, a record = [y, dense, categorical] int32, entry idx =
 records [idx * B, (idx + 1) * B).  `bin_extents` is their batch geometry as arithmetic; the device loader shares its ring,
-staging and hand-out with `DeviceDayLoader` (`_DeviceWindowLoader`) and cuts with csrc/binfile.hip."""
+staging and hand-out with `DeviceDayLoader` (`_DeviceWindowLoader`) and cuts with csrc/binfile.hip.
+
+The third dataset arm, the in-memory processed file, is data_loader_processed.py; its device loader takes the ring from here."""
 from __future__ import annotations
 
 import math
@@ -265,7 +267,10 @@ class _DeviceWindowLoader:
         _pieces(batches)         the pieces of a window's batches, in order: (rows, source) with rows <= self._stage_rows
         _fill(h, rows, source)   write the piece's raw int32 dwords, rows * (n_dense + n_cat + 1) of them, to h (pinned)
         _cut(d, rows, slot, col) launch the kernel that cuts the piece's dwords d (device) into the slot at column col
-        _rows(batch)             samples of one batch"""
+        _rows(batch)             samples of one batch
+
+    A loader whose rows are already on the device (data_loader_processed.DeviceProcessedLoader) takes the ring alone
+    (`_setup_ring`) and brings an `_upload` of its own: no staging is allocated for it."""
 
     RING = 3
     STAGE_BATCHES = 64
@@ -274,23 +279,30 @@ class _DeviceWindowLoader:
     _slots = None
     _uploads = 0                # windows uploaded so far, over all epochs: upload u lives in slot u % RING
 
-    def _setup(self, n_batches: int):
+    def _setup_ring(self, n_batches: int) -> int:
+        """The loader's stream, the ring of window buffers, the shared lS_o and the helper thread; returns a window's rows."""
         B, dev = self.batch_size, self.device
         W = min(self.window, n_batches) * B
-        width = self.n_dense + self.n_cat + 1
-        self._stage_rows = min(W, self.STAGE_BATCHES * B)
         with torch.cuda.device(dev):
             self._copy = torch.cuda.Stream(device=dev)
             self._slots = [dict(X=torch.empty(W, self.n_dense, dtype=torch.float32, device=dev),
                                 I=torch.empty(self.n_cat, W, dtype=torch.int64, device=dev),
                                 T=torch.empty(W, 1, dtype=torch.float32, device=dev), ev=torch.cuda.Event(), consumers=set())
                            for _ in range(self.RING)]
+        self._lS_o = torch.arange(B, device=dev).repeat(self.n_cat, 1)
+        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=self.THREAD)
+        return W
+
+    def _setup(self, n_batches: int):
+        B, dev = self.batch_size, self.device
+        W = self._setup_ring(n_batches)
+        width = self.n_dense + self.n_cat + 1
+        self._stage_rows = min(W, self.STAGE_BATCHES * B)
+        with torch.cuda.device(dev):
             self._stage = [dict(host=torch.empty(self._stage_rows * width, dtype=torch.int32).pin_memory(),
                                 dev=torch.empty(self._stage_rows * width, dtype=torch.int32, device=dev), ev=None)
                            for _ in range(2)]
         self._pieces_done = 0
-        self._lS_o = torch.arange(B, device=dev).repeat(self.n_cat, 1)
-        self._pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix=self.THREAD)
 
     def _submit(self, batches):
         """Start the upload of the window made of `batches` into the next ring slot (see the ring rule)."""

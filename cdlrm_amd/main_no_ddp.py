@@ -132,7 +132,9 @@ def ProcessArgs(argv=None):
     parser.add_argument("--day-file-loader", type=str, default="host", choices=["host", "device"],
                         help="--data-generation=dataset: `host` = the reference's per-batch host loader; `device` = the raw rows "
                              "of a whole look-ahead window are uploaded ahead and cut into batches on the GPU "
-                             "(data_loader_terabyte.DeviceDayLoader; with --mlperf-bin-loader: BinLoader / DeviceBinLoader)")
+                             "(data_loader_terabyte.DeviceDayLoader; with --mlperf-bin-loader: BinLoader / DeviceBinLoader; with an "
+                             "existing --processed-data-file and no --memory-map: ProcessedLoader / DeviceProcessedLoader, "
+                             "which keeps the file's rows resident in HBM)")
     parser.add_argument("--device-rng", action="store_true", default=False,
                         help="way choice by counter-based Philox on the GPU (perf mode; not bit-comparable with the "
                              "reference's torch-CPU Categorical draw)")
@@ -853,6 +855,49 @@ def main(argv=None):
             print("MLPerf binary loader: %s (%s) reads %s, %d batches of %d%s; test: %s" % (
                 type(train_ld).__name__, args.day_file_loader, train_file, len(train_ld), args.mini_batch_size,
                 ", shuffled" if args.mlperf_bin_shuffle else "", test_file), flush=True)
+    elif args.data_generation == "dataset" and not args.memory_map and os.path.isfile(args.processed_data_file):
+        # the in-memory processed file of the reference's default dataset path (dlrm_data_pytorch.py:47-320, :493-545; the
+        # CLI's default --data-set=kaggle takes it): one .npz split by the day counts, ordered by --data-randomize.  Taken
+        # exactly when --memory-map is off and --processed-data-file exists (the reference would start its ETL otherwise; the
+        # Criteo pre-processing is not part of this program -- --data-sub-sample-rate is a flag of that ETL alone).  Train,
+        # then test, draw from the generator seeded above, as main_no_ddp.py:509, :525 do: every rank draws the same order.
+        # The training loader leaves the short last batch out, as the other two arms do (a step's batch is sliced across ranks).
+        from .data_loader_processed import (RANDOMIZE, DeviceProcessedLoader, ProcessedDataset, ProcessedLoader,
+                                            processed_order, processed_paths)
+        if args.data_randomize not in RANDOMIZE:
+            sys.exit("ERROR: --data-randomize=%s is not supported (total | day | none)" % args.data_randomize)
+        try:
+            days, _, count_file = processed_paths(args.data_set, args.raw_data_file)
+        except ValueError:
+            sys.exit("ERROR: --data-set=%s is not supported with --processed-data-file (kaggle | terabyte)" % args.data_set)
+        if not os.path.isfile(count_file):
+            sys.exit("ERROR: %s does not exist (the day counts of %s; the Criteo pre-processing that writes it is not part of "
+                     "this program)" % (count_file, args.processed_data_file))
+        try:
+            with np.load(count_file) as data:
+                total_per_file = data["total_per_file"]
+            if len(total_per_file) != days:
+                raise ValueError("%s lists %d days, --data-set=%s has %d" % (count_file, len(total_per_file), args.data_set, days))
+            data = ProcessedDataset(args.processed_data_file, total_per_file)
+        except ValueError as e:
+            sys.exit("ERROR: " + str(e))
+        train_order = processed_order(total_per_file, "train", args.data_randomize)
+        test_order = processed_order(total_per_file, "test", args.data_randomize)
+        args.arch_embedding_size = "-".join(str(int(c)) for c in data.counts)
+        ln_bot[0] = data.m_den          # main_no_ddp.py:530-538
+        tb = args.test_mini_batch_size if args.test_mini_batch_size > 0 else args.mini_batch_size
+        if args.day_file_loader == "device":
+            # (the device is chosen below: the loaders touch it when they are first iterated)
+            train_ld = DeviceProcessedLoader(data, train_order, args.mini_batch_size, args.max_ind_range, True,
+                                             window=args.lookahead)
+            test_ld = DeviceProcessedLoader(data, test_order, tb, args.max_ind_range, window=16)
+        else:
+            train_ld = ProcessedLoader(data, train_order, args.mini_batch_size, args.max_ind_range, True)
+            test_ld = ProcessedLoader(data, test_order, tb, args.max_ind_range)
+        if rank == 0:
+            print("Processed-file loader: %s (%s) reads %s, %d batches of %d, --data-randomize=%s; test: %d batches of %d" % (
+                type(train_ld).__name__, args.day_file_loader, args.processed_data_file, len(train_ld), args.mini_batch_size,
+                args.data_randomize, len(test_ld), tb), flush=True)
     elif args.data_generation == "dataset":
         # the pre-processed day files of the reference's terabyte path (dlrm_data_pytorch.py:440-492): table sizes
         # from <raw>_fea_count.npz (:180-181), batches from <raw>_<day>_reordered.npz
@@ -922,7 +967,7 @@ def main(argv=None):
     launch.check_world(args.world_size)
     if args.data_generation == "dataset" and args.day_file_loader == "device":
         train_ld.device = test_ld.device = dev
-        if rank == 0 and not args.mlperf_bin_loader:
+        if rank == 0 and type(train_ld).__name__ == "DeviceDayLoader":
             print("Day-file loader: device (windows of %d batches cut on the GPU, one window uploaded ahead)" % train_ld.window,
                   flush=True)
     from . import synth

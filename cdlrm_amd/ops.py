@@ -1079,6 +1079,37 @@ def dayfile_window(x_int: torch.Tensor, x_cat: torch.Tensor, y: torch.Tensor, ma
                                           X.data_ptr(), lS_i.data_ptr(), pitch, col0, T.data_ptr(), stream_ptr(stream)))
 
 
+def rows_tile() -> int:
+    """Samples per workgroup of `rows_window`'s kernel."""
+    return int(_lib.lib().cdlrm_rows_tile())
+
+
+def rows_window(x_int: torch.Tensor, x_cat: torch.Tensor, y: torch.Tensor, order: torch.Tensor, max_ind_range: int,
+                X: torch.Tensor, lS_i: torch.Tensor, T: torch.Tensor, col0: int = 0, stream=None) -> None:
+    """Rows order[0 .. n) of arrays that stay on the device (x_int int32 [n_rows, n_dense], x_cat int32 [n_rows, n_cat], y int32
+    [n_rows]; order int64 [n], every entry in [0, n_rows) -- not checked here, nor by the kernel) -> samples [col0, col0 + n) of a
+    window, with `dayfile_window`'s outputs and rules (include/cdlrm_hip.h: cdlrm_rows_window)."""
+    for t, name in ((x_int, "x_int"), (x_cat, "x_cat"), (y, "y"), (order, "order"), (X, "X"), (lS_i, "lS_i"), (T, "T")):
+        _require_cuda(t, name)
+    assert x_int.dtype == torch.int32 and x_cat.dtype == torch.int32 and y.dtype == torch.int32 and order.dtype == torch.int64
+    assert X.dtype == torch.float32 and T.dtype == torch.float32 and lS_i.dtype == torch.int64
+    assert x_int.dim() == 2 and x_cat.dim() == 2 and y.dim() == 1 and order.dim() == 1 and X.dim() == 2 and lS_i.dim() == 2
+    assert x_int.is_contiguous() and x_cat.is_contiguous() and y.is_contiguous() and order.is_contiguous()
+    assert X.is_contiguous() and T.is_contiguous()
+    n_rows, n, nd, nc = y.shape[0], order.shape[0], x_int.shape[1], x_cat.shape[1]
+    col0 = int(col0)
+    assert x_int.shape[0] == n_rows and x_cat.shape[0] == n_rows and n_rows >= 1
+    assert X.shape[1] == nd and lS_i.shape[0] == nc and nd >= 1 and nc >= 1
+    assert col0 >= 0 and col0 + n <= X.shape[0] and col0 + n <= T.numel() and col0 + n <= lS_i.shape[1], \
+        "samples [%d, %d) do not fit the window buffers" % (col0, col0 + n)
+    assert lS_i.stride(1) == 1 or lS_i.shape[1] == 1
+    pitch = lS_i.stride(0) if nc > 1 else lS_i.shape[1]
+    assert pitch >= lS_i.shape[1]
+    check(_lib.lib().cdlrm_rows_window(x_int.data_ptr(), x_cat.data_ptr(), y.data_ptr(), n_rows, order.data_ptr(), n, nd, nc,
+                                       int(max_ind_range), X.data_ptr(), lS_i.data_ptr(), pitch, col0, T.data_ptr(),
+                                       stream_ptr(stream)))
+
+
 def binfile_tile() -> int:
     """Samples per workgroup of `binfile_window`'s kernel."""
     return int(_lib.lib().cdlrm_binfile_tile())

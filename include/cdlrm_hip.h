@@ -792,6 +792,24 @@ int cdlrm_dayfile_window(const int32_t* x_int, const int32_t* x_cat, const int32
 /* samples per workgroup of cdlrm_dayfile_window (tests probe its edges; tools size their grids by it) */
 int cdlrm_dayfile_tile(void);
 
+/* ---- rows of the processed Criteo file, resident in HBM, cut by an order (data_loader_processed.DeviceProcessedLoader) ---
+ * Replaces, for the in-memory processed file of the reference's default dataset path (dlrm_data_pytorch.py:198-254: the whole
+ * X_int / X_cat / y re-listed row by row in the randomised order), its per-sample CriteoDataset.__getitem__ (:258-295, the
+ * `% max_ind_range`), the DataLoader's collate_wrapper_criteo (:323-338) and the trainer's per-step uploads of the result
+ * (main_no_ddp.py:388-391).  x_int int32 [n_rows, n_dense], x_cat int32 [n_rows, n_cat], y int32 [n_rows] are the file's
+ * arrays as they lie in HBM; sample i of the piece is row order[i], order int64 [n] on the device, 8-byte aligned, every entry
+ * in [0, n_rows) -- the caller's responsibility (the loader checks an order once on the host when it uploads it; the kernel
+ * does not look again).  Outputs and their meaning are cdlrm_dayfile_window's, word for word, for x_int[order[i], :],
+ * x_cat[order[i], :], y[order[i]]: the same log in double rounded once, the same floor-mod, T = (float)y, cells outside
+ * columns [col0, col0 + n) not written, n_cat <= 60; for the same rows the two entry points give the same bits.  Every row
+ * address is formed in 64 bits (row * 104 B passes 2^32 at 41.3 M rows).  A run of consecutive rows needs no order: it goes
+ * through cdlrm_dayfile_window on offset pointers.  Not a tape entry point: it never runs on the training queue. */
+int cdlrm_rows_window(const int32_t* x_int, const int32_t* x_cat, const int32_t* y, int64_t n_rows, const int64_t* order,
+                      int64_t n, int32_t n_dense, int32_t n_cat, int64_t max_ind_range, float* X, int64_t* lS_i,
+                      int64_t lS_i_pitch, int64_t col0, float* T, void* stream);
+/* samples per workgroup of cdlrm_rows_window */
+int cdlrm_rows_tile(void);
+
 /* ---- MLPerf binary Criteo records cut on the device (data_loader_terabyte.DeviceBinLoader) ------------------------------
  * Replaces, for n records of the binary file that lie in HBM as the file stores them (rec int32 [n, 1 + n_dense + n_cat],
  * a record = [y | n_dense | n_cat], data_loader_terabyte.py:238-275), CriteoBinDataset.__getitem__'s host transform
