@@ -189,6 +189,10 @@ PROTOTYPES = {
     "cdlrm_tape_replay": (C.c_int, [vp]),
     "cdlrm_tape_set_lanes": (C.c_int, [vp, vp, vp, c_i64]),
     "cdlrm_tape_selftest": (C.c_int, []),
+    "cdlrm_tape_set_float_cells": (C.c_int, [vp, c_i32]),
+    "cdlrm_tape_float_cells": (vp, [vp]),
+    "cdlrm_tape_add_fc": (C.c_int, [vp, vp, c_i32, vp, vp, c_i32, vp, vp]),
+    "cdlrm_tape_float_cells_selftest": (C.c_int, []),
     "cdlrm_event_record": (C.c_int, [vp, vp]),
     "cdlrm_stream_wait_event": (C.c_int, [vp, vp]),
     "cdlrm_event_attach_next": (C.c_int, [vp, vp]),
@@ -338,6 +342,8 @@ def native_tape_ok() -> bool:
 class NativeTape:
     """A recorded step as a C-side tape: `prog` is the engine's list of (function, arguments, is_library_call) with the
     per-step pointers already replaced by shared ctypes cells; replay() re-issues all of it with ONE library call.
+    `cells` may hold shared `c_float` objects beside the pointer cells (the learning rates under a schedule): a float argument
+    that IS one of them -- the object, never an equal value -- becomes a float cell of the C-side tape.
     Library calls are stored by address with their arguments split by register class (ctypes argtypes tell which);
     torch stream / event calls become cdlrm_stream_wait_event / cdlrm_event_record on the raw HIP handles."""
 
@@ -348,10 +354,13 @@ class NativeTape:
         the host the way their events order them on the GPU (cdlrm_tape_set_lanes)."""
         import torch
         L = raw()
-        order = list(cells.values())
+        order = [c for c in cells.values() if not isinstance(c, C.c_float)]
+        forder = [c for c in cells.values() if isinstance(c, C.c_float)]
         index = {id(c): i for i, c in enumerate(order)}
+        findex = {id(c): i for i, c in enumerate(forder)}
         self._cell_ids = set(index)
         self._cells_py = order
+        self._fcells_py = forder
         self._keep = []                          # torch events created for wait_stream: must outlive the tape
         h = L.cdlrm_tape_create(len(order))
         if not h:
@@ -359,9 +368,11 @@ class NativeTape:
         self._h = h
         ops = []
         try:
+            if forder:
+                check(L.cdlrm_tape_set_float_cells(h, len(forder)))
             for fn, args, _ in prog:
                 for target, cargs in self._translate(fn, args, torch):
-                    self._add(L, target, cargs, index)
+                    self._add(L, target, cargs, index, findex)
                     ops.append((target, cargs))
             self.lanes = 1
             if main_stream and max_lanes > 1:
@@ -372,6 +383,8 @@ class NativeTape:
             raise
         addr = L.cdlrm_tape_cells(h) if order else None     # (a tape without cells has no cell array)
         self._cells = (C.c_int64 * len(order)).from_address(addr) if addr else None
+        faddr = L.cdlrm_tape_float_cells(h) if forder else None
+        self._fcells = (C.c_float * len(forder)).from_address(faddr) if faddr else None
         self._replay = L.cdlrm_tape_replay
 
     def op_times(self):
@@ -468,14 +481,19 @@ class NativeTape:
             raise TapeUnsupported("an event that was never recorded has no HIP handle yet")
         return int(h)
 
-    def _add(self, L, fn, args, index):
+    def _add(self, L, fn, args, index, findex=None):
         types = fn.argtypes
         if len(types) != len(args):
             raise TapeUnsupported("argument count of %r" % fn)
-        ia, ci, fa = [], [], []
+        ia, ci, fa, fc = [], [], [], []
         for a, ty in zip(args, types):
             if ty is C.c_float:
-                fa.append(float(a))
+                if findex and isinstance(a, C.c_float) and id(a) in findex:
+                    fa.append(0.0)
+                    fc.append(findex[id(a)])
+                else:
+                    fa.append(a.value if isinstance(a, C.c_float) else float(a))
+                    fc.append(-1)
                 continue
             if ty is C.c_double:
                 raise TapeUnsupported("double argument")
@@ -498,7 +516,11 @@ class NativeTape:
         IA = (C.c_int64 * max(1, n))(*ia)
         CI = (C.c_int32 * max(1, n))(*ci)
         FA = (C.c_float * max(1, len(fa)))(*fa)
-        rc = L.cdlrm_tape_add(self._h, C.cast(fn, C.c_void_p), n, IA, CI, len(fa), FA)
+        if any(c >= 0 for c in fc):
+            FC = (C.c_int32 * len(fc))(*fc)
+            rc = L.cdlrm_tape_add_fc(self._h, C.cast(fn, C.c_void_p), n, IA, CI, len(fa), FA, FC)
+        else:
+            rc = L.cdlrm_tape_add(self._h, C.cast(fn, C.c_void_p), n, IA, CI, len(fa), FA)
         if rc:
             raise TapeUnsupported("%s: %s" % (getattr(fn, "__name__", fn), L.cdlrm_last_error().decode("utf-8", "replace")))
 
@@ -507,6 +529,10 @@ class NativeTape:
         cs = self._cells
         for i, c in enumerate(self._cells_py):
             cs[i] = c.value or 0
+        if self._fcells is not None:
+            fs = self._fcells
+            for i, c in enumerate(self._fcells_py):
+                fs[i] = c.value
         return self._replay(self._h)
 
     def __del__(self):

@@ -128,6 +128,8 @@ struct TapeOp {
     int64_t iargs[TAPE_MAX_INT];
     int32_t cell[TAPE_MAX_INT];     // -1: literal, else index of the cell whose value is the argument
     float fargs[TAPE_MAX_FLT];
+    int32_t fcell[TAPE_MAX_FLT];    // -1: literal, else index of the float cell whose value is the argument
+    bool has_fcell = false;         // any of them >= 0 (a tape without float cells calls with fargs as they are)
     int32_t lane = 0;       // 0: issued by the replaying thread, 1 .. 3: by that helper thread (cdlrm_tape_set_lanes)
     int32_t dep = -1;       // tape index of an op of ANOTHER lane that has to be issued before this one (-1: none)
     const char* name = "";
@@ -138,6 +140,7 @@ struct TapeOp {
 struct cdlrm_tape {
     std::vector<TapeOp> ops;
     std::vector<int64_t> cells;
+    std::vector<float> fcells;          // float cells (cdlrm_tape_set_float_cells): the learning rates of a scheduled run
     // multi-lane replay
     int lanes = 1;                      // lanes in use (1: single-threaded replay)
     int device = 0;
@@ -147,7 +150,12 @@ struct cdlrm_tape {
     char err[TAPE_MAX_LANES][256];
 };
 
-static inline int tape_call(const TapeOp& o, const int64_t* a) { return o.invoke(o.fn, a, o.fargs); }
+static inline int tape_call(const TapeOp& o, const int64_t* a, const float* fcells) {
+    if (!o.has_fcell) return o.invoke(o.fn, a, o.fargs);
+    float f[TAPE_MAX_FLT];
+    for (int i = 0; i < TAPE_MAX_FLT; ++i) f[i] = o.fcell[i] >= 0 ? fcells[o.fcell[i]] : o.fargs[i];
+    return o.invoke(o.fn, a, f);
+}
 
 extern "C" cdlrm_tape* cdlrm_tape_create(int32_t n_cells) {
     if (n_cells < 0 || n_cells > 64) { cdlrm_set_error("cdlrm_tape_create: 0..64 cells"); return nullptr; }
@@ -159,8 +167,21 @@ extern "C" cdlrm_tape* cdlrm_tape_create(int32_t n_cells) {
 
 extern "C" void cdlrm_tape_destroy(cdlrm_tape* t) { delete t; }
 
-extern "C" int cdlrm_tape_add(cdlrm_tape* t, void* fn, int32_t n_int, const int64_t* iargs, const int32_t* cell,
-                              int32_t n_flt, const float* fargs) {
+// float cells of a tape (0 .. 16), all 0.f: arguments that are floats AND change from step to step (the learning rates under a
+// schedule).  Call it before the ops that name them are added; the host writes cdlrm_tape_float_cells(t)[k] before a replay,
+// like the integer cells -- cdlrm_tape_replay reads them only after that, from every lane.
+extern "C" int cdlrm_tape_set_float_cells(cdlrm_tape* t, int32_t n) {
+    CDLRM_REQUIRE(t, "null tape");
+    CDLRM_REQUIRE(n >= 0 && n <= 16, "0..16 float cells");
+    for (const TapeOp& o : t->ops) CDLRM_REQUIRE(!o.has_fcell, "ops of this tape already name float cells");
+    t->fcells.assign((size_t)n, 0.f);
+    return 0;
+}
+
+extern "C" float* cdlrm_tape_float_cells(cdlrm_tape* t) { return (t && !t->fcells.empty()) ? t->fcells.data() : nullptr; }
+
+static int tape_add(cdlrm_tape* t, void* fn, int32_t n_int, const int64_t* iargs, const int32_t* cell, int32_t n_flt,
+                    const float* fargs, const int32_t* fcell) {
     CDLRM_REQUIRE(t && fn, "null argument");
     CDLRM_REQUIRE(n_int >= 0 && n_int <= TAPE_MAX_INT && n_flt >= 0 && n_flt <= TAPE_MAX_FLT, "too many arguments for a tape call");
     const TapeEntry* e = nullptr;
@@ -182,9 +203,26 @@ extern "C" int cdlrm_tape_add(cdlrm_tape* t, void* fn, int32_t n_int, const int6
         o.cell[i] = i < n_int ? cell[i] : -1;
         CDLRM_REQUIRE(o.cell[i] >= -1 && o.cell[i] < (int)t->cells.size(), "cell index outside the tape's cells");
     }
-    for (int i = 0; i < TAPE_MAX_FLT; ++i) o.fargs[i] = i < n_flt ? fargs[i] : 0.f;
+    for (int i = 0; i < TAPE_MAX_FLT; ++i) {
+        o.fargs[i] = i < n_flt ? fargs[i] : 0.f;
+        o.fcell[i] = (fcell && i < n_flt) ? fcell[i] : -1;
+        CDLRM_REQUIRE(o.fcell[i] >= -1 && o.fcell[i] < (int)t->fcells.size(), "float cell index outside the tape's float cells");
+        o.has_fcell = o.has_fcell || o.fcell[i] >= 0;
+    }
     t->ops.push_back(o);
     return 0;
+}
+
+extern "C" int cdlrm_tape_add(cdlrm_tape* t, void* fn, int32_t n_int, const int64_t* iargs, const int32_t* cell,
+                              int32_t n_flt, const float* fargs) {
+    return tape_add(t, fn, n_int, iargs, cell, n_flt, fargs, nullptr);
+}
+
+// cdlrm_tape_add with a float cell index per float argument (fcell[i] -1: the literal fargs[i])
+extern "C" int cdlrm_tape_add_fc(cdlrm_tape* t, void* fn, int32_t n_int, const int64_t* iargs, const int32_t* cell,
+                                 int32_t n_flt, const float* fargs, const int32_t* fcell) {
+    CDLRM_REQUIRE(fcell, "null argument");
+    return tape_add(t, fn, n_int, iargs, cell, n_flt, fargs, fcell);
 }
 
 extern "C" int64_t* cdlrm_tape_cells(cdlrm_tape* t) { return t ? t->cells.data() : nullptr; }
@@ -227,6 +265,7 @@ static inline int64_t tape_now_ns() {
 
 static int tape_run_lane(cdlrm_tape* t, int lane) {
     const int64_t* cells = t->cells.data();
+    const float* fcells = t->fcells.data();
     const int n = (int)t->ops.size();
     const bool timed = g_cdlrm_debug[3] != 0;
     int rc = 0;
@@ -241,7 +280,7 @@ static int tape_run_lane(cdlrm_tape* t, int lane) {
         const int64_t t1 = timed ? tape_now_ns() : 0;
         int64_t a[TAPE_MAX_INT];
         for (int i = 0; i < TAPE_MAX_INT; ++i) a[i] = o.cell[i] >= 0 ? cells[o.cell[i]] : o.iargs[i];
-        rc = tape_call(o, a);
+        rc = tape_call(o, a, fcells);
         if (timed) { const int64_t d = tape_now_ns() - t1; o.wait_ns += t1 - t0; o.call_ns += d; ++o.calls; if (d > o.max_ns) o.max_ns = d; }
         if (rc) break;
         t->done[lane].store(k, std::memory_order_release);
@@ -327,12 +366,13 @@ extern "C" int cdlrm_tape_replay(cdlrm_tape* t) {
     CDLRM_REQUIRE(t, "null tape");
     if (t->lanes <= 1) {
         const int64_t* cells = t->cells.data();
+        const float* fcells = t->fcells.data();
         const bool timed = g_cdlrm_debug[3] != 0;
         for (TapeOp& o : t->ops) {
             int64_t a[TAPE_MAX_INT];
             for (int i = 0; i < TAPE_MAX_INT; ++i) a[i] = o.cell[i] >= 0 ? cells[o.cell[i]] : o.iargs[i];
             const int64_t t0 = timed ? tape_now_ns() : 0;
-            const int rc = tape_call(o, a);
+            const int rc = tape_call(o, a, fcells);
             if (timed) { const int64_t d = tape_now_ns() - t0; o.call_ns += d; ++o.calls; if (d > o.max_ns) o.max_ns = d; }
             if (rc) return rc;
         }
@@ -484,6 +524,42 @@ extern "C" int cdlrm_tape_selftest(void) {
         const double wantf = 1.5 + 2.0 * -2.25 + 4.0 * 1024.0 + 8.0 * 0.125;
         if (!rc && (g_probe_sum != want || g_probe_fsum != wantf)) {
             cdlrm_set_error("cdlrm_tape_selftest: the typed call does not reach its arguments");
+            rc = CDLRM_EINVAL;
+        }
+    }
+    cdlrm_tape_destroy(t);
+    return rc;
+}
+
+// ... and of the float cells: ONE op with a float cell in two argument positions next to two literals, replayed with three
+// values (the learning rates of a scheduled run: patched per replay, everything else as recorded)
+extern "C" int cdlrm_tape_float_cells_selftest(void) {
+    cdlrm_tape* t = cdlrm_tape_create(1);
+    if (!t) return CDLRM_EINVAL;
+    const int64_t ia[10] = {3, -5, 0x7f00deadbeefLL, 0, 77, -(1LL << 40), 12345, 0x7e00cafe0000LL, -9, 1LL << 50};
+    const int32_t cell[10] = {-1, -1, -1, 0, -1, -1, -1, -1, -1, -1};
+    const float fa[4] = {1.5f, 99.f, 1024.f, -99.f};          // (the literals under a cell must never be read)
+    const int32_t fc[4] = {-1, 1, -1, 1};
+    const int32_t bad[4] = {-1, 2, -1, 1};
+    int rc = cdlrm_tape_set_float_cells(t, 2);
+    if (!rc && cdlrm_tape_add_fc(t, (void*)cdlrm_tape_probe, 10, ia, cell, 4, fa, bad) == 0) {
+        cdlrm_set_error("cdlrm_tape_float_cells_selftest: a float cell index outside the tape's was accepted");
+        rc = CDLRM_EINVAL;
+    }
+    if (!rc) rc = cdlrm_tape_add_fc(t, (void*)cdlrm_tape_probe, 10, ia, cell, 4, fa, fc);
+    if (!rc && (cdlrm_tape_length(t) != 1 || !cdlrm_tape_float_cells(t))) rc = CDLRM_EINVAL;
+    const float vals[3] = {0.25f, 0.1f * 0.64f, 3.0e-9f};
+    for (int k = 0; k < 3 && !rc; ++k) {
+        cdlrm_tape_cells(t)[0] = 1000 + k;
+        cdlrm_tape_float_cells(t)[0] = -7.f;                   // a cell no argument names
+        cdlrm_tape_float_cells(t)[1] = vals[k];
+        g_probe_sum = 0; g_probe_fsum = 0;
+        rc = cdlrm_tape_replay(t);
+        const int64_t want = ia[0] + 3 * ia[1] + 5 * ia[2] + 7 * (1000 + k) + 11 * ia[4] + 13 * ia[5] + 17 * ia[6] + 19 * ia[7] +
+                             23 * ia[8] + 29 * ia[9];
+        const double wantf = 1.5 + 2.0 * (double)vals[k] + 4.0 * 1024.0 + 8.0 * (double)vals[k];
+        if (!rc && (g_probe_sum != want || g_probe_fsum != wantf)) {
+            cdlrm_set_error("cdlrm_tape_float_cells_selftest: replay %d does not reach its float cells", k);
             rc = CDLRM_EINVAL;
         }
     }

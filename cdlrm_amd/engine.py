@@ -25,6 +25,7 @@ import math
 import os
 from typing import List, NamedTuple, Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -32,6 +33,7 @@ from . import _lib
 from . import _streams as S
 from . import ops
 from ._lib import record as rec
+from .lr_schedule import RateCell, effective_rate
 from .model_no_ddp import DLRM_Net, Embedding_Table_Cache_Group, Embedding_Table_Group, _linears
 
 
@@ -694,6 +696,7 @@ class StepPath(NamedTuple):
     matmul_precision: str
     lr: float
     lr_embeds: float
+    lr_cells: bool = False          # the rate arguments are the engine's two rate cells, not literals
     embed_optimizer: str = "sgd"    # the cache rows' update: "sgd" or "rowwise_adagrad" 
     adagrad_eps: float = 0.0
     dense_optimizer: str = "sgd"    # the MLP parameters' update: "sgd" or "adagrad" 
@@ -998,6 +1001,12 @@ class TrainEngine:
         self.ctx = cache_group.ctx
         self.dev = cache_group.weight.device
         self.lr, self.lr_embeds = float(lr), float(lr_embeds)
+        # A learning-rate schedule: lr / lr_embeds stay the BASE rates and part of the step's path; the factor
+        # is not.  Until a factor is first set every rate argument is the literal base rate; from then on (lr_cells) it is one of
+        # these two shared cells, which step() sets to the effective rates and a launch tape reads at every replay.
+        self.lr_cells = False
+        self._lr_factor = 1.0
+        self._lr_cell, self._lr_embeds_cell = RateCell(self.lr), RateCell(self.lr_embeds)
         self.world, self.rank = int(world_size), int(rank)
         self.multi = self.world > 1 or bool(force_collectives)      # the multi-rank control flow is on
         self.agg_freq, self.agg_op = int(table_agg_freq), table_agg_op
@@ -1248,19 +1257,48 @@ class TrainEngine:
         self.SW = {l: beside(W) for l, W in self.W.items()}
         self.Sb = {l: beside(l.bias.data) for l in self.W}
 
+    # ---- the learning-rate factor -----------------------------------------------------------------------------------------
+    def set_lr_factor(self, f: float):
+        """Scale both rates of the steps that follow by f (cdlrm_amd.lr_schedule): the rates handed to the library become
+        effective_rate(lr, f) and effective_rate(lr_embeds, f).  The first call switches the engine's rate arguments from
+        literals to cells for good -- one re-recording per control path --; no later call, whatever its value, changes a path."""
+        f = float(f)
+        if not (f >= 0.0 and f != float("inf")):
+            raise ValueError("lr factor %r: a finite number >= 0" % (f,))
+        self._lr_factor = f
+        self.lr_cells = True        # (step() writes the cells: lr / lr_embeds may still be assigned before it)
+
+    lr_factor = property(lambda self: self._lr_factor, set_lr_factor)
+
+    def effective_rates(self):
+        """(dense, embedding) rates of the next step as float32: the base rates without a factor."""
+        if not self.lr_cells:
+            return np.float32(self.lr), np.float32(self.lr_embeds)
+        return effective_rate(self.lr, self._lr_factor), effective_rate(self.lr_embeds, self._lr_factor)
+
+    def _set_rate_cells(self):
+        self._lr_cell.value, self._lr_embeds_cell.value = self.effective_rates()
+
+    def _rate(self, path: StepPath):
+        """The dense rate argument of this step's calls, in a tape or outside one."""
+        return self._lr_cell if path.lr_cells else self.lr
+
+    def _rate_embeds(self, path: StepPath):
+        return self._lr_embeds_cell if path.lr_cells else self.lr_embeds
+
     def _dense_step(self, path: StepPath):
         """The dense optimizer's step over the whole flat buffer, on the current stream."""
         if path.dense_optimizer == "sgd":
-            ops.sgd_step(self.param_flat, self.grad_flat, self.lr)
+            ops.sgd_step(self.param_flat, self.grad_flat, self._rate(path))
         else:
-            ops.dense_opt_step(self.param_flat, self.grad_flat, self.dense_state, self.lr, *self._dense_opt(path))
+            ops.dense_opt_step(self.param_flat, self.grad_flat, self.dense_state, self._rate(path), *self._dense_opt(path))
 
     def _dense_step2(self, path: StepPath, rng, **kw):
         """... over one sub-network's weights and biases (rng_bot / rng_top); kw: stream."""
         if path.dense_optimizer == "sgd":
-            ops.sgd_step2(self.param_flat, self.grad_flat, *rng, self.lr, **kw)
+            ops.sgd_step2(self.param_flat, self.grad_flat, *rng, self._rate(path), **kw)
         else:
-            ops.dense_opt_step2(self.param_flat, self.grad_flat, self.dense_state, *rng, self.lr, *self._dense_opt(path), **kw)
+            ops.dense_opt_step2(self.param_flat, self.grad_flat, self.dense_state, *rng, self._rate(path), *self._dense_opt(path), **kw)
 
     def _dense_opt(self, path: StepPath):
         """ops.mlp_wgrad's `opt` for this step."""
@@ -1452,7 +1490,7 @@ class TrainEngine:
             matmul_precision=self.matmul_precision, lr=self.lr, lr_embeds=self.lr_embeds,
             embed_optimizer=self.embed_optimizer, adagrad_eps=self.adagrad_eps if self.embed_optimizer != "sgd" else 0.0,
             dense_optimizer=self.dense_optimizer,
-            dense_adagrad_eps=self.dense_adagrad_eps if self.dense_optimizer != "sgd" else 0.0)
+            dense_adagrad_eps=self.dense_adagrad_eps if self.dense_optimizer != "sgd" else 0.0, lr_cells=bool(self.lr_cells))
 
     def _take(self, idx, res, phase: int, which, st):
         """A batch's (slots, miss_pos, miss_count) into the probe buffers `which`, misses into aux region `phase`, on stream st:
@@ -1749,6 +1787,8 @@ class TrainEngine:
                 # nothing orders this step behind that sort -- it sorts its own slots
                 self._cur_sorted = None
         main = S.current_stream(self.dev)
+        if self.lr_cells:
+            self._set_rate_cells()          # (lr / lr_embeds may have been assigned since the factor was set)
         path = self._step_path(X, lS_i, lS_o, next_idx)
         # the addresses-and-strides half of a tape's key: no decision, but baked into the recorded arguments
         pr = self._pending_resolve if self._mark_this else None
@@ -2010,7 +2050,7 @@ class TrainEngine:
             if not (attach and n_top - (1 if fused_head else 0) > 0):
                 rec(ev["top_dz"].record, main)
             rec(wst.wait_event, ev["top_dz"])
-            ops.mlp_wgrad(split[1], stream=wst, lr=self.lr if sgd_in_wgrad else None, **dopt)
+            ops.mlp_wgrad(split[1], stream=wst, lr=self._rate(path) if sgd_in_wgrad else None, **dopt)
             if not self.defer_top:
                 rec(ev["wgrad_done"].record, wst)
             elif not self.multi:
@@ -2023,7 +2063,7 @@ class TrainEngine:
             if attach:
                 ops.event_attach_next(ev["interacted"], main)      # completes with the interaction backward's launch
             if once:
-                ops.gather_interact_bwd_sgd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, sv.once, sv.stride, self.lr_embeds,
+                ops.gather_interact_bwd_sgd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, sv.once, sv.stride, self._rate_embeds(path),
                                             x_act=self.bot[-1][1])
             elif fused:
                 ops.gather_interact_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
@@ -2044,21 +2084,21 @@ class TrainEngine:
             qw = self._qr_work(n)
             ops.qr_cached_bwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, dfeat[:, 1:, :], dfeat.stride(0), D, qw,
                               stream=side)
-            ops.qr_cached_bwd_finish(ctx, self.qr_coll, n, qw, self.lr_embeds, self.Wr, stream=side)
+            ops.qr_cached_bwd_finish(ctx, self.qr_coll, n, qw, self._rate_embeds(path), self.Wr, stream=side)
         if path.embed_optimizer != "sgd":
             # the same plan, the Adagrad epilogue: S[tags[slot]] and the row, once per looked-up cache-proper slot
             opt = dict(opt=path.embed_optimizer, eps=path.adagrad_eps, state=self.emb_state, state_base=self.state_base, stream=side)
             if sv is not None:
-                ops.embbag_bwd_apply_sorted_opt(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work, sv.keys,
+                ops.embbag_bwd_apply_sorted_opt(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self._rate_embeds(path), emb_work, sv.keys,
                                                 sv.meta, sv.stride, self._phase, False, cg.touched if self.multi else None, **opt)
             else:
-                ops.embbag_bwd_apply_opt(ctx, n, lS_o, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work,
+                ops.embbag_bwd_apply_opt(ctx, n, lS_o, dfeat[:, 1:, :], dfeat.stride(0), D, self._rate_embeds(path), emb_work,
                                          cg.touched if self.multi else None, **opt)
         elif sv is not None:
-            ops.embbag_bwd_apply_sorted(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work, sv.keys, sv.meta, sv.stride,
+            ops.embbag_bwd_apply_sorted(ctx, n, dfeat[:, 1:, :], dfeat.stride(0), D, self._rate_embeds(path), emb_work, sv.keys, sv.meta, sv.stride,
                                         self._phase, once, cg.touched if self.multi else None, stream=side)
         else:
-            ops.embbag_bwd_apply(ctx, n, lS_o, dfeat[:, 1:, :], dfeat.stride(0), D, self.lr_embeds, emb_work,
+            ops.embbag_bwd_apply(ctx, n, lS_o, dfeat[:, 1:, :], dfeat.stride(0), D, self._rate_embeds(path), emb_work,
                                  cg.touched if self.multi else None, stream=side)
         emb_done = ev["emb_done"]
         rec(emb_done.record, side)
@@ -2082,7 +2122,7 @@ class TrainEngine:
             dY = dX
         if split is not None:
             split[0].set_x(0, X)
-            ops.mlp_wgrad(split[0], lr=self.lr if sgd_in_wgrad else None, **dopt)
+            ops.mlp_wgrad(split[0], lr=self._rate(path) if sgd_in_wgrad else None, **dopt)
             if not self.defer_top:
                 rec(main.wait_event, ev["wgrad_done"])
         else:
@@ -2197,6 +2237,10 @@ class TrainEngine:
             by_value = {c.value: c for c in cells.values()}
             if len(by_value) != len(cells):
                 return not self.multi      # aliased inputs: stay on the untaped path
+            if path.lr_cells:
+                # the rate cells are on the recording already (ops passes them through); named here for the native tape, which
+                # finds a float argument's cell by the object's identity
+                cells["lr"], cells["lr_embeds"] = self._lr_cell, self._lr_embeds_cell
             prog = []
             for fn, args in calls:
                 if getattr(fn, "argtypes", None) is not None:

@@ -150,7 +150,20 @@ def ProcessArgs(argv=None):
                         help="the MLP parameters' update: `sgd` = the reference's optim.SGD; `adagrad` = element-wise Adagrad, one "
                              "fp32 accumulator per parameter, stepped where the SGD step runs (DESIGN.md 4.6)")
     parser.add_argument("--dense-adagrad-eps", type=float, default=1e-10, help="--dense-optimizer=adagrad: std = sqrt(S) + eps")
+    # (the upstream DLRM's flag names; the definition is cdlrm_amd/lr_schedule.py's)
+    parser.add_argument("--lr-num-warmup-steps", type=int, default=0,
+                        help="both learning rates rise linearly over the first W optimizer steps: step s < W runs at s / W")
+    parser.add_argument("--lr-decay-start-step", type=int, default=0,
+                        help="with --lr-num-decay-steps: the first step of the polynomial decay (not inside the warm-up)")
+    parser.add_argument("--lr-num-decay-steps", type=int, default=0,
+                        help="N > 0: from --lr-decay-start-step on both rates fall as ((N - d) / N)^2 over N steps and stay at "
+                             "the last one's 1 / N^2")
     args = parser.parse_args(argv)
+    from . import lr_schedule
+    try:
+        lr_schedule.check(args.lr_num_warmup_steps, args.lr_decay_start_step, args.lr_num_decay_steps)
+    except ValueError as e:
+        sys.exit("ERROR: learning-rate schedule: %s" % e)
     from .engine import check_dense_optimizer
     try:
         check_dense_optimizer(args.dense_optimizer, args.dense_adagrad_eps)
@@ -489,6 +502,23 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         if ld.get("emb_state") is None:
             print("--load-model: %s holds no emb_state: the row-wise Adagrad accumulators start at zero" % args.load_model)
         eng.load_emb_state(ld.get("emb_state"))
+    # the learning-rate schedule (lr_schedule.py): one factor for both rates, a pure function of the optimizer step about to be
+    # taken -- every rank counts the same steps, nothing is communicated.  The counter runs across epochs and travels with
+    # --save-model / --load-model
+    from .lr_schedule import LRSchedule
+    sched = LRSchedule(getattr(args, "lr_num_warmup_steps", 0), getattr(args, "lr_decay_start_step", 0),
+                       getattr(args, "lr_num_decay_steps", 0))
+    lr_step = 0                 # optimizer steps taken so far
+    if sched.active:
+        if args.load_model:
+            if ld.get("lr_step") is None:
+                if rank == 0:
+                    print("--load-model: %s holds no lr_step: the learning-rate schedule starts at step 0" % args.load_model)
+            else:
+                lr_step = int(ld["lr_step"])
+        if rank == 0:
+            print("Learning-rate schedule: warm-up over %d steps, decay from step %d over %d steps (both rates)"
+                  % (sched.W, sched.S0, sched.N), flush=True)
     for kv in filter(None, os.environ.get("CDLRM_ENGINE_ATTR", "").split(",")):
         # development (as bench.py --engine-attr): TrainEngine schedule knobs for same-box A/B runs of the CLI, 'name=value,...'
         k_, v_ = kv.split("=")
@@ -663,6 +693,9 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                 nxt = rank_indices(window[0][2]) if window else None
                 carried_idx = nxt
             rs = resolver if (resolver is not None and Xr.shape[0] == resolver.width) else None
+            if sched.active:
+                eng.set_lr_factor(sched.factor(lr_step + 1))
+            lr_step += 1
             lossbuf = eng.step(Xr, Ir, Tr, lS_o=Or, j=j, next_idx=nxt,
                                res=rs.batch(wj) if rs is not None else None,
                                next_res=rs.batch(wj + 1) if (rs is not None and nxt is not None) else None,
@@ -690,6 +723,9 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                     avg_caching_overhead = np.mean(caching_overhead) / args.lookahead if caching_overhead else 0.0
                     print('Epoch {}: Finished {}/{} in {} ms/it. Caching overhead = {}. Loss = {}, Train Acc = {}'.format(
                         epoch, j, len(train_ld), gT, 1000 * avg_caching_overhead, gL, gA), flush=True)
+                    if sched.active:        # (an extra line behind the reference's: the rates of the step just taken)
+                        print('Learning rates at step {}: {} (MLPs), {} (embeddings)'.format(
+                            lr_step, *(str(x) for x in eng.effective_rates())), flush=True)   # (float32, shortest digits)
                 acc.zero_()
                 total_iter = total_samp = 0
                 caching_overhead = []
@@ -759,7 +795,7 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                            {"emb_r": [E.weight_r.data.clone() if hasattr(E, "weight_r") else None for E in emb_tables.emb_l]}),
                         **({} if eng.emb_state is None else {"emb_state": eng.emb_state_to_host()}),
                         **({} if eng.dense_state is None else {"dense_state": eng.dense_state_to_host()}),
-                        "ln_emb": [int(n) for n in ln_emb], "m_spa": int(m_spa)}, args.save_model)
+                        "lr_step": int(lr_step), "ln_emb": [int(n) for n in ln_emb], "m_spa": int(m_spa)}, args.save_model)
         if world > 1:
             dist.barrier()
     return eng

@@ -12,6 +12,7 @@ import torch
 from . import _lib
 from ._lib import Geometry, Plan, check, ptr, stream_ptr
 from ._lib import Victims as _VictimsStruct
+from .lr_schedule import rate_arg as _rate     # a learning rate: a number by value, or the engine's rate cell passed through
 
 
 def _require_cuda(t: torch.Tensor, name: str):
@@ -277,7 +278,7 @@ def qr_cached_bwd_finish(ctx: CacheCtx, collisions: torch.Tensor, n: int, work: 
                          gWr: Optional[torch.Tensor] = None, stream=None):
     """Wr -= lr * gWr, gWr = the partial sums of qr_cached_bwd in ascending order (optionally stored)."""
     assert Wr.dtype == torch.float32 and Wr.is_contiguous() and (gWr is None or (gWr.shape == Wr.shape and gWr.is_contiguous()))
-    check(_lib.lib().cdlrm_qr_cached_bwd_finish(ctx.handle, collisions.data_ptr(), int(Wr.shape[1]), n, work.data_ptr(), float(lr),
+    check(_lib.lib().cdlrm_qr_cached_bwd_finish(ctx.handle, collisions.data_ptr(), int(Wr.shape[1]), n, work.data_ptr(), _rate(lr),
                                                 Wr.data_ptr(), ptr(gWr), stream_ptr(stream)))
 
 
@@ -298,7 +299,7 @@ def embbag_bwd_sgd(ctx: CacheCtx, slots: torch.Tensor, offsets: Optional[torch.T
     nb = n if offsets is None else offsets.shape[1]
     check(_lib.lib().cdlrm_embbag_bwd_sgd(ctx.handle, slots.data_ptr(), ptr(offsets), n, nb,
                                           0 if offsets is None else offsets.stride(0), grad.data_ptr(), ld_bag,
-                                          ld_table, float(lr), work.data_ptr(), ptr(touched), stream_ptr(stream)))
+                                          ld_table, _rate(lr), work.data_ptr(), ptr(touched), stream_ptr(stream)))
 
 
 def embbag_bwd_prepare(ctx: CacheCtx, slots: torch.Tensor, work: torch.Tensor, stream=None):
@@ -310,7 +311,7 @@ def embbag_bwd_apply(ctx: CacheCtx, n: int, offsets: Optional[torch.Tensor], gra
                      ld_table: int, lr: float, work: torch.Tensor, touched: Optional[torch.Tensor] = None, stream=None):
     nb = n if offsets is None else offsets.shape[1]
     check(_lib.lib().cdlrm_embbag_bwd_apply(ctx.handle, ptr(offsets), n, nb, 0 if offsets is None else offsets.stride(0),
-                                            grad.data_ptr(), ld_bag, ld_table, float(lr), work.data_ptr(), ptr(touched),
+                                            grad.data_ptr(), ld_bag, ld_table, _rate(lr), work.data_ptr(), ptr(touched),
                                             stream_ptr(stream)))
 
 
@@ -319,7 +320,7 @@ def embbag_bwd_apply_rest(ctx: CacheCtx, n: int, offsets: Optional[torch.Tensor]
     """embbag_bwd_apply behind gather_interact_bwd_sgd: the once-only slots are done, the runs of >= 2 lookups are left."""
     nb = n if offsets is None else offsets.shape[1]
     check(_lib.lib().cdlrm_embbag_bwd_apply_rest(ctx.handle, ptr(offsets), n, nb, 0 if offsets is None else offsets.stride(0),
-                                                 grad.data_ptr(), ld_bag, ld_table, float(lr), work.data_ptr(), ptr(touched),
+                                                 grad.data_ptr(), ld_bag, ld_table, _rate(lr), work.data_ptr(), ptr(touched),
                                                  stream_ptr(stream)))
 
 
@@ -362,7 +363,7 @@ def embbag_bwd_apply_sorted(ctx: CacheCtx, n: int, grad: torch.Tensor, ld_bag: i
                             keys: int, meta: int, tstride: int, aux_phase: int, rest: bool,
                             touched: Optional[torch.Tensor] = None, stream=None):
     """embbag_bwd_apply / _apply_rest over a sorted chunk's lists (addresses from embbag_bwd_sorted_views)."""
-    check(_lib.lib().cdlrm_embbag_bwd_apply_sorted(ctx.handle, n, grad.data_ptr(), ld_bag, ld_table, float(lr), work.data_ptr(),
+    check(_lib.lib().cdlrm_embbag_bwd_apply_sorted(ctx.handle, n, grad.data_ptr(), ld_bag, ld_table, _rate(lr), work.data_ptr(),
                                                    keys, meta, tstride, int(aux_phase), int(bool(rest)), ptr(touched),
                                                    stream_ptr(stream)))
 
@@ -379,7 +380,7 @@ def embbag_bwd_apply_opt(ctx: CacheCtx, n: int, offsets: Optional[torch.Tensor],
     nb = n if offsets is None else offsets.shape[1]
     _check_emb_state(ctx, state, state_base)
     check(_lib.lib().cdlrm_embbag_bwd_apply_opt(ctx.handle, ptr(offsets), n, nb, 0 if offsets is None else offsets.stride(0),
-                                                grad.data_ptr(), ld_bag, ld_table, float(lr), work.data_ptr(), ptr(touched),
+                                                grad.data_ptr(), ld_bag, ld_table, _rate(lr), work.data_ptr(), ptr(touched),
                                                 EMB_OPTS[opt], float(eps), ptr(state), ptr(state_base), stream_ptr(stream)))
 
 
@@ -389,7 +390,7 @@ def embbag_bwd_apply_sorted_opt(ctx: CacheCtx, n: int, grad: torch.Tensor, ld_ba
                                 state: Optional[torch.Tensor] = None, state_base: Optional[torch.Tensor] = None, stream=None):
     """embbag_bwd_apply_sorted with an optimizer for the cache rows (embbag_bwd_apply_opt); rest=True takes "sgd" only."""
     _check_emb_state(ctx, state, state_base)
-    check(_lib.lib().cdlrm_embbag_bwd_apply_sorted_opt(ctx.handle, n, grad.data_ptr(), ld_bag, ld_table, float(lr), work.data_ptr(),
+    check(_lib.lib().cdlrm_embbag_bwd_apply_sorted_opt(ctx.handle, n, grad.data_ptr(), ld_bag, ld_table, _rate(lr), work.data_ptr(),
                                                        keys, meta, tstride, int(aux_phase), int(bool(rest)), ptr(touched),
                                                        EMB_OPTS[opt], float(eps), ptr(state), ptr(state_base),
                                                        stream_ptr(stream)))
@@ -683,7 +684,7 @@ def gather_interact_bwd_sgd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor,
     assert slots.dtype == torch.int32 and slots.stride(1) == 1 and x.stride(1) == 1 and dfeat.is_contiguous()
     check(_lib.lib().cdlrm_gather_interact_bwd_sgd(ctx.handle, slots.data_ptr(), slots.stride(0), x.data_ptr(), x.stride(0),
                                                    dR.data_ptr(), dR.stride(0), B, int(bool(itself)), int(x_act),
-                                                   dfeat.data_ptr(), int(once), int(ld_once), float(lr), stream_ptr(stream)))
+                                                   dfeat.data_ptr(), int(once), int(ld_once), _rate(lr), stream_ptr(stream)))
 
 
 IA_OPS = {"fwd": 0, "bwd": 1, "gather_fwd": 2, "gather_bwd": 3, "gather_bwd_sgd": 4}
@@ -881,7 +882,7 @@ def mlp_wgrad(plan: WgradPlan, stream=None, lr: Optional[float] = None, opt=None
         name, eps = opt
         adagrad = DENSE_OPTS[name] != 0
         check(_lib.lib().cdlrm_mlp_wgrad_opt_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
-                                                plan.P_b, float(lr), plan.M, plan.N, plan.K, flags, DENSE_OPTS[name], float(eps),
+                                                plan.P_b, _rate(lr), plan.M, plan.N, plan.K, flags, DENSE_OPTS[name], float(eps),
                                                 plan.S_w if adagrad else None, plan.S_b if adagrad else None,
                                                 plan.work.data_ptr(), stream_ptr(stream)))
     elif lr is None:
@@ -889,7 +890,7 @@ def mlp_wgrad(plan: WgradPlan, stream=None, lr: Optional[float] = None, opt=None
                                             plan.K, flags, plan.work.data_ptr(), stream_ptr(stream)))
     else:
         check(_lib.lib().cdlrm_mlp_wgrad_sgd_ex(plan.n, plan.X, plan.ld_x, plan.dZ, plan.ld_dz, plan.dW, plan.db, plan.P_w,
-                                                plan.P_b, float(lr), plan.M, plan.N, plan.K, flags, plan.work.data_ptr(),
+                                                plan.P_b, _rate(lr), plan.M, plan.N, plan.K, flags, plan.work.data_ptr(),
                                                 stream_ptr(stream)))
 
 
@@ -969,7 +970,7 @@ def act_bwd(dX: torch.Tensor, X: torch.Tensor, act: int, stream=None):
 def sgd_step2(param: torch.Tensor, grad: torch.Tensor, off0: int, n0: int, off1: int, n1: int, lr: float, stream=None):
     assert param.is_contiguous() and grad.is_contiguous() and param.numel() == grad.numel()
     assert 0 <= off0 and off0 + n0 <= param.numel() and 0 <= off1 and off1 + n1 <= param.numel()
-    check(_lib.lib().cdlrm_sgd_step2(param.data_ptr(), grad.data_ptr(), int(off0), int(n0), int(off1), int(n1), float(lr),
+    check(_lib.lib().cdlrm_sgd_step2(param.data_ptr(), grad.data_ptr(), int(off0), int(n0), int(off1), int(n1), _rate(lr),
                                      stream_ptr(stream)))
 
 
@@ -983,7 +984,7 @@ def dense_opt_step(param: torch.Tensor, grad: torch.Tensor, state: Optional[torc
                    stream=None):
     """sgd_step with the dense optimizer named (DENSE_OPTS): "adagrad" steps `state` (param's layout) and param."""
     _check_dense_state(param, grad, state, opt)
-    check(_lib.lib().cdlrm_dense_opt_step(param.data_ptr(), grad.data_ptr(), ptr(state), param.numel(), float(lr),
+    check(_lib.lib().cdlrm_dense_opt_step(param.data_ptr(), grad.data_ptr(), ptr(state), param.numel(), _rate(lr),
                                           DENSE_OPTS[opt], float(eps), stream_ptr(stream)))
 
 
@@ -993,7 +994,7 @@ def dense_opt_step2(param: torch.Tensor, grad: torch.Tensor, state: Optional[tor
     _check_dense_state(param, grad, state, opt)
     assert 0 <= off0 and off0 + n0 <= param.numel() and 0 <= off1 and off1 + n1 <= param.numel()
     check(_lib.lib().cdlrm_dense_opt_step2(param.data_ptr(), grad.data_ptr(), ptr(state), int(off0), int(n0), int(off1),
-                                           int(n1), float(lr), DENSE_OPTS[opt], float(eps), stream_ptr(stream)))
+                                           int(n1), _rate(lr), DENSE_OPTS[opt], float(eps), stream_ptr(stream)))
 
 
 def scale_div(x: torch.Tensor, divisor: float, stream=None):
@@ -1146,7 +1147,7 @@ def mark_rows(ctx: CacheCtx, slots: torch.Tensor, touched: torch.Tensor, stream=
 
 def sgd_step(param: torch.Tensor, grad: torch.Tensor, lr: float, stream=None):
     assert param.is_contiguous() and grad.is_contiguous() and param.numel() == grad.numel()
-    check(_lib.lib().cdlrm_sgd_step(param.data_ptr(), grad.data_ptr(), param.numel(), float(lr), stream_ptr(stream)))
+    check(_lib.lib().cdlrm_sgd_step(param.data_ptr(), grad.data_ptr(), param.numel(), _rate(lr), stream_ptr(stream)))
 
 
 def roc_auc(scores: torch.Tensor, targets: torch.Tensor) -> float:

@@ -855,6 +855,17 @@ int cdlrm_tape_replay(cdlrm_tape* t);      /* first non-zero return code of a re
  * n = cdlrm_tape_length. */
 int cdlrm_tape_set_lanes(cdlrm_tape* t, const int32_t* lane, const int32_t* dep, int64_t n);
 int cdlrm_tape_selftest(void);
+/* Float cells: float arguments that change from step to step -- the two learning rates under a schedule;
+ * every kernel still takes its rate by value.  cdlrm_tape_set_float_cells gives the tape n (0 .. 16) of them, before the ops
+ * that name them are added; cdlrm_tape_add_fc is cdlrm_tape_add with fcell[i] >= 0 taking fargs[i] from that float cell at
+ * replay time (-1: the literal); the host writes cdlrm_tape_float_cells(t)[k] (NULL: the tape has none) before
+ * cdlrm_tape_replay, which reads them only from then on, in every lane.  cdlrm_tape_float_cells_selftest(): one op with a
+ * float cell in two argument positions next to literals, replayed with three values (no GPU involved). */
+int cdlrm_tape_set_float_cells(cdlrm_tape* t, int32_t n);
+float* cdlrm_tape_float_cells(cdlrm_tape* t);
+int cdlrm_tape_add_fc(cdlrm_tape* t, void* fn, int32_t n_int, const int64_t* iargs, const int32_t* cell, int32_t n_flt,
+                      const float* fargs, const int32_t* fcell);
+int cdlrm_tape_float_cells_selftest(void);
 /* Self-test hooks (no GPU involved; used by cdlrm_tape_selftest and tests/test_host_logic.py): a call with interleaved
  * float / int32 / pointer / int64 parameters that adds its arguments up, and a logging call (spins `spin` iterations, then
  * appends `tag` to a process-wide log that cdlrm_tape_probe_log_take drains; returns the number of entries logged). */
