@@ -297,22 +297,31 @@ __global__ void __launch_bounds__(WIN_THREADS) k_assign(const TableDesc* __restr
         const int64_t set = mod_sets(v, P);
         const unsigned long long avail = ~prot[tab[t].set_base + set] & full;
         // probs = avail / avail.sum(-1)  (torch.distributions.Categorical), float32
-        const float p = 1.0f / (float)__popcll(avail);
-        float best = 0.f;
         int bw = 0;
-        for (int w = 0; w < ways; ++w) {
-            float qv;
-            if (q) {
-                qv = q[m * ways + w];
-            } else {
+        if (q) {
+            const float p = 1.0f / (float)__popcll(avail);
+            float best = 0.f;
+            for (int w = 0; w < ways; ++w) {
+                const float a = ((avail >> w) & 1ull) ? p : 0.0f;
+                const float val = a / q[m * ways + w];   // torch.multinomial: argmax(probs / q), first maximum
+                if (w == 0 || val > best) { best = val; bw = w; }
+            }
+        } else {
+            // Device draw: u_w = ((r[0] >> 8) + 1) * 2^-24 in (0, 1] from the Philox block at counter m * ways + w, and
+            // q_w = -log(u_w) ~ Exp(1).  p is one value over the available ways and -log falls strictly, so argmax(p / q)
+            // is the FIRST MAXIMUM OF u OVER THE AVAILABLE WAYS: the 24-bit integers are compared as they are.  (Through
+            // p / -__logf(u) the draw u = 1 gave q = -0 and p / q = -inf, 0 / q = NaN for a protected way: the winning
+            // draw could never win, and at way 0 NaN as the first `best` kept a protected way.)
+            uint32_t best = 0;
+            bool any = false;
+            for (int w = 0; w < ways; ++w) {
+                if (!((avail >> w) & 1ull)) continue;
                 uint32_t r[4];
                 const uint64_t ctr = (uint64_t)m * ways + w;
                 philox4x32((uint32_t)ctr, (uint32_t)(ctr >> 32), 0x43444c52u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-                qv = -__logf(((float)(r[0] >> 8) + 1.0f) * (1.0f / 16777216.0f));
+                const uint32_t x = r[0] >> 8;
+                if (!any || x > best) { best = x; bw = w; any = true; }
             }
-            const float a = ((avail >> w) & 1ull) ? p : 0.0f;
-            const float val = a / qv;                // torch.multinomial: argmax(probs / q), first maximum
-            if (w == 0 || val > best) { best = val; bw = w; }
         }
         way_out[m] = (uint8_t)bw;
         atomicMax(&winner[tab[t].row_base + P * bw + set], (int32_t)m);

@@ -302,8 +302,11 @@ int cdlrm_plan_offsets_sync(cdlrm_ctx* ctx, const cdlrm_plan* plan, int64_t* uni
 /* K3: way choice + contested-slot resolution (main_no_ddp.py:171-185, 203-204).
  *   q  device fp32 [M_total, ways] Exp(1) draws in claimant order (parity mode: drawn by the torch
  *      CPU generator exactly as Categorical.sample() does), or NULL: counter-based Philox keyed by
- *      `seed` on the device (perf mode, not bit-comparable with the reference).
- * way = argmax_w((avail_w / sum avail) / q_w), first maximum; the claimant latest in ascending-index
+ *      `seed` on the device (perf mode, not bit-comparable with the reference): claimant m draws, per
+ *      way w, x_w = r[0] >> 8 of the Philox4x32-10 block at counter (lo, hi)(m * ways + w), c2 =
+ *      0x43444c52, c3 = 0, key (lo, hi)(seed); u_w = (x_w + 1) * 2^-24, q_w = -log(u_w).
+ * way = argmax_w((avail_w / sum avail) / q_w), first maximum (q == NULL: the first maximum of x_w
+ * over the available ways, compared as integers); the claimant latest in ascending-index
  * order wins a contested (set, way).  Fills way / win_* . */
 int cdlrm_plan_assign(cdlrm_ctx* ctx, const cdlrm_plan* plan, const float* q, uint64_t seed,
                       void* stream);

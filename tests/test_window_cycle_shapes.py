@@ -110,20 +110,18 @@ WindowRef = namedtuple("WindowRef", "uniq q way kept_n win_idx victims victim_po
 Reference = namedtuple("Reference", "fx wins")
 
 
-@functools.lru_cache(maxsize=None)
-def reference(ci):
-    """Fixture + what the oracle leaves after each window.  Shared by every test of the case and never modified."""
-    fx = build_fixture(CASES[ci])
+def oracle_windows(fx, q_source_of, n_windows=N_WINDOWS):
+    """The oracle over the fixture's first n_windows windows, on copies; q_source_of(w) is window w's q source
+    (O.cache_embeddings calls it table by table).  One WindowRef per window."""
     case, T, ways = fx.case, fx.case.T, fx.case.ways
     host = [h.clone() for h in fx.host]
     occ = O.new_occupancy_tables(fx.cache_sizes, ways)
     weights = [fx.weight0[k][:ways * fx.cache_sizes[k]].clone() for k in range(T)]
-    gen = torch.Generator().manual_seed(1000 + case.seed)
     wins = []
-    for w in range(N_WINDOWS):
+    for w in range(n_windows):
         pre = [o.clone() for o in occ]
         rows, uniqs, _ = O.process_batch_slice([fx.windows[w][k] for k in range(T)], host, build_maps=False)
-        ev, det = O.cache_embeddings(rows, uniqs, occ, weights, fx.cache_sizes, lambda M, wy: O.draw_q(M, wy, gen))
+        ev, det = O.cache_embeddings(rows, uniqs, occ, weights, fx.cache_sizes, q_source_of(w))
         O.eviction_writeback(host, ev, average_on_writeback=(w == N_WINDOWS - 1))
         win_idx, victims, victim_pos, evd, delta = [], [], [], [], []
         counts = dict(hits=0, kept=0, contested=0, evictions=0, victims=0)
@@ -149,7 +147,15 @@ def reference(ci):
             counts["victims"] += int(vm.sum())
         wins.append(WindowRef(uniqs, [d["q"] for d in det], [d["way"] for d in det], [len(d["way"]) for d in det], win_idx,
                               victims, victim_pos, evd, [o.clone() for o in occ], [x.clone() for x in weights], delta, counts))
-    return Reference(fx, wins)
+    return wins
+
+
+@functools.lru_cache(maxsize=None)
+def reference(ci):
+    """Fixture + what the oracle leaves after each window.  Shared by every test of the case and never modified."""
+    fx = build_fixture(CASES[ci])
+    gen = torch.Generator().manual_seed(1000 + fx.case.seed)
+    return Reference(fx, oracle_windows(fx, lambda w: lambda M, wy: O.draw_q(M, wy, gen)))
 
 
 def host_after(ref, n_windows):
@@ -249,9 +255,10 @@ def _free_the_case_before_the_next():
             empty_host()
 
 
-def run_window(st, plan, ref, w, by_position=False, victims=()):
-    """One window on the device, with the oracle's q.  The unique lists and the claimant counts are asserted on the way
-    (the q tensor only fits when they are right).  Returns (uniq_off, kept_off, win_off)."""
+def run_window(st, plan, ref, w, by_position=False, victims=(), seed=None):
+    """One window on the device, with the oracle's q (seed given: with the device's own draw at that seed instead).  The
+    unique lists and the claimant counts are asserted on the way (the q tensor only fits when they are right).  Returns
+    (uniq_off, kept_off, win_off)."""
     ops, fx, wr = st.ops, ref.fx, ref.wins[w]
     T, D, ways = fx.case.T, fx.case.D, fx.case.ways
     plan.unique(fx.windows[w].to(DEV))
@@ -260,7 +267,10 @@ def run_window(st, plan, ref, w, by_position=False, victims=()):
     assert uo == np.cumsum([0] + [u.numel() for u in wr.uniq]).tolist(), w
     assert torch.equal(plan.uniq[:uo[T]].cpu(), torch.cat(wr.uniq)), w
     assert [ko[k + 1] - ko[k] for k in range(T)] == wr.kept_n, w
-    plan.assign(torch.cat([q.reshape(-1, ways) for q in wr.q]).contiguous().to(DEV))
+    if seed is None:
+        plan.assign(torch.cat([q.reshape(-1, ways) for q in wr.q]).contiguous().to(DEV))
+    else:
+        plan.assign(None, seed=seed)
     if by_position:
         rows = [ops.gather_rows(st.host_ptrs[k], plan.uniq[uo[k]:uo[k + 1]], D) for k in range(T)]
         for k in range(T):
@@ -289,35 +299,43 @@ def test_three_windows_equal_the_oracle(ops, ci, by_position):
     for bit, and the plan's scratch is clean.  Window 3 writes back with average=True: (h + v) / 2 is one correctly rounded
     fp32 addition and an exact halving on both sides."""
     ref = reference(ci)
-    fx, T, ways = ref.fx, ref.fx.case.T, ref.fx.case.ways
+    fx = ref.fx
     st = CycleState(ops, fx)
     plan = ops.WindowPlan(st.ctx, fx.case.n_win)
     exp_host = [h.clone() for h in fx.host]
     for w in range(N_WINDOWS):
-        wr = ref.wins[w]
-        uo, ko, wo = run_window(st, plan, ref, w, by_position)
-        way, tags, weight = plan.way[:ko[T]].cpu().long(), st.tags.cpu(), st.weight.cpu()
-        ev_tag, ev_rows = plan.ev_tag[:wo[T]].cpu(), plan.stage[:wo[T]].cpu()
-        c = st.ctx
-        for k in range(T):
-            assert wo[k + 1] - wo[k] == wr.win_idx[k].numel(), (w, k)
-            assert torch.equal(way[ko[k]:ko[k + 1]], wr.way[k]), (w, k)
-            assert torch.equal(tags[c.tag_base[k]:c.tag_base[k + 1]].view(-1, ways), wr.occ[k]), (w, k)
-            nslots = ways * fx.cache_sizes[k]
-            assert torch.equal(weight[c.row_base[k]:c.row_base[k] + nslots], wr.weight[k]), (w, k)
-            # the aux rows are not the window path's to touch
-            assert torch.equal(weight[c.row_base[k] + nslots:c.row_base[k + 1]], fx.weight0[k][nslots:]), (w, k)
-            et, er = ev_tag[wo[k]:wo[k + 1]], ev_rows[wo[k]:wo[k + 1]]
-            valid = et != -1
-            mi, mr = O.dedup_evictions(et[valid], er[valid])
-            assert torch.equal(mi, wr.ev[k][0]) and torch.equal(mr, wr.ev[k][1]), (w, k)
-            di, rows = wr.host_delta[k]
-            exp_host[k][di] = rows
-            assert torch.equal(st.host[k], exp_host[k]), (w, k)
-        assert torch.equal(plan.win_idx[:wo[T]].cpu(), torch.cat(wr.win_idx)), w
-        assert int((plan.winner != -1).sum()) == 0 and int(plan.prot.abs().sum()) == 0, w
-        assert int(plan.bitmap.abs().sum()) == 0, w
+        _, ko, wo = run_window(st, plan, ref, w, by_position)
+        assert_window_equals_oracle(st, plan, ref, w, ko, wo, exp_host)
     st.ctx.check()
+
+
+def assert_window_equals_oracle(st, plan, ref, w, ko, wo, exp_host):
+    """After run_window(w): ways, winners, tags, cache rows, the evicted (tag, row) set and the host tables equal the oracle's
+    window w bit for bit, the aux rows are untouched and the plan's scratch is clean.  exp_host (the oracle's host tables
+    before the window) moves on to the state after it."""
+    fx, wr = ref.fx, ref.wins[w]
+    T, ways = fx.case.T, fx.case.ways
+    way, tags, weight = plan.way[:ko[T]].cpu().long(), st.tags.cpu(), st.weight.cpu()
+    ev_tag, ev_rows = plan.ev_tag[:wo[T]].cpu(), plan.stage[:wo[T]].cpu()
+    c = st.ctx
+    for k in range(T):
+        assert wo[k + 1] - wo[k] == wr.win_idx[k].numel(), (w, k)
+        assert torch.equal(way[ko[k]:ko[k + 1]], wr.way[k]), (w, k)
+        assert torch.equal(tags[c.tag_base[k]:c.tag_base[k + 1]].view(-1, ways), wr.occ[k]), (w, k)
+        nslots = ways * fx.cache_sizes[k]
+        assert torch.equal(weight[c.row_base[k]:c.row_base[k] + nslots], wr.weight[k]), (w, k)
+        # the aux rows are not the window path's to touch
+        assert torch.equal(weight[c.row_base[k] + nslots:c.row_base[k + 1]], fx.weight0[k][nslots:]), (w, k)
+        et, er = ev_tag[wo[k]:wo[k + 1]], ev_rows[wo[k]:wo[k + 1]]
+        valid = et != -1
+        mi, mr = O.dedup_evictions(et[valid], er[valid])
+        assert torch.equal(mi, wr.ev[k][0]) and torch.equal(mr, wr.ev[k][1]), (w, k)
+        di, rows = wr.host_delta[k]
+        exp_host[k][di] = rows
+        assert torch.equal(st.host[k], exp_host[k]), (w, k)
+    assert torch.equal(plan.win_idx[:wo[T]].cpu(), torch.cat(wr.win_idx)), w
+    assert int((plan.winner != -1).sum()) == 0 and int(plan.prot.abs().sum()) == 0, w
+    assert int(plan.bitmap.abs().sum()) == 0, w
 
 
 # ---- 3. per-iteration path on the state window 2 left ---------------------------------------------------------------------
