@@ -176,6 +176,12 @@ PROTOTYPES = {
     "cdlrm_rows_tile": (C.c_int, []),
     "cdlrm_binfile_window": (C.c_int, [vp, c_i64, c_i32, c_i32, c_i64, vp, vp, c_i64, c_i64, vp, vp]),
     "cdlrm_binfile_tile": (C.c_int, []),
+    "cdlrm_etl_line_index_work_bytes": (c_i64, [c_i64]),
+    "cdlrm_etl_line_index": (C.c_int, [vp, c_i64, vp, c_i64, vp, vp, c_i64, vp]),
+    "cdlrm_etl_parse": (C.c_int, [vp, c_i64, vp, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp]),
+    "cdlrm_etl_subsample_work_bytes": (c_i64, [c_i64]),
+    "cdlrm_etl_subsample": (C.c_int, [vp, vp, vp, c_i64, vp, c_i64, c_i64, C.c_double, vp, vp, vp, c_i64, vp, vp, vp, c_i64, vp]),
+    "cdlrm_etl_encode": (C.c_int, [vp, c_i64, c_i32, c_i32, vp, vp, c_i64, c_i64, vp, vp]),
     "cdlrm_tape_create": (vp, [c_i32]),
     "cdlrm_tape_destroy": (None, [vp]),
     "cdlrm_tape_add": (C.c_int, [vp, vp, c_i32, vp, vp, c_i32, vp]),

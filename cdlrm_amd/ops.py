@@ -1139,6 +1139,102 @@ def binfile_window(rec: torch.Tensor, n_dense: int, max_ind_range: int, X: torch
                                           col0, T.data_ptr(), stream_ptr(stream)))
 
 
+# ---- raw Criteo text (cdlrm_amd/data_utils.py; include/cdlrm_hip.h: cdlrm_etl_*) -----------------------------------
+
+ETL_N_DENSE, ETL_N_CAT = 13, 26
+ETL_NO_ERROR = -1          # the error word as int64: all ones = no error
+ETL_CODES = {1: "not exactly 40 tab-separated fields", 2: "a decimal field holds a byte outside [0-9] (one leading - allowed)",
+             3: "a decimal field does not fit int32", 4: "a hex field holds a byte outside [0-9a-fA-F]",
+             5: "a hex field has more than 8 digits", 6: "a value is missing from its column's dictionary",
+             7: "a line span outside the text buffer"}
+
+
+def etl_error_word(device) -> torch.Tensor:
+    """A fresh device error word (int64 [1], all ones = no error) for the `etl_*` calls."""
+    return torch.full((1,), ETL_NO_ERROR, dtype=torch.int64, device=device)
+
+
+def etl_error(err: torch.Tensor):
+    """None, or (1-based line / row number, code) of the FIRST malformed line the word has seen (synchronises)."""
+    w = int(err.item())
+    if w == ETL_NO_ERROR:
+        return None
+    w &= (1 << 64) - 1
+    return w >> 8, w & 0xff
+
+
+def etl_line_index(text: torch.Tensor, length: int = None, starts: torch.Tensor = None, count: torch.Tensor = None, stream=None):
+    """text uint8 [>= length] on the device -> (starts int64 [cap + 1], count int64 [1]): starts[j] is the offset of line j,
+    starts[count] one past the last newline; count = the lines that END inside text[:length] (cdlrm_etl_line_index)."""
+    _require_cuda(text, "text")
+    assert text.dtype == torch.uint8 and text.dim() == 1 and text.is_contiguous()
+    n = text.numel() if length is None else int(length)
+    assert 0 <= n <= text.numel()
+    if starts is None:
+        starts = torch.empty(n + 1, dtype=torch.int64, device=text.device)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int64, device=text.device)
+    assert starts.dtype == torch.int64 and starts.is_contiguous() and starts.numel() >= 1 and count.dtype == torch.int64
+    L = _lib.lib()
+    work = torch.empty(int(L.cdlrm_etl_line_index_work_bytes(n)), dtype=torch.uint8, device=text.device)
+    check(L.cdlrm_etl_line_index(text.data_ptr(), n, starts.data_ptr(), starts.numel() - 1, count.data_ptr(), work.data_ptr(),
+                                 work.numel(), stream_ptr(stream)))
+    return starts, count
+
+
+def etl_parse(text: torch.Tensor, length: int, starts: torch.Tensor, n: int, line0: int, max_ind_range: int, y: torch.Tensor,
+              x_int: torch.Tensor, x_cat: torch.Tensor, err: torch.Tensor, row0: int = 0, stream=None) -> None:
+    """Lines [0, n) of `etl_line_index`'s starts -> rows [row0, row0 + n) of y [*], x_int [*, 13], x_cat [*, 26] (int32);
+    line0: the file's 0-based number of line 0 (cdlrm_etl_parse)."""
+    for t, name in ((text, "text"), (starts, "starts"), (y, "y"), (x_int, "x_int"), (x_cat, "x_cat"), (err, "err")):
+        _require_cuda(t, name)
+        assert t.is_contiguous(), name
+    assert text.dtype == torch.uint8 and starts.dtype == torch.int64 and err.dtype == torch.int64 and err.numel() == 1
+    assert y.dtype == x_int.dtype == x_cat.dtype == torch.int32
+    assert 0 <= length <= text.numel() and 0 <= n and starts.numel() >= n + 1
+    assert x_int.dim() == 2 and x_int.shape[1] == ETL_N_DENSE and x_cat.dim() == 2 and x_cat.shape[1] == ETL_N_CAT
+    assert row0 >= 0 and row0 + n <= min(y.numel(), x_int.shape[0], x_cat.shape[0]), "rows [%d, %d) do not fit" % (row0, row0 + n)
+    check(_lib.lib().cdlrm_etl_parse(text.data_ptr(), int(length), starts.data_ptr(), int(n), int(line0), int(max_ind_range),
+                                     y.data_ptr() + 4 * row0, x_int.data_ptr() + 4 * ETL_N_DENSE * row0,
+                                     x_cat.data_ptr() + 4 * ETL_N_CAT * row0, err.data_ptr(), stream_ptr(stream)))
+
+
+def etl_subsample(y: torch.Tensor, x_int: torch.Tensor, x_cat: torch.Tensor, n: int, rand_u: torch.Tensor, line0: int, rate: float,
+                  out_y: torch.Tensor, out_x_int: torch.Tensor, out_x_cat: torch.Tensor, rows_in: torch.Tensor,
+                  rows_out: torch.Tensor, stream=None) -> None:
+    """Rows [0, n) -> the kept ones, in order, behind row rows_in[0] of the out arrays; rows_out[0] = rows_in[0] + kept
+    (int64 [1] each, two different tensors).  Row i is dropped iff y[i] == 0 and rand_u[line0 + i] < rate (cdlrm_etl_subsample)."""
+    for t, name in ((y, "y"), (x_int, "x_int"), (x_cat, "x_cat"), (rand_u, "rand_u"), (out_y, "out_y"), (out_x_int, "out_x_int"),
+                    (out_x_cat, "out_x_cat"), (rows_in, "rows_in"), (rows_out, "rows_out")):
+        _require_cuda(t, name)
+        assert t.is_contiguous(), name
+    assert y.dtype == x_int.dtype == x_cat.dtype == out_y.dtype == out_x_int.dtype == out_x_cat.dtype == torch.int32
+    assert rand_u.dtype == torch.float64 and rows_in.dtype == rows_out.dtype == torch.int64
+    assert 0 <= n <= min(y.numel(), x_int.shape[0], x_cat.shape[0])
+    assert x_int.shape[1] == out_x_int.shape[1] == ETL_N_DENSE and x_cat.shape[1] == out_x_cat.shape[1] == ETL_N_CAT
+    out_cap = min(out_y.numel(), out_x_int.shape[0], out_x_cat.shape[0])
+    L = _lib.lib()
+    work = torch.empty(int(L.cdlrm_etl_subsample_work_bytes(n)), dtype=torch.uint8, device=y.device)
+    check(L.cdlrm_etl_subsample(y.data_ptr(), x_int.data_ptr(), x_cat.data_ptr(), int(n), rand_u.data_ptr(), rand_u.numel(),
+                                int(line0), float(rate), out_y.data_ptr(), out_x_int.data_ptr(), out_x_cat.data_ptr(), out_cap,
+                                rows_in.data_ptr(), rows_out.data_ptr(), work.data_ptr(), work.numel(), stream_ptr(stream)))
+
+
+def etl_encode(x_cat: torch.Tensor, col: int, keys: torch.Tensor, ids: torch.Tensor, err: torch.Tensor, n: int = None,
+               row0: int = 0, stream=None) -> None:
+    """Column `col` of x_cat int32 [*, n_cols], rows [0, n), in place: value -> ids[k] with keys[k] == value; keys int32
+    ascending, ids int32 beside them (cdlrm_etl_encode)."""
+    for t, name in ((x_cat, "x_cat"), (keys, "keys"), (ids, "ids"), (err, "err")):
+        _require_cuda(t, name)
+        assert t.is_contiguous(), name
+    assert x_cat.dtype == keys.dtype == ids.dtype == torch.int32 and err.dtype == torch.int64 and err.numel() == 1
+    assert x_cat.dim() == 2 and keys.dim() == 1 and keys.shape == ids.shape
+    n = x_cat.shape[0] if n is None else int(n)
+    assert 0 <= n <= x_cat.shape[0]
+    check(_lib.lib().cdlrm_etl_encode(x_cat.data_ptr(), n, x_cat.shape[1], int(col), keys.data_ptr(), ids.data_ptr(), keys.numel(),
+                                      int(row0), err.data_ptr(), stream_ptr(stream)))
+
+
 def mark_rows(ctx: CacheCtx, slots: torch.Tensor, touched: torch.Tensor, stream=None):
     assert slots.dtype == torch.int32 and slots.is_contiguous() and slots.shape[0] == ctx.T
     check(_lib.lib().cdlrm_mark_rows(ctx.handle, slots.data_ptr(), slots.shape[1], touched.data_ptr(),

@@ -827,6 +827,44 @@ int cdlrm_binfile_window(const int32_t* rec, int64_t n, int32_t n_dense, int32_t
 /* samples per workgroup of cdlrm_binfile_window */
 int cdlrm_binfile_tile(void);
 
+/* ---- raw Criteo text -> processed arrays (cdlrm_amd/data_utils.py: getCriteoAdData) ---------------------------------------
+ * The reference's ETL (data_utils.py:876-1121) reads the raw text line by line in Python (process_one_file, :966-1044),
+ * sub-samples (:976-993), builds one dictionary per categorical column (:1008-1009, :1080-1089) and rewrites every value as
+ * its id (processCriteoAdData, :111-169).  These entry points do the per-line work on a chunk of text in HBM; the grammar of
+ * a line, the two departures from the reference (int32 X_cat; a hash >= 2^31 keeps its bit pattern) and the error codes are
+ * csrc/etl_parse.h and DESIGN.md section 3.  None is a tape entry point; every launch is on the stream given.
+ *
+ * err: ONE 64-bit word on the device, set to all ones by the caller (= no error).  A malformed line, or a value missing from
+ * a dictionary, lowers it to (line << 8 | code) by an integer atomic minimum, line the 1-based number in the file (row for
+ * cdlrm_etl_encode): the host reads the FIRST bad line whatever the order the lanes ran in. */
+
+/* bytes of cdlrm_etl_line_index's work buffer for a chunk of len bytes */
+int64_t cdlrm_etl_line_index_work_bytes(int64_t len);
+/* text [len] (16-byte aligned) -> starts[0] = 0, starts[j + 1] = one past the j-th newline, for j < min(count, cap);
+ * *d_count = the number of newlines = of lines that END inside the chunk (data_utils.py:982: `for k, line in enumerate(f)`).
+ * Line j is text[starts[j], starts[j + 1] - 1); bytes behind starts[count] are no line (the host carries them in front of the
+ * next chunk); a chunk without a newline gives count 0.  starts holds cap + 1 entries. */
+int cdlrm_etl_line_index(const uint8_t* text, int64_t len, int64_t* starts, int64_t cap, int64_t* d_count, void* work,
+                         int64_t work_bytes, void* stream);
+/* lines [0, n) of the index -> y [n], x_int [n, 13] (negatives already 0, data_utils.py:150), x_cat [n, 26] int32, the hex
+ * value % max_ind_range first when max_ind_range > 0 (:984-1006).  line0: the 0-based number in its file of line 0 (for the
+ * error word).  A malformed line gives zeros and its code; a span outside text[0, len) is never read. */
+int cdlrm_etl_parse(const uint8_t* text, int64_t len, const int64_t* starts, int64_t n, int64_t line0, int64_t max_ind_range,
+                    int32_t* y, int32_t* x_int, int32_t* x_cat, void* err, void* stream);
+/* bytes of cdlrm_etl_subsample's work buffer for n rows */
+int64_t cdlrm_etl_subsample_work_bytes(int64_t n);
+/* data_utils.py:989-993: row i is dropped iff y[i] == 0 and rand_u[line0 + i] < rate (float64); the kept rows go, in order,
+ * to rows [*rows_in, *rows_in + kept) of the out arrays (out_cap rows) and *rows_out = *rows_in + kept -- two different
+ * device words, so consecutive chunks chain without a host read.  rate > 0: at rate 0 nothing is launched. */
+int cdlrm_etl_subsample(const int32_t* y, const int32_t* x_int, const int32_t* x_cat, int64_t n, const double* rand_u,
+                        int64_t n_rand, int64_t line0, double rate, int32_t* out_y, int32_t* out_x_int, int32_t* out_x_cat,
+                        int64_t out_cap, const int64_t* rows_in, int64_t* rows_out, void* work, int64_t work_bytes, void* stream);
+/* data_utils.py:144-147 (`X_cat_t[j, k] = convertDicts[j][x]`): x_cat[r, col] of a row-major [n, n_cols] array becomes
+ * ids[k] where keys[k] equals it; keys [m] ascending, m < 2^31, found in at most 32 halvings.  A value keys does not hold
+ * becomes 0 and sets err to (row0 + r + 1) << 8 | 6. */
+int cdlrm_etl_encode(int32_t* x_cat, int64_t n, int32_t n_cols, int32_t col, const int32_t* keys, const int32_t* ids, int64_t m,
+                     int64_t row0, void* err, void* stream);
+
 /* ---- launch tapes -------------------------------------------------------------------------------------------------
  * A training step's call sequence (this library's entry points + event records / stream waits), recorded once per control
  * path by the host and re-issued by ONE call per step (the reference issues the same ops from Python every iteration,
