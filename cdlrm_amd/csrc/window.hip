@@ -919,9 +919,9 @@ __global__ void __launch_bounds__(256) k_gather_rows(const float4* __restrict__ 
 
 extern "C" int cdlrm_gather_rows(const float* src, const int64_t* index, int64_t count, int32_t dim, float* out,
                                  void* stream) {
-    CDLRM_REQUIRE(src && index && out && dim % 4 == 0, "bad argument");
+    if (count == 0) return 0;                   // (an empty list's tensors have no address)
+    CDLRM_REQUIRE(src && index && out && dim % 4 == 0 && count > 0, "bad argument");
     CDLRM_REQUIRE((((uintptr_t)src | (uintptr_t)out) & 15) == 0, "16-byte aligned rows");
-    if (count == 0) return 0;
     int64_t gx = cdiv(count * (dim / 4), 256);
     if (gx > 4096) gx = 4096;
     hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream,
@@ -1128,9 +1128,9 @@ __global__ void __launch_bounds__(256) k_scatter_rows(float4* __restrict__ dst, 
 
 extern "C" int cdlrm_scatter_rows(float* dst, const int64_t* index, const float* rows, int64_t count, int32_t dim,
                                   int average, void* stream) {
-    CDLRM_REQUIRE(dst && index && rows && dim % 4 == 0, "bad argument");
-    CDLRM_REQUIRE((((uintptr_t)dst | (uintptr_t)rows) & 15) == 0, "16-byte aligned rows");
     if (count == 0) return 0;
+    CDLRM_REQUIRE(dst && index && rows && dim % 4 == 0 && count > 0, "bad argument");
+    CDLRM_REQUIRE((((uintptr_t)dst | (uintptr_t)rows) & 15) == 0, "16-byte aligned rows");
     int64_t gx = cdiv(count * (dim / 4), 256);
     if (gx > 4096) gx = 4096;
     hipLaunchKernelGGL(k_scatter_rows, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream,
@@ -1157,9 +1157,9 @@ __global__ void __launch_bounds__(256) k_blend_rows(const float4* __restrict__ d
 
 extern "C" int cdlrm_blend_rows(const float* dst, const int64_t* index, const float* rows, int64_t count, int32_t dim,
                                 float* out, void* stream) {
-    CDLRM_REQUIRE(dst && index && rows && out && dim % 4 == 0, "bad argument");
-    CDLRM_REQUIRE((((uintptr_t)dst | (uintptr_t)rows | (uintptr_t)out) & 15) == 0, "16-byte aligned rows");
     if (count == 0) return 0;
+    CDLRM_REQUIRE(dst && index && rows && out && dim % 4 == 0 && count > 0, "bad argument");
+    CDLRM_REQUIRE((((uintptr_t)dst | (uintptr_t)rows | (uintptr_t)out) & 15) == 0, "16-byte aligned rows");
     int64_t gx = cdiv(count * (dim / 4), 256);
     if (gx > 4096) gx = 4096;
     hipLaunchKernelGGL(k_blend_rows, dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream,
