@@ -965,6 +965,296 @@ class WindowResolver:
         return out
 
 
+# ---- the touched-row merge in deadline order -----------------------------------------------------------------------------
+# broadcast_and_aggregate (main_no_ddp.py:250-292) replaces every row any rank touched since the last merge by its mean
+# (max, sum) over the ranks, at step j, before step j + 1 runs.  What step j + 1 can observe of that is the rows IT uses;
+# a row nobody uses before step j + d may be merged any time before step j + d -- it does not change in between on any
+# rank.  The window's resolved slot ids (WindowResolver.lookahead: every rank's lookups of the next batches) say which
+# rows the next K steps use: the merge's row list is sorted by the first batch that needs a row (classes: batch 1, 2, 3-4,
+# 5-8, 9-16, 17-32, 33-64, later = "cold", due at batch K + 1) and exchanged in that order on the exchange stream -- gather, all-
+# reduce, scatter per chunk -- a few chunks per step, while the training steps run; a step waits for the chunk that holds
+# the last row it needs.  At c3 (100 steps x 8192 lookups x 26 tables, Zipf 1.05: 1.86 M rows, 0.95 GB) the next batch
+# needs 2.3 % of the merge's rows, the next 16 batches 13 %.  Same values as the merge in one piece: every rank builds the
+# same list from the same flags and the same window, and a row's gather reads what the one-piece merge would have read.
+#
+# Every rank has to cut the exchange into the same pieces in the same order (a mismatch is a hang, not a failed assert): the
+# arithmetic that decides the pieces is MergeSchedule + merge_pieces, no torch and no streams (tests/test_merge_schedule_host.py);
+# MergePump holds the buffers and the in-flight state and issues what the schedule says.
+MERGE_CLASS_FIRST = (1, 2, 3, 5, 9, 17, 33)     # first batch (after the merge step) of each deadline class; then: cold
+MERGE_LOOKAHEAD = 64                            # batches ahead the classes reach (the resolver decides how many are known)
+
+
+class MergeSchedule(NamedTuple):
+    """One merge's deadlines.  off: the class offsets into the merge's row list (cdlrm_agg_split: len(MERGE_CLASS_FIRST) + 2
+    entries, rows of class c at [off[c], off[c + 1]), the cold class last); K: how many batches ahead were known; U: rows in
+    the merge; budget: rows issued per step beyond what the next step needs."""
+    off: tuple
+    K: int
+    U: int
+    budget: int
+
+    def need(self, d: int) -> int:
+        """Rows that have to have landed before the d-th step after the merge."""
+        if d > self.K:
+            return self.U
+        need = 0
+        for c, f in enumerate(MERGE_CLASS_FIRST):
+            if f <= d:
+                need = self.off[c + 1]
+        return need
+
+    def target(self, d_next: int, issued: int, everything: bool = False) -> int:
+        """Rows to have issued once a step is done: what the NEXT step (the d_next-th after the merge) needs, plus the budget."""
+        return self.U if everything else max(self.need(d_next), min(self.U, issued + self.budget))
+
+
+def merge_pieces(issued: int, target: int, chunk: int):
+    """The (lo, hi) cuts that take a merge from `issued` rows to `target`, at most `chunk` rows each."""
+    ch, cuts = max(1, int(chunk)), []
+    while issued < target:
+        cuts.append((issued, min(target, issued + ch)))
+        issued = cuts[-1][1]
+    return cuts
+
+
+class MergePump:
+    """The touched-row merge of a multi-rank engine (TrainEngine.merge): its buffers -- allocated at the first merge, grown by
+    doubling, none in a steady-state merge -- and the one merge that may be on its way across steps.  Everything here is
+    COLLECTIVE: every rank makes the same calls at the same steps."""
+
+    def __init__(self, engine: "TrainEngine"):
+        self.eng = engine
+        self.list_rows = None       # the union's sorted row list; with it: count, count_host, flags, counted, xbuf, tier
+        self._clear()
+
+    def _clear(self):
+        self.sched = None           # MergeSchedule of the merge in flight
+        self.rows = self.buf = self.rop = self.ready = self.rs = None
+        self.scale = 1.0
+        self.j0 = self.step0 = 0    # the merge step's batch in its window (rs), and its engine iteration
+        self.issued = self.waited = 0
+        self.chunks = []            # (hi, event) per piece issued
+
+    @property
+    def pending(self) -> bool:
+        return self.sched is not None
+
+    def _alloc(self):
+        if self.list_rows is None:
+            dev, n = self.eng.dev, self.eng.ctx.total_rows
+            self.list_rows = torch.empty(n, dtype=torch.int64, device=dev)
+            self.count = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.count_host = S.pinned(torch.zeros(1, dtype=torch.int64), dev)
+            self.flags = torch.zeros(n, dtype=torch.uint8, device=dev)
+            self.counted = S.new_event(dev)
+            self.xbuf = self.tier = None
+
+    def _list(self, flags) -> int:
+        """flags -> sorted row list (device) and its length on the host.  The host waits for THIS copy only (an event
+        behind the compaction), not for the stream: kernels queued behind it keep the GPU busy meanwhile."""
+        ops.agg_compact(self.eng.ctx, flags, self.list_rows, self.count)
+        self.count_host.copy_(self.count, non_blocking=True)
+        self.counted.record(S.current_stream(self.eng.dev))
+        self.counted.synchronize()
+        return int(self.count_host[0])
+
+    def _buffer(self, U: int) -> torch.Tensor:
+        """[>= U, D] exchange buffer, kept between merges (grown by doubling: no allocation in a steady-state merge)."""
+        if self.xbuf is None or self.xbuf.shape[0] < U:
+            cap = 1 << max(12, (U - 1).bit_length())
+            self.xbuf = torch.empty(min(cap, self.eng.ctx.total_rows), self.eng.D, dtype=torch.float32, device=self.eng.dev)
+        return self.xbuf[:U]
+
+    def sync_to_rank0(self):
+        """The reference refills rank 0's cache and then broadcasts EVERY cache table from rank 0
+        (main_no_ddp.py:318-319), which also overwrites whatever the other ranks changed since the last
+        table-agg merge.  Same result without moving 10.9 GB: only the rows some rank touched since that merge can
+        differ, so broadcast exactly those (union of the touched flags), leaving the flags set for the next merge."""
+        eng = self.eng
+        self.drain()                # the refill that follows reads and evicts cache rows: the last merge lands first
+        self._alloc()
+        self.flags.copy_(eng.cg.touched)
+        dist.all_reduce(self.flags, op=dist.ReduceOp.MAX, group=eng.pg)
+        U = self._list(self.flags)
+        if U == 0:
+            return
+        buf = self._buffer(U)
+        ops.agg_gather(eng.ctx, self.list_rows, self.count, 1.0, buf, U)
+        dist.broadcast(buf, src=0, group=eng.pg)
+        ops.agg_scatter(eng.ctx, self.list_rows, self.count, buf, U)
+
+    def aggregate(self, pos, it: int):
+        """The merge of engine iteration `it`, whose batch is pos = (resolver, batch number) of its window (None: unknown).
+        Slot ids are global, so the union of touched rows is an all-reduce(MAX) of the flag bytes (the reference all-gathers
+        the slot lists and takes torch.unique per table); the rows then travel as ONE compacted [U, D] buffer: in deadline
+        order over the next steps (lazy_merge, _start), or at once, in chunks -- while chunk i is reduced over xGMI on the
+        exchange stream, chunk i+1 is gathered and chunk i-1 scattered back on the main stream.  The host waits only for
+        the row count (and the class offsets)."""
+        eng = self.eng
+        ctx, main, comm = eng.ctx, S.current_stream(eng.dev), eng.comm
+        touched = eng.cg.touched
+        dist.all_reduce(touched, op=dist.ReduceOp.MAX, group=eng.pg)
+        self._alloc()
+        U = self._list(touched)                       # consumes (clears) the flags
+        if U == 0:
+            return
+        buf = self._buffer(U)
+        if eng.agg_op == "mean":
+            scale, rop = float(eng.world), dist.ReduceOp.SUM
+        elif eng.agg_op == "sum":
+            scale, rop = 1.0, dist.ReduceOp.SUM
+        elif eng.agg_op == "max":
+            scale, rop = 1.0, dist.ReduceOp.MAX
+        else:
+            raise ValueError(eng.agg_op)
+        if eng.lazy_merge and self._start(pos, it, U, buf, scale, rop):
+            return
+        rows, count, ch = self.list_rows, self.count, eng.agg_chunk_rows
+        nch = (U + ch - 1) // ch
+        if nch == 1 or not S.is_hip(eng.dev):
+            ops.agg_gather(ctx, rows, count, scale, buf, U)
+            dist.all_reduce(buf, op=rop, group=eng.pg)
+            ops.agg_scatter(ctx, rows, count, buf, U)
+            return
+        gathered = [S.new_event(eng.dev) for _ in range(nch)]
+        reduced = [S.new_event(eng.dev) for _ in range(nch)]
+
+        def gather(i):
+            lo, hi = i * ch, min(U, (i + 1) * ch)
+            ops.agg_gather(ctx, rows[lo:], count, scale, buf[lo:hi], hi - lo, first=lo)
+            gathered[i].record(main)
+
+        def reduce(i):
+            lo, hi = i * ch, min(U, (i + 1) * ch)
+            with S.on_stream(comm):
+                comm.wait_event(gathered[i])
+                dist.all_reduce(buf[lo:hi], op=rop, group=eng.pg)
+                reduced[i].record(comm)
+
+        def scatter(i):
+            lo, hi = i * ch, min(U, (i + 1) * ch)
+            main.wait_event(reduced[i])
+            ops.agg_scatter(ctx, rows[lo:], count, buf[lo:hi], hi - lo, first=lo)
+
+        gather(0)
+        for i in range(nch):
+            reduce(i)
+            if i + 1 < nch:
+                gather(i + 1)
+            if i >= 1:
+                scatter(i - 1)
+        scatter(nch - 1)
+
+    def _start(self, pos, it, U, buf, scale, rop) -> bool:
+        """Sort the merge's rows by their deadline and begin the exchange; False: nothing known about the next batches."""
+        if pos is None:
+            return False
+        rs, j = pos
+        la = rs.lookahead(j, MERGE_LOOKAHEAD)
+        if not la:
+            return False            # nothing known about the next batch (end of the window): the merge in one piece
+        eng = self.eng
+        ctx, main = eng.ctx, S.current_stream(eng.dev)
+        first = MERGE_CLASS_FIRST
+        C = len(first) + 1
+        K = la[-1][0]
+        if self.tier is None:
+            self.tier = (torch.empty(ctx.total_rows, dtype=torch.uint8, device=eng.dev),
+                         torch.empty(ctx.total_rows, dtype=torch.int64, device=eng.dev),
+                         torch.zeros(C + 1, dtype=torch.int64, device=eng.dev),
+                         S.pinned(torch.zeros(C + 1, dtype=torch.int64), eng.dev))
+        tier, rows_sorted, off_dev, off_host = self.tier
+        tier.fill_(C - 1)
+        seen = set()
+        for k, ws, ev in la:
+            if id(ev) not in seen:
+                main.wait_event(ev)
+                seen.add(id(ev))
+        for c in reversed(range(C - 1)):        # latest deadline first: the earliest class that names a row wins
+            hi = first[c + 1] if c + 1 < len(first) else MERGE_LOOKAHEAD + 1
+            for k, ws, ev in la:
+                if first[c] <= k < hi:
+                    ops.agg_mark_tier(ctx, ws, c, tier)
+        ops.agg_split(ctx, self.list_rows, U, tier, C, rows_sorted, off_dev)
+        eng._events["tier_marked"].record(main)
+        off_host.copy_(off_dev, non_blocking=True)
+        self.counted.record(main)
+        self.counted.synchronize()
+        ready = S.new_event(eng.dev)
+        ready.record(main)
+        # (the budget cuts the exchange into pieces: it has to be the same number on every rank -- the resolver's lbs =
+        #  ceil(B / world), not this rank's slice width, which is shorter on the last rank when world does not divide B)
+        budget = int(eng.merge_budget_rows)
+        if eng.merge_budget_auto:
+            budget = max(budget, int(rs.lbs) * eng.T)
+        sched = MergeSchedule(tuple(int(x) for x in off_host.tolist()), K, U, budget)
+        self.start(sched, rows_sorted, buf, scale, rop, ready, rs, j, it)
+        return True
+
+    def start(self, sched: MergeSchedule, rows, buf, scale, rop, ready, rs, j0: int, it: int):
+        """A merge is on its way from here: rows [U] in deadline order, buf [U, D]; `ready`: rows and buf may be read."""
+        self._clear()
+        self.sched, self.rows, self.buf, self.scale, self.rop, self.ready = sched, rows, buf, scale, rop, ready
+        self.rs, self.j0, self.step0 = rs, j0, it
+        self.after_step(it)
+
+    def issue(self, lo: int, hi: int):
+        """Rows [lo, hi) of the merge in flight on the exchange stream; returns the event behind their scatter."""
+        eng, comm = self.eng, self.eng.comm
+        with S.on_stream(comm):
+            if not self.chunks:
+                comm.wait_event(self.ready)
+            ops.agg_gather(eng.ctx, self.rows[lo:], self.count, self.scale, self.buf[lo:hi], hi - lo, first=lo)
+            dist.all_reduce(self.buf[lo:hi], op=self.rop, group=eng.pg)
+            ops.agg_scatter(eng.ctx, self.rows[lo:], self.count, self.buf[lo:hi], hi - lo, first=lo)
+            ev = S.new_event(eng.dev)
+            ev.record(comm)
+        return ev
+
+    def before_step(self, pos, it: int):
+        """In front of engine iteration `it`, whose batch is `pos`: the rows of a pending merge that this step uses have landed.
+        The deadlines were computed for the batches FOLLOWING the merge step in its window: a step that is not the expected
+        next batch of that window (another resolver, a jump) gets the whole merge first."""
+        if self.sched is None:
+            return
+        if pos is None or pos[0] is not self.rs or pos[1] != self.j0 + (it - self.step0):
+            self.drain()
+        else:
+            self.wait(it)
+
+    def after_step(self, it: int, everything: bool = False):
+        """Issue the pieces the NEXT step needs, plus the budget's share of the rest (everything: all of it)."""
+        s = self.sched
+        if s is None:
+            return
+        target = s.target(it + 1 - self.step0, self.issued, everything)
+        for lo, hi in merge_pieces(self.issued, target, self.eng.agg_chunk_rows):
+            self.chunks.append((hi, self.issue(lo, hi)))
+            self.issued = hi
+
+    def wait(self, it: int, everything: bool = False):
+        """The training (and the side) stream wait for the piece that holds the last row iteration `it` needs."""
+        s, eng = self.sched, self.eng
+        need = s.U if everything else s.need(it - self.step0)
+        if need > self.waited:
+            assert self.issued >= need, "merge rows this step needs were never issued"
+            for hi, ev in self.chunks:
+                if hi >= need:
+                    S.current_stream(eng.dev).wait_event(ev)
+                    eng.side.wait_event(ev)
+                    self.waited = hi
+                    break
+        if self.waited >= s.U:
+            self._clear()
+
+    def drain(self):
+        """Land every row of the merge in flight (nothing to do without one)."""
+        if self.sched is not None:
+            self.after_step(self.step0, everything=True)
+            self.wait(self.step0, everything=True)
+            self._clear()
+
+
 class TrainEngine:
     def __init__(self, cache_group: Embedding_Table_Cache_Group, dlrm: DLRM_Net, host_tables: Embedding_Table_Group,
                  *, lr: float, lr_embeds: float, world_size: int = 1, rank: int = 0, table_agg_freq: int = 1,
@@ -1050,20 +1340,19 @@ class TrainEngine:
         self.comm = S.new_stream(self.dev) if self.multi else None
         self.side = S.new_stream(self.dev)
         self.pref = S.new_stream(self.dev)          # next batch's tag probe + aux-row fill
-        self.agg_rows = None
         # rows per chunk of the touched-row merge (32 MB at D = 128: large enough for xGMI bandwidth, small enough that
         # the gather of chunk i+1 hides under the reduction of chunk i)
         self.agg_chunk_rows = 1 << 16
         # The merge of step j is due, row by row, before the first later step that USES the row (on any rank) -- the look-ahead
         # window knows those steps --, so only the rows the very next batch needs are exchanged at step j; the others follow in
-        # deadline order over the next steps, `merge_budget_rows` per step beyond what the next step needs (MergePump below).
+        # deadline order over the next steps, `merge_budget_rows` per step beyond what the next step needs (MergePump).
         self.lazy_merge = True
         # per step, beyond what the next step needs: max(this, the rank's lookups per step) rows -- 32 MB at c3's per-rank batch,
         # 109 MB at c5's: about one step's length of xGMI time at ring rates, so that the next step's gradient exchange (same
         # communicator stream) finds the stream free; a c3 merge drains in ~29 steps, a c5 merge in ~41 (look-ahead: 34-65)
         self.merge_budget_rows = 1 << 16
         self.merge_budget_auto = True           # (tests switch the per-step-lookups floor off to keep rows on their way)
-        self._pump = None
+        self.merge = MergePump(self) if self.multi else None
         self._pref = None
         self._phase = 0                             # aux region of the batch being trained
         self._emb_done = None
@@ -1404,7 +1693,7 @@ class TrainEngine:
         rec(ev["res_slot"].record, self.side)
         rec(pst.wait_event, ev["res_slot"])
         if self.multi:
-            # ... and the row merge's deadline pass (main stream, _pump_start) has read the slot ids it wanted from it
+            # ... and the row merge's deadline pass (main stream, MergePump.aggregate) has read the slot ids it wanted from it
             rec(pst.wait_event, ev["tier_marked"])
         ops.window_resolve(self.ctx, pr["cols"], pr["lbs"], pr["ws"], pr["wsrc"], stream=pst, batch_len=pr["B"])
         if S.is_hip(self.dev):
@@ -1664,49 +1953,32 @@ class TrainEngine:
 
     # ----------------------------------------------------------------------------------------------
     def sync_touched_to_rank0(self):
-        """The reference refills rank 0's cache and then broadcasts EVERY cache table from rank 0
-        (main_no_ddp.py:318-319), which also overwrites whatever the other ranks changed since the last
-        table-agg merge.  Same result without moving 10.9 GB: only the rows some rank touched since that merge can
-        differ, so broadcast exactly those (union of the touched flags), leaving the flags set for the next merge."""
-        if not self.multi:
+        """Rank 0's copy of every row some rank touched since the last merge, on all ranks (MergePump.sync_to_rank0): call it
+        on every rank in front of a window's refill.  Nothing to do on one rank."""
+        if self.merge is not None:
+            self.merge.sync_to_rank0()
+
+    def table_aggregate(self):
+        """broadcast_and_aggregate (main_no_ddp.py:250-292): average the rows any rank touched since the last merge
+        (MergePump.aggregate).  A merge that is still on its way lands first (a merge period shorter than the look-ahead), then
+        the remainder tables of quotient-remainder mode are merged whole, one small all-reduce."""
+        if self.merge is None:
+            self.cg.touched.zero_()
             return
-        ctx = self.ctx
-        self._pump_finish()         # the refill that follows reads and evicts cache rows: the last merge lands first
-        self._agg_alloc()
-        self._agg_flags.copy_(self.cg.touched)
-        dist.all_reduce(self._agg_flags, op=dist.ReduceOp.MAX, group=self.pg)
-        U = self._agg_list(self._agg_flags)
-        if U == 0:
+        self.merge.drain()
+        if self.Wr is not None:
+            self._merge_wr()
+        self.merge.aggregate(self._res.pos if self._res is not None else None, self.iter)
+
+    def _exchange(self, g, stream=None):
+        """aggregate_gradients (main_no_ddp.py:239-244) on the current stream: g /= world, all-reduce(SUM) -- or the one
+        all-reduce(AVG) where that gives the same bits (_reduce_avg).  stream: passed on to the scaling launch."""
+        if self._reduce_avg():
+            dist.all_reduce(g, op=dist.ReduceOp.AVG, group=self.pg)
             return
-        buf = self._agg_buffer(U)
-        ops.agg_gather(ctx, self.agg_rows, self.agg_count, 1.0, buf, U)
-        dist.broadcast(buf, src=0, group=self.pg)
-        ops.agg_scatter(ctx, self.agg_rows, self.agg_count, buf, U)
-
-    def _agg_alloc(self):
-        if self.agg_rows is None:
-            self.agg_rows = torch.empty(self.ctx.total_rows, dtype=torch.int64, device=self.dev)
-            self.agg_count = torch.zeros(1, dtype=torch.int64, device=self.dev)
-            self.agg_count_host = S.pinned(torch.zeros(1, dtype=torch.int64), self.dev)
-            self._agg_flags = torch.zeros(self.ctx.total_rows, dtype=torch.uint8, device=self.dev)
-            self._agg_counted = S.new_event(self.dev)
-            self._agg_buf = None
-
-    def _agg_list(self, flags) -> int:
-        """flags -> sorted row list (device) and its length on the host.  The host waits for THIS copy only (an event
-        behind the compaction), not for the stream: kernels queued behind it keep the GPU busy meanwhile."""
-        ops.agg_compact(self.ctx, flags, self.agg_rows, self.agg_count)
-        self.agg_count_host.copy_(self.agg_count, non_blocking=True)
-        self._agg_counted.record(S.current_stream(self.dev))
-        self._agg_counted.synchronize()
-        return int(self.agg_count_host[0])
-
-    def _agg_buffer(self, U: int) -> torch.Tensor:
-        """[>= U, D] exchange buffer, kept between merges (grown by doubling: no allocation in a steady-state merge)."""
-        if self._agg_buf is None or self._agg_buf.shape[0] < U:
-            cap = 1 << max(12, (U - 1).bit_length())
-            self._agg_buf = torch.empty(min(cap, self.ctx.total_rows), self.D, dtype=torch.float32, device=self.dev)
-        return self._agg_buf[:U]
+        kw = {} if stream is None else {"stream": stream}
+        ops.scale_div(g, float(self.world), **kw)       # layer.weight.grad /= world (:239); biases untouched
+        dist.all_reduce(g, op=dist.ReduceOp.SUM, group=self.pg)
 
     def step(self, X: torch.Tensor, lS_i: torch.Tensor, T: torch.Tensor, lS_o: Optional[torch.Tensor] = None,
              j: Optional[int] = None, gather_events: Optional[list] = None, next_idx: Optional[torch.Tensor] = None,
@@ -1766,14 +2038,8 @@ class TrainEngine:
         else:
             self._gslot = (ops.TimingEvent(), ops.TimingEvent())
             gather_events.append(self._gslot)
-        if self._pump is not None:
-            # the deadlines of a pending merge were computed for the batches FOLLOWING the merge step in its window: a step that
-            # is not the expected next batch of that window (another resolver, a jump) gets the whole merge first
-            p, pos = self._pump, (res.pos if res is not None else None)
-            if pos is None or pos[0] is not p["rs"] or pos[1] != p["j0"] + (self.iter - p["step0"]):
-                self._pump_finish()
-        if self._pump is not None:
-            self._pump_wait()       # rows of an earlier merge that THIS step uses have landed
+        if self.merge is not None:
+            self.merge.before_step(res.pos if res is not None else None, self.iter)     # rows of an earlier merge this step uses
         self._cur_sorted = self._next_sorted = None
         sliced = lS_o is None and not self.evict_victim
         if sliced:
@@ -1822,33 +2088,19 @@ class TrainEngine:
             # two exchanges, issued in the same order on every rank: the top MLP's (its weight gradients were launched
             # on the side stream right after the top dgrad chain) runs beside the rest of this step's backward and the
             # head of the next step; the bottom MLP's is the only one on the critical path
-            wst, W = self.wst, float(self.world)
+            wst = self.wst
             gt, gb = self._grad_views
-            avg = self._reduce_avg()
             with S.on_stream(wst):
-                if avg:
-                    dist.all_reduce(gt, op=dist.ReduceOp.AVG, group=self.pg)
-                else:
-                    ops.scale_div(gt, W, stream=wst)             # layer.weight.grad /= world (:239); biases untouched
-                    dist.all_reduce(gt, op=dist.ReduceOp.SUM, group=self.pg)
+                self._exchange(gt, stream=wst)
                 self._dense_step2(path, self.rng_top, stream=wst)
                 self._events["top_updated"].record(wst)
-            if avg:
-                dist.all_reduce(gb, op=dist.ReduceOp.AVG, group=self.pg)
-            else:
-                ops.scale_div(gb, W)
-                dist.all_reduce(gb, op=dist.ReduceOp.SUM, group=self.pg)
+            self._exchange(gb)
             if path.join == "emb_done":
                 S.current_stream(self.dev).wait_event(self._events["emb_done"])
             self._dense_step2(path, self.rng_bot)
             sgd_done = True
         elif self.multi:
-            gw = self.grad_flat[:self.n_weight]
-            if self._reduce_avg():
-                dist.all_reduce(gw, op=dist.ReduceOp.AVG, group=self.pg)
-            else:
-                ops.scale_div(gw, float(self.world))             # layer.weight.grad /= world (:239); biases untouched
-                dist.all_reduce(gw, op=dist.ReduceOp.SUM, group=self.pg)
+            self._exchange(self.grad_flat[:self.n_weight])
             # the join _fwd_bwd left out: the embedding backward / sparse SGD on the side stream ran beside the
             # all-reduce (the reference overlaps optimizer_embeds.step() with it the same way, :412-414)
             S.current_stream(self.dev).wait_event(self._events["emb_done"])
@@ -1864,8 +2116,8 @@ class TrainEngine:
             self.table_aggregate()
             # the next step's gather may run on the side stream: it has to see the merged rows
             self.side.wait_stream(S.current_stream(self.dev))
-        elif self._pump is not None:
-            self._pump_advance()    # the rows the NEXT step needs, and this step's share of the rest
+        elif self.merge is not None:
+            self.merge.after_step(self.iter)    # the rows the NEXT step needs, and this step's share of the rest
         self.iter += 1
         return self._buffers(B)["loss"]
 
@@ -2147,7 +2399,7 @@ class TrainEngine:
         ctx = self.ctx
         B, n = X.shape[0], lS_i.shape[1]
         assert n <= ctx.aux, "test batch larger than the aux table (test_mini_batch_size <= aux_table_size)"
-        if self._pump is not None:
+        if self.merge is not None and self.merge.pending:
             # Rows of the last merge are still on their way, and landing them means COLLECTIVES.  The test loop runs on rank 0
             # only (main_no_ddp.py:478-494): a rank that issued the remaining exchanges from here would issue them alone, in
             # other pieces and at another place of the communicator's order than its peers (a hang, or other ranks' gradients
@@ -2195,7 +2447,8 @@ class TrainEngine:
     def drain_merge(self):
         """Land every row of a merge that is still travelling in deadline order (MergePump).  COLLECTIVE: call it on every rank
         at the same step, or on none -- in front of anything only some ranks do next (the rank-0 test loop, a checkpoint)."""
-        self._pump_finish()
+        if self.merge is not None:
+            self.merge.drain()
 
     def finish(self):
         """Order the current stream behind a deferred top-MLP update (defer_top_update): call before reading the top
@@ -2205,7 +2458,7 @@ class TrainEngine:
             S.current_stream(self.dev).wait_event(self._events["top_updated"])
         if self._emb_done is not None:          # a pipelined short-batch step leaves the embedding update un-joined
             S.current_stream(self.dev).wait_event(self._emb_done)
-        self._pump_finish()                     # rows of the last merge that are still on their way
+        self.drain_merge()                      # rows of the last merge that are still on their way
 
     def prediction(self, B: int) -> torch.Tensor:
         """Z of the last step at batch size B as DLRM_Net.forward returns it (clamped under --loss-threshold)."""
@@ -2303,188 +2556,3 @@ class TrainEngine:
             p["rcols"], p["rws"] = pr["cols"].data_ptr(), pr["ws"].data_ptr()
             p["rwsrc"], p["rev"] = pr["wsrc"].data_ptr(), int(pr["ev"].cuda_event)
         return p
-
-    # ---- the touched-row merge in deadline order ----------------------------------------------------------------------
-    # broadcast_and_aggregate (main_no_ddp.py:250-292) replaces every row any rank touched since the last merge by its mean
-    # (max, sum) over the ranks, at step j, before step j + 1 runs.  What step j + 1 can observe of that is the rows IT uses;
-    # a row nobody uses before step j + d may be merged any time before step j + d -- it does not change in between on any
-    # rank.  The window's resolved slot ids (WindowResolver.lookahead: every rank's lookups of the next batches) say which
-    # rows the next K steps use: the merge's row list is sorted by the first batch that needs a row (classes: batch 1, 2, 3-4,
-    # 5-8, 9-16, 17-32, 33-64, later = "cold", due at batch K + 1) and exchanged in that order on the exchange stream -- gather, all-
-    # reduce, scatter per chunk -- a few chunks per step, while the training steps run; a step waits for the chunk that holds
-    # the last row it needs.  At c3 (100 steps x 8192 lookups x 26 tables, Zipf 1.05: 1.86 M rows, 0.95 GB) the next batch
-    # needs 2.3 % of the merge's rows, the next 16 batches 13 %.  Same values as the merge in one piece: every rank builds the
-    # same list from the same flags and the same window, and a row's gather reads what the one-piece merge would have read.
-    MERGE_CLASS_FIRST = (1, 2, 3, 5, 9, 17, 33)     # first batch (after the merge step) of each deadline class; then: cold
-    MERGE_LOOKAHEAD = 64                            # batches ahead the classes reach (the resolver decides how many are known)
-
-    def _pump_start(self, U, buf, scale, rop) -> bool:
-        pos = self._res.pos if self._res is not None else None
-        if pos is None:
-            return False
-        rs, j = pos
-        la = rs.lookahead(j, self.MERGE_LOOKAHEAD)
-        if not la:
-            return False            # nothing known about the next batch (end of the window): the merge in one piece
-        ctx, main = self.ctx, S.current_stream(self.dev)
-        first = self.MERGE_CLASS_FIRST
-        C = len(first) + 1
-        K = la[-1][0]
-        if ("agg_tier",) not in self._bufs:
-            self._bufs[("agg_tier",)] = (torch.empty(ctx.total_rows, dtype=torch.uint8, device=self.dev),
-                                         torch.empty(ctx.total_rows, dtype=torch.int64, device=self.dev),
-                                         torch.zeros(C + 1, dtype=torch.int64, device=self.dev),
-                                         S.pinned(torch.zeros(C + 1, dtype=torch.int64), self.dev))
-        tier, rows_sorted, off_dev, off_host = self._bufs[("agg_tier",)]
-        tier.fill_(C - 1)
-        seen = set()
-        for k, ws, ev in la:
-            if id(ev) not in seen:
-                main.wait_event(ev)
-                seen.add(id(ev))
-        for c in reversed(range(C - 1)):        # latest deadline first: the earliest class that names a row wins
-            hi = first[c + 1] if c + 1 < len(first) else self.MERGE_LOOKAHEAD + 1
-            for k, ws, ev in la:
-                if first[c] <= k < hi:
-                    ops.agg_mark_tier(ctx, ws, c, tier)
-        ops.agg_split(ctx, self.agg_rows, U, tier, C, rows_sorted, off_dev)
-        self._events["tier_marked"].record(main)
-        off_host.copy_(off_dev, non_blocking=True)
-        self._agg_counted.record(main)
-        self._agg_counted.synchronize()
-        off = [int(x) for x in off_host.tolist()]
-        ready = S.new_event(self.dev)
-        ready.record(main)
-        # (the budget cuts the exchange into pieces: it has to be the same number on every rank -- the resolver's lbs =
-        #  ceil(B / world), not this rank's slice width, which is shorter on the last rank when world does not divide B)
-        budget = int(self.merge_budget_rows)
-        if self.merge_budget_auto:
-            budget = max(budget, int(rs.lbs) * self.T)
-        self._pump = dict(rows=rows_sorted, U=U, buf=buf, scale=scale, rop=rop, off=off, K=K, step0=self.iter, issued=0,
-                          waited=0, chunks=[], ready=ready, budget=budget, rs=rs, j0=j)
-        self._pump_advance()
-        return True
-
-    def _pump_need(self, d: int) -> int:
-        """Rows of the pending merge that have to have landed before the d-th step after it."""
-        p = self._pump
-        if d > p["K"]:
-            return p["U"]
-        need = 0
-        for c, f in enumerate(self.MERGE_CLASS_FIRST):
-            if f <= d:
-                need = p["off"][c + 1]
-        return need
-
-    def _pump_issue(self, lo: int, hi: int):
-        p, ctx, comm = self._pump, self.ctx, self.comm
-        with S.on_stream(comm):
-            if not p["chunks"]:
-                comm.wait_event(p["ready"])
-            ops.agg_gather(ctx, p["rows"][lo:], self.agg_count, p["scale"], p["buf"][lo:hi], hi - lo, first=lo)
-            dist.all_reduce(p["buf"][lo:hi], op=p["rop"], group=self.pg)
-            ops.agg_scatter(ctx, p["rows"][lo:], self.agg_count, p["buf"][lo:hi], hi - lo, first=lo)
-            ev = S.new_event(self.dev)
-            ev.record(comm)
-        p["chunks"].append((hi, ev))
-        p["issued"] = hi
-
-    def _pump_advance(self, everything: bool = False):
-        """Issue the chunks the NEXT step needs, plus `merge_budget_rows` of the rest (everything: all of it)."""
-        p = self._pump
-        if p is None:
-            return
-        d_next = self.iter + 1 - p["step0"]
-        target = p["U"] if everything else max(self._pump_need(d_next), min(p["U"], p["issued"] + p["budget"]))
-        ch = max(1, int(self.agg_chunk_rows))
-        while p["issued"] < target:
-            self._pump_issue(p["issued"], min(target, p["issued"] + ch))
-
-    def _pump_wait(self, everything: bool = False):
-        """The training (and the side) stream wait for the chunk that holds the last row this step needs."""
-        p = self._pump
-        need = p["U"] if everything else self._pump_need(self.iter - p["step0"])
-        if need > p["waited"]:
-            assert p["issued"] >= need, "merge rows this step needs were never issued"
-            for hi, ev in p["chunks"]:
-                if hi >= need:
-                    S.current_stream(self.dev).wait_event(ev)
-                    self.side.wait_event(ev)
-                    p["waited"] = hi
-                    break
-        if p["waited"] >= p["U"]:
-            self._pump = None
-
-    def _pump_finish(self):
-        if self._pump is not None:
-            self._pump_advance(everything=True)
-            self._pump_wait(everything=True)
-            self._pump = None
-
-    def table_aggregate(self):
-        """broadcast_and_aggregate (main_no_ddp.py:250-292): average the rows any rank touched since the last
-        merge.  Slot ids are global, so the union of touched rows is an all-reduce(MAX) of the flag bytes (the reference
-        all-gathers the slot lists and takes torch.unique per table); the rows then travel as ONE compacted [U, D]
-        buffer, in chunks: while chunk i is reduced over xGMI on the exchange stream, chunk i+1 is gathered and chunk
-        i-1 scattered back on the main stream.  No allocation in steady state; the host waits only for the row count."""
-        cg, ctx = self.cg, self.ctx
-        touched = cg.touched
-        if not self.multi:
-            touched.zero_()
-            return
-        main = S.current_stream(self.dev)
-        self._pump_finish()         # (a merge period shorter than the look-ahead: the previous merge's rows land first)
-        if self.Wr is not None:
-            self._merge_wr()        # one small all-reduce: the remainder tables, whole
-        dist.all_reduce(touched, op=dist.ReduceOp.MAX, group=self.pg)
-        self._agg_alloc()
-        U = self._agg_list(touched)                   # consumes (clears) the flags
-        if U == 0:
-            return
-        buf = self._agg_buffer(U)
-        if self.agg_op == "mean":
-            scale, rop = float(self.world), dist.ReduceOp.SUM
-        elif self.agg_op == "sum":
-            scale, rop = 1.0, dist.ReduceOp.SUM
-        elif self.agg_op == "max":
-            scale, rop = 1.0, dist.ReduceOp.MAX
-        else:
-            raise ValueError(self.agg_op)
-        if self.lazy_merge and self.comm is not None and self._pump_start(U, buf, scale, rop):
-            return
-        ch = self.agg_chunk_rows
-        nch = (U + ch - 1) // ch
-        if nch == 1 or self.comm is None or not S.is_hip(self.dev):
-            ops.agg_gather(ctx, self.agg_rows, self.agg_count, scale, buf, U)
-            dist.all_reduce(buf, op=rop, group=self.pg)
-            ops.agg_scatter(ctx, self.agg_rows, self.agg_count, buf, U)
-            return
-        comm = self.comm
-        gathered = [S.new_event(self.dev) for _ in range(nch)]
-        reduced = [S.new_event(self.dev) for _ in range(nch)]
-
-        def gather(i):
-            lo, hi = i * ch, min(U, (i + 1) * ch)
-            ops.agg_gather(ctx, self.agg_rows[lo:], self.agg_count, scale, buf[lo:hi], hi - lo, first=lo)
-            gathered[i].record(main)
-
-        def reduce(i):
-            lo, hi = i * ch, min(U, (i + 1) * ch)
-            with S.on_stream(comm):
-                comm.wait_event(gathered[i])
-                dist.all_reduce(buf[lo:hi], op=rop, group=self.pg)
-                reduced[i].record(comm)
-
-        def scatter(i):
-            lo, hi = i * ch, min(U, (i + 1) * ch)
-            main.wait_event(reduced[i])
-            ops.agg_scatter(ctx, self.agg_rows[lo:], self.agg_count, buf[lo:hi], hi - lo, first=lo)
-
-        gather(0)
-        for i in range(nch):
-            reduce(i)
-            if i + 1 < nch:
-                gather(i + 1)
-            if i >= 1:
-                scatter(i - 1)
-        scatter(nch - 1)

@@ -92,7 +92,7 @@ class AsyncPeers:
         raise AssertionError("the sharded window fetch is not part of this test (shard_fetch=False)")
 
 
-def _train(g, *, world, defer, chunk, agg_freq, agg_op, long_batch=False, budget=0, skip_pump_wait=False, stats=None):
+def _train(g, *, world, defer, chunk, agg_freq, agg_op, long_batch=False, budget=0, skip_step_wait=False, stats=None):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_engine_parity import DEV, make_batches
     import cdlrm_amd.engine as engine
@@ -118,8 +118,8 @@ def _train(g, *, world, defer, chunk, agg_freq, agg_op, long_batch=False, budget
         eng.gather_alone_min = 1
     if budget:
         eng.merge_budget_rows, eng.merge_budget_auto = budget, False
-    if skip_pump_wait:              # negative control: steps do not wait for the merge rows they use
-        eng._pump_wait = lambda everything=False: None if not everything else engine.TrainEngine._pump_wait(eng, True)
+    if skip_step_wait:              # negative control: steps do not wait for the merge rows they use
+        eng.merge.wait = lambda it, everything=False: None if not everything else engine.MergePump.wait(eng.merge, it, True)
     batches = make_batches(g)
     dev_idx = [b[1].to(DEV) for b in batches]
     losses = []
@@ -140,7 +140,7 @@ def _train(g, *, world, defer, chunk, agg_freq, agg_op, long_batch=False, budget
                         next_res=rs.batch(j % L + 1) if (rs is not None and nxt is not None) else None)
         if rs is not None:
             rs.ensure(j % L + rs.CH + 2)
-        if stats is not None and eng._pump is not None:
+        if stats is not None and eng.merge.pending:
             stats["steps_with_rows_on_their_way"] = stats.get("steps_with_rows_on_their_way", 0) + 1
         losses.append(loss[0:1].clone())
     eng.finish()
@@ -193,7 +193,7 @@ def test_the_double_notices_a_step_that_does_not_wait_for_its_merge_rows(golden,
     with torch.cuda.stream(main):
         plain = _train(g, world=1, **LAZY)
         monkeypatch.setattr(engine, "dist", AsyncPeers(2, "nccl", 400000))
-        multi = _train(g, world=2, skip_pump_wait=True, **LAZY)
+        multi = _train(g, world=2, skip_step_wait=True, **LAZY)
     assert not torch.equal(multi["weight"], plain["weight"])
 
 

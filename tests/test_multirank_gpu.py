@@ -581,11 +581,12 @@ def _lz_worker(rank, world, port, host_shared, ret, long_batch, auto_budget=Fals
                 eng.gather_alone_min = 1
             pipe = engine.WindowPipeline(cg, eg, L * B, parity_rng=True, rank=rank, world_size=world)
             losses, pending, deferred_rows = [], 0, 0
+            merges = []         # per merge that stayed on its way: its schedule, the chunk size, the pieces issued (their hi)
             for w in range(LZ["nwin"]):
                 wb = batches[w * L:(w + 1) * L]
                 win = torch.cat([b[1] for b in wb], dim=1).to(dev)
                 eng.sync_touched_to_rank0()
-                assert eng._pump is None
+                assert not eng.merge.pending
                 torch.manual_seed(5000 + w * L)
                 pipe.plan_window(win)
                 pipe.commit()
@@ -599,22 +600,31 @@ def _lz_worker(rank, world, port, host_shared, ret, long_batch, auto_budget=Fals
                                     next_res=rs.batch(jj + 1) if nxt is not None else None)
                     rs.ensure(jj + rs.CH + 2)
                     gstep = w * L + jj
-                    if eng._pump is not None:
+                    if eng.merge.pending:
+                        pump = eng.merge
                         pending += 1
-                        deferred_rows = max(deferred_rows, eng._pump["U"] - eng._pump["issued"])
+                        deferred_rows = max(deferred_rows, pump.sched.U - pump.issued)
+                        # the pieces issued so far, after eng.iter - step0 advances of this merge (the latest look replaces
+                        # the earlier ones of the same merge)
+                        look = dict(step0=pump.step0, sched=tuple(pump.sched), chunk=int(eng.agg_chunk_rows),
+                                    advances=eng.iter - pump.step0, pieces=[hi for hi, _ in pump.chunks])
+                        if merges and merges[-1]["step0"] == pump.step0:
+                            merges[-1] = look
+                        else:
+                            merges.append(look)
                         if pending == 1 and rank == 0:
                             # a rank-local test loop (main_no_ddp.py:478-494 runs on rank 0 only) must not land the rows that
                             # are still travelling: that takes collectives, which this rank would issue alone
-                            issued = eng._pump["issued"]
+                            issued = pump.issued
                             with pytest.raises(RuntimeError, match="drain_merge"):
                                 eng.evaluate(batches[0][0].to(dev), batches[0][1].to(dev))
-                            assert eng._pump is not None and eng._pump["issued"] == issued
+                            assert eng.merge.pending and pump.issued == issued
                         if pending == 2:
                             eval_at = gstep
                     if gstep == eval_at:
                         # what Run does at a test step: every rank drains, then rank 0 alone evaluates
                         eng.drain_merge()
-                        assert eng._pump is None
+                        assert not eng.merge.pending
                         if rank == 0:
                             evals.append(eng.evaluate(batches[0][0].to(dev), batches[0][1].to(dev)).cpu().clone())
                     losses.append(loss[0:1].clone())
@@ -624,7 +634,7 @@ def _lz_worker(rank, world, port, host_shared, ret, long_batch, auto_budget=Fals
             lin = M._linears(dl.top_l)
             outs[lazy] = dict(losses=torch.cat(losses).cpu(), tags=cg.tags.cpu().clone(),
                               rows=[cg.emb_l[k].weight.data[: LZ["ways"] * cg.cache_sizes[k]].cpu().clone() for k in range(len(ln_emb))],
-                              top_w=[l.weight.data.cpu().clone() for l in lin], pending=pending, deferred=deferred_rows)
+                              top_w=[l.weight.data.cpu().clone() for l in lin], pending=pending, deferred=deferred_rows, merges=merges)
         a, b = outs[True], outs[False]
         assert a["pending"] > 0 and a["deferred"] > 0, "the fixture must leave merge rows on their way across steps"
         assert b["pending"] == 0
@@ -645,7 +655,7 @@ def _lz_worker(rank, world, port, host_shared, ret, long_batch, auto_budget=Fals
         for x, y in zip(a["top_w"], b["top_w"]):
             assert same(x, y)
         ret.put((rank, dict(losses=a["losses"].numpy(), occ=[o.cpu().numpy() for o in cg.occupancy_tables],
-                            top_w=[w.numpy() for w in a["top_w"]], pending=a["pending"])))
+                            top_w=[w.numpy() for w in a["top_w"]], pending=a["pending"], merges=a["merges"])))
         dist.barrier()
         dist.destroy_process_group()
     except BaseException:
@@ -699,3 +709,15 @@ def test_merge_in_deadline_order_two_ranks(long_batch, port, world, auto_budget)
         for i in range(len(got[r]["top_w"])):
             np.testing.assert_allclose(got[r]["top_w"][i], tr.top[r][0][i].numpy(), rtol=1e-4, atol=1e-6)
             assert np.array_equal(got[r]["top_w"][i], got[0]["top_w"][i]), "weight replicas agree bit for bit"
+    # every rank cut its merges into the same pieces (mismatched collectives otherwise), and they are the schedule's pieces
+    from cdlrm_amd.engine import MERGE_CLASS_FIRST, MergeSchedule, merge_pieces
+    assert got[0]["merges"] and any(len(m["pieces"]) > 1 for m in got[0]["merges"])
+    for r in range(1, world):
+        assert got[r]["merges"] == got[0]["merges"], "rank %d issued other pieces than rank 0" % r
+    for m in got[0]["merges"]:
+        sched, want = MergeSchedule(*m["sched"]), []
+        assert len(sched.off) == len(MERGE_CLASS_FIRST) + 2 and sched.off[0] == 0 and sched.off[-1] == sched.U
+        for d_next in range(1, m["advances"] + 1):
+            issued = want[-1] if want else 0
+            want += [hi for _, hi in merge_pieces(issued, sched.target(d_next, issued), m["chunk"])]
+        assert m["pieces"] == want, m
