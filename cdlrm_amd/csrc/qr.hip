@@ -80,6 +80,7 @@ __global__ void __launch_bounds__(256) k_qr_bwd(const int64_t* __restrict__ idx,
             }
             for (int64_t i = lo; i < hi; ++i) {
                 const int64_t v = idx[i];
+                if (v < 0) continue;    // the forward flags it (r < 0); v % c would point below gWr
                 int64_t q = qr_quotient(v, c);
                 if (q < 0 || q >= rows_q) q = 0;
                 const int64_t r = v % c;
@@ -106,7 +107,7 @@ static int qr_lpr(int D4) { int l = pow2ceil(D4); return l > 64 ? 64 : (l < 4 ? 
 extern "C" int cdlrm_qr_embbag_fwd(const int64_t* idx, const int64_t* offsets, int64_t n, int64_t n_bags, const float* Wq,
                                    const float* Wr, int64_t rows_q, int32_t collisions, int32_t dim, int32_t op,
                                    float* out, float* eq_out, float* er_out, int32_t* err_word, void* stream) {
-    CDLRM_REQUIRE(idx && offsets && Wq && Wr && out && err_word, "null argument");
+    CDLRM_REQUIRE((idx || n == 0) && offsets && Wq && Wr && out && err_word, "null argument");   // no lookups: no idx to read
     CDLRM_REQUIRE(dim >= 4 && dim % 4 == 0 && collisions >= 1 && op >= 0 && op <= 2, "bad shape / operation");
     CDLRM_REQUIRE((((uintptr_t)Wq | (uintptr_t)Wr | (uintptr_t)out) & 15) == 0, "16-byte aligned rows");
     if (n_bags == 0) return 0;
@@ -123,7 +124,7 @@ extern "C" int cdlrm_qr_embbag_fwd(const int64_t* idx, const int64_t* offsets, i
 extern "C" int cdlrm_qr_embbag_bwd(const int64_t* idx, const int64_t* offsets, int64_t n, int64_t n_bags, const float* eq,
                                    const float* er, const float* grad_out, int64_t rows_q, int32_t collisions,
                                    int32_t dim, int32_t op, float* gWq, float* gWr, void* stream) {
-    CDLRM_REQUIRE(idx && offsets && grad_out && gWq && gWr, "null argument");
+    CDLRM_REQUIRE((idx || n == 0) && offsets && grad_out && gWq && gWr, "null argument");
     CDLRM_REQUIRE(op != 0 || (eq && er), "mult backward needs the pooled operands");
     CDLRM_REQUIRE(dim >= 4 && dim % 4 == 0 && collisions >= 1 && op >= 0 && op <= 2, "bad shape / operation");
     if (n_bags == 0) return 0;
@@ -179,7 +180,7 @@ __global__ void __launch_bounds__(256) k_bag_bwd(const int64_t* __restrict__ idx
 
 extern "C" int cdlrm_bag_fwd(const int64_t* idx, const int64_t* offsets, int64_t n, int64_t n_bags, const float* W,
                              int64_t rows, int32_t dim, float* out, int32_t* err_word, void* stream) {
-    CDLRM_REQUIRE(idx && offsets && W && out && err_word && dim >= 1 && rows >= 1, "bad argument");
+    CDLRM_REQUIRE((idx || n == 0) && offsets && W && out && err_word && dim >= 1 && rows >= 1, "bad argument");
     if (n_bags == 0) return 0;
     int64_t gx = cdiv(n_bags * dim, 256);
     if (gx > 8192) gx = 8192;
@@ -191,7 +192,7 @@ extern "C" int cdlrm_bag_fwd(const int64_t* idx, const int64_t* offsets, int64_t
 
 extern "C" int cdlrm_bag_bwd(const int64_t* idx, const int64_t* offsets, int64_t n, int64_t n_bags, const float* grad_out,
                              int64_t rows, int32_t dim, float* gW, void* stream) {
-    CDLRM_REQUIRE(idx && offsets && grad_out && gW && dim >= 1 && rows >= 1, "bad argument");
+    CDLRM_REQUIRE((idx || n == 0) && offsets && grad_out && gW && dim >= 1 && rows >= 1, "bad argument");
     if (n_bags == 0) return 0;
     int64_t gx = cdiv(n_bags * dim, 256);
     if (gx > 8192) gx = 8192;

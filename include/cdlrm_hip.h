@@ -402,7 +402,8 @@ int cdlrm_blend_rows(const float* dst, const int64_t* index, const float* rows, 
  *   out[b] = sum_bag Wq[q] (op 0: * , 1: + , 2: concat) sum_bag Wr[r];  out is [n_bags, D] (2D for concat).
  *   eq_out / er_out (optional, [n_bags, D]) keep the pooled operands for the mult backward.
  *   err_word: device int32, set non-zero when a quotient falls outside Wq.
- * bwd accumulates DENSE gradients gWq [rows_q, D], gWr [collisions, D] (caller zeroes them).
+ * bwd accumulates DENSE gradients gWq [rows_q, D], gWr [collisions, D] (caller zeroes them); it skips a negative idx
+ * (which the forward reports through err_word).  idx may be NULL when n == 0 (every bag empty: zero rows out).
  * ------------------------------------------------------------------------------------------- */
 int cdlrm_qr_embbag_fwd(const int64_t* idx, const int64_t* offsets, int64_t n, int64_t n_bags,
                         const float* Wq, const float* Wr, int64_t rows_q, int32_t collisions, int32_t dim,
@@ -447,7 +448,8 @@ int cdlrm_qr_cached_bwd_finish(cdlrm_ctx* ctx, const int32_t* collisions, int32_
  * mixed-dimension trick's PrEmbeddingBag (tricks/md_embedding_bag.py:60-78; its widths are powers of two down to 1).
  * Stand-alone operator like the QR bag: the reference never wires it into the cached path (main_no_ddp.py:612-621).
  *   out [n_bags, dim] = sum over the bag's indices of W[idx];  gW [rows, dim] += grad_out[bag] (float atomics).
- *   err_word: device int32, bit 0 set when an index lies outside [0, rows). */
+ *   err_word: device int32, bit 0 set when an index lies outside [0, rows); the backward skips such an index.
+ *   idx may be NULL when n == 0. */
 int cdlrm_bag_fwd(const int64_t* idx, const int64_t* offsets, int64_t n, int64_t n_bags, const float* W, int64_t rows,
                   int32_t dim, float* out, int32_t* err_word, void* stream);
 int cdlrm_bag_bwd(const int64_t* idx, const int64_t* offsets, int64_t n, int64_t n_bags, const float* grad_out,

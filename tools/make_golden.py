@@ -826,6 +826,77 @@ def g_md(M, MD, CM, QR):
     save("md", **out)
 
 
+def trick_bags_restated():
+    """tests/trick_bags_restated.py: the builders of the edge inputs, shared with tests/test_trick_bags_edges.py."""
+    tests = os.path.dirname(OUT)
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import trick_bags_restated as R  # noqa
+    return R
+
+
+def g_qr_edges(M, MD, CM, QR, out=None):
+    """The reference's QREmbeddingBag on the edge inputs of tests/trick_bags_restated.py at D = 12 and 20, all three
+    operations: `ragged` bags over a 103-category table, and the float32-quotient ids of the 39 884 406-category table in
+    `closed_by_n` bags.  The big quotient table's contents are qr_c4_weights; the fixture holds the rows the lookups address
+    and the gradient's rows (the sparse gradient names no other row)."""
+    R = trick_bags_restated()
+    out = {} if out is None else out
+    for kind in ("ragged", "quirk"):
+        for D in R.FIX_DIMS:
+            inp = R.fixture_qr_inputs(kind, D)
+            ncat, c = inp["ncat"], inp["c"]
+            rows_q = math.ceil(ncat / c)
+            idx, offs = torch.from_numpy(inp["idx"].copy()), torch.from_numpy(inp["off"].copy())
+            if kind == "ragged":
+                rng = np.random.RandomState(350 + D)
+                wq = torch.from_numpy(rng.randn(rows_q, D).astype(np.float32))
+                wr = torch.from_numpy(rng.randn(c, D).astype(np.float32))
+                used = torch.arange(rows_q)
+            else:
+                wq, wr = qr_c4_weights(rows_q, D, 5 + D), qr_c4_weights(c, D, 901 + D)
+                used = torch.unique((idx / c).long())
+                assert int(((idx / c).long() != idx // c).sum()) * 10 >= idx.numel()
+            key = "qr_%s_D%d_" % (kind, D)
+            out.update({key + "idx": idx, key + "offs": offs, key + "ncat": ncat, key + "c": c, key + "G": inp["G"],
+                        key + "wq_rows": used, key + "wq": wq[used], key + "wr": wr})
+            for op in ("mult", "add", "concat"):
+                E = QR.QREmbeddingBag(ncat, D, c, operation=op, mode="sum", sparse=True, _weight=[wq, wr])
+                V = E(idx, offs)
+                G = torch.from_numpy(inp["G"][:, :V.shape[1]].copy())
+                V.backward(G)
+                gq = E.weight_q.grad.coalesce()
+                assert bool(torch.isin(gq.indices()[0], used).all())
+                dense = torch.zeros(used.numel(), D)
+                dense[torch.searchsorted(used, gq.indices()[0])] = gq.values()
+                out.update({key + op + "_V": V.detach(), key + op + "_gq": dense, key + op + "_gr": E.weight_r.grad.to_dense()})
+                E.weight_q.grad = E.weight_r.grad = None
+            del wq
+    return out
+
+
+def g_md_edges(M, MD, CM, QR, out=None):
+    """The reference's PrEmbeddingBag.embs (nn.EmbeddingBag, sum) at widths 3 and 5 on `ragged` bags."""
+    from tricks import md_embedding_bag as MDT  # noqa
+    R = trick_bags_restated()
+    out = {} if out is None else out
+    for D in R.FIX_WIDTHS:
+        inp = R.fixture_bag_inputs(D)
+        torch.manual_seed(360 + D)
+        E = MDT.PrEmbeddingBag(inp["ncat"], D, D)
+        V = E(torch.from_numpy(inp["idx"].copy()), torch.from_numpy(inp["off"].copy()))
+        V.backward(torch.from_numpy(inp["G"].copy()))
+        key = "bag_D%d_" % D
+        out.update({key + "idx": inp["idx"], key + "offs": inp["off"], key + "G": inp["G"], key + "W": E.embs.weight.detach().clone(),
+                    key + "V": V.detach(), key + "gW": E.embs.weight.grad.to_dense()})
+    return out
+
+
+def g_trick_bag_edges(M, MD, CM, QR):
+    """tests/golden/trick_bag_edges.npz = g_qr_edges + g_md_edges (one file)."""
+    save("trick_bag_edges", **g_md_edges(M, MD, CM, QR, g_qr_edges(M, MD, CM, QR)))
+
+
 def g_window_groups(M, MD, CM, QR):
     """Drive the reference's Prefetcher.run() for real on a fake loader and record which batches end
     up in which FIFO entry (a-1)."""
@@ -896,7 +967,7 @@ def g_criteo_loader(M, MD, CM, QR):
 GENS = dict(criteo_loader=g_criteo_loader, isprime=g_isprime, appendix_a=g_appendix_a, writeback=g_writeback, init=g_init, dense=g_dense,
             dense_variants=g_dense_variants, random_data=g_random_data, synthetic_data=g_synthetic_data,
             embbag_sgd=g_embbag_sgd, train_w1=g_train_w1, train_shapes=g_train_shapes, train_w2=g_train_w2, qr=g_qr, qr_c4=g_qr_c4, md=g_md,
-            window_groups=g_window_groups)
+            trick_bag_edges=g_trick_bag_edges, window_groups=g_window_groups)
 
 
 def main():
