@@ -159,7 +159,7 @@ def dump_outputs(out_dir, eng, cg, host, idx, seed):
     for k in range(T):
         m = (tab_h == k) & ~cached_h
         if bool(m.any()):
-            rows[m] = host.emb_l[k].weight.data[ids_h[m]]
+            rows[m] = host.emb_l[k].weight.data[ids_h[m]].cpu()     # (.cpu(): a table hostmem.place_tables put in HBM)
     out = {"loss": eng._buffers(n)["loss"][:3], "prediction": eng.prediction(n).reshape(-1),
            "dense_params": eng.param_flat, "emb_rows": rows,
            "emb_lookups": torch.stack([tab_h, ids_h, cached_h.long()], 1).double()}

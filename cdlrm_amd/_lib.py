@@ -75,6 +75,9 @@ PROTOTYPES = {
     "cdlrm_ctx_bind_host_tables": (C.c_int, [vp, C.POINTER(vp)]),
     "cdlrm_host_register": (C.c_int, [vp, c_u64, C.POINTER(vp)]),
     "cdlrm_host_unregister": (C.c_int, [vp]),
+    "cdlrm_host_register_supported": (C.c_int, []),
+    "cdlrm_host_alloc": (C.c_int, [c_u64, C.POINTER(vp)]),
+    "cdlrm_host_free": (C.c_int, [vp]),
     "cdlrm_ctx_check_sync": (C.c_int, [vp, vp]),
     "cdlrm_embbag_probe": (C.c_int, [vp, vp, c_i64, c_i64, vp, vp, vp, c_i32, vp]),
     "cdlrm_window_resolve": (C.c_int, [vp, vp, c_i64, c_i64, c_i64, c_i64, vp, vp, vp]),
@@ -297,6 +300,43 @@ def require_gpu(what: str = "cdlrm_amd") -> None:
         raise CdlrmLibraryError(
             "%s needs a HIP device (MI355X / gfx950) and found none: cdlrm_amd has no CPU fallback for the cached training "
             "path -- every compute entry point is a hand-written HIP kernel behind csrc/libcdlrm_hip.so" % what)
+
+
+def host_register_supported() -> bool:
+    """Can this machine page-lock memory the process already has (hipHostRegister)?  Some guests cannot; pinned memory the
+    runtime allocates itself (hipHostMalloc) is what they offer."""
+    return raw().cdlrm_host_register_supported() == 1
+
+
+class PinnedBlock:
+    """`nbytes` of pinned, GPU-visible host memory straight from hipHostMalloc, at its exact size (torch's pinned allocator
+    rounds a request up to a power of two: a 20 GB table would take 32).  Freed with the last tensor over it (`tensor()` hands
+    out views that keep the block alive).  Raises MemoryError when the machine has no more pinned memory to give."""
+
+    def __init__(self, nbytes: int):
+        self.ptr, self.nbytes = None, int(nbytes)
+        out = vp()
+        rc = raw().cdlrm_host_alloc(self.nbytes, C.byref(out))
+        if rc == -12:
+            raise MemoryError(raw().cdlrm_last_error().decode("utf-8", "replace"))
+        check(rc)
+        self.ptr = out.value
+
+    def tensor(self, shape):
+        """fp32 tensor of `shape` over the block."""
+        import torch
+        n = 1
+        for s in shape:
+            n *= int(s)
+        assert n * 4 <= self.nbytes
+        buf = (C.c_float * n).from_address(self.ptr)
+        buf._block = self                       # the buffer a tensor is built on keeps the allocation alive
+        return torch.frombuffer(buf, dtype=torch.float32).view(*shape)
+
+    def __del__(self):
+        p, self.ptr = getattr(self, "ptr", None), None
+        if p and _lib is not None:
+            _lib.cdlrm_host_free(p)
 
 
 # Hardware queues per process that bench.py, the CLI, the launcher and the tools pin before HIP starts.  A card has a fixed

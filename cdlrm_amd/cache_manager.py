@@ -170,6 +170,7 @@ class Prefetcher:
                                      embeddings.to(dev, torch.float32).contiguous(), average_on_writeback,
                                      distinct=False)
                 torch.cuda.synchronize()
+                emb_tables.publish_rows([d[0] for d in eviction_data])
                 # queue.Queue / Manager().Queue: lets a caller wait until the host tables hold the rows
                 # (`eviction_fifo.join()`); the reference offers no such point and reads whatever has landed
                 done = getattr(eviction_fifo, "task_done", None)

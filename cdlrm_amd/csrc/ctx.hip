@@ -123,8 +123,51 @@ extern "C" int cdlrm_ctx_bind_host_tables(cdlrm_ctx* c, float* const* host_rows)
 
 extern "C" int cdlrm_host_register(void* host_ptr, uint64_t bytes, void** device_alias) {
     CDLRM_REQUIRE(host_ptr && bytes && device_alias, "null argument");
-    CDLRM_HIP_CHECK(hipHostRegister(host_ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable));
+    hipError_t e = hipHostRegister(host_ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();        // (the refusal is this call's result, not the next launch's)
+        cdlrm_set_error("hipHostRegister of %llu bytes failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        return (int)e;
+    }
     CDLRM_HIP_CHECK(hipHostGetDevicePointer(device_alias, host_ptr, 0));
+    return 0;
+}
+
+// Can this machine page-lock memory the process already has?  Some cannot (a guest whose driver has no user-pointer
+// mappings refuses every hipHostRegister with "invalid argument"): asked once, with a page of our own.
+extern "C" int cdlrm_host_register_supported(void) {
+    static int known = -1;
+    if (known < 0) {
+        void* p = nullptr;
+        if (posix_memalign(&p, 4096, 4096) != 0) return 0;
+        memset(p, 0, 4096);
+        hipError_t e = hipHostRegister(p, 4096, hipHostRegisterMapped | hipHostRegisterPortable);
+        if (e == hipSuccess) (void)hipHostUnregister(p);
+        (void)hipGetLastError();
+        free(p);
+        known = e == hipSuccess ? 1 : 0;
+    }
+    return known;
+}
+
+// Pinned, GPU-visible host memory of exactly `bytes` (no rounding up: the host tables are tens of GB each).
+// CDLRM_ENOMEM: the machine has no more pinned memory to give (the caller may place the block elsewhere).
+extern "C" int cdlrm_host_alloc(uint64_t bytes, void** out) {
+    CDLRM_REQUIRE(bytes && out, "null argument");
+    *out = nullptr;
+    hipError_t e = hipHostMalloc(out, bytes, hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *out = nullptr;
+        cdlrm_set_error("hipHostMalloc of %llu bytes failed: %s", (unsigned long long)bytes, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? CDLRM_ENOMEM : (int)e;
+    }
+    return 0;
+}
+
+extern "C" int cdlrm_host_free(void* ptr) {
+    if (!ptr) return 0;
+    CDLRM_HIP_CHECK(hipHostFree(ptr));
     return 0;
 }
 

@@ -250,6 +250,9 @@ class WindowPipeline:
         self.multi = self.world > 1 or bool(force_collectives)
         self.host_ptrs = host_tables.device_pointers()
         self.ctx.bind_host_tables(self.host_ptrs)
+        # tables that hostmem.place_tables had to put in HBM (a machine short of pinned memory): not for the CPU row gather
+        self._hbm_tables = [k for k, E in enumerate(host_tables.emb_l)
+                            if getattr(E, "weight_q" if hasattr(E, "weight_q") else "weight").data.is_cuda]
         # every rank holds a private copy of the host tables (hostmem.make_host_tables "replicas"): every rank writes its evictions
         # back -- identical rows on every rank at a commit (sync_touched_to_rank0 precedes it), so the copies stay identical
         self.replicated_host = bool(getattr(host_tables, "_replicated", False))
@@ -346,11 +349,21 @@ class WindowPipeline:
             rows_h = self._pinned(key + "_rows", (m, D), torch.float32)
             t2 = _time.perf_counter()
             off_r = [min(max(int(o), lo), hi) - lo for o in off]
-            ops.host_gather_rows(self.host_ptrs, idx_h, off_r, D, rows_h, self.gather_threads)
+            if not self._hbm_tables:
+                ops.host_gather_rows(self.host_ptrs, idx_h, off_r, D, rows_h, self.gather_threads)
+            else:       # the CPU gathers from the pinned tables only; the GPU copies the rows of the others behind the DMA
+                for k in range(len(self.host_ptrs)):
+                    a, b = off_r[k], off_r[k + 1]
+                    if b > a and k not in self._hbm_tables:
+                        ops.host_gather_rows(self.host_ptrs[k:k + 1], idx_h[a:b], [0, b - a], D, rows_h[a:b], self.gather_threads)
             t3 = _time.perf_counter()
             ev0, ev1 = S.new_event(self.dev, timing=True), S.new_event(self.dev, timing=True)
             ev0.record(side)
             dst_dev[lo:hi].copy_(rows_h[:m], non_blocking=True)
+            for k in self._hbm_tables:
+                a, b = lo + off_r[k], lo + off_r[k + 1]
+                if b > a:
+                    ops.gather_rows(self.host_ptrs[k], idx_dev[a:b], D, stream=side, out=dst_dev[a:b])
             ev1.record(side)
             if bd is not None:
                 bd["cpu_gather"] += (t3 - t2) * 1e3
@@ -573,6 +586,13 @@ class WindowPipeline:
                 self.plan.writeback(self.host_ptrs, self.avg, stream=self.side)
             self.written_back = S.new_event(self.dev)
             self.written_back.record(self.side)
+        if self.rank == 0 and self.write_back and getattr(self.host, "_shared", None):
+            # the tables are private copies of shared tensors (register_shared() where host memory cannot be registered): the
+            # rows just written back go to the shared tensors too, as a registered mapping would have received them
+            self.written_back.synchronize()
+            _, _, wo = self.plan.offsets()
+            tags = self.plan.ev_tag[:wo[self.ctx.T]].cpu()
+            self.host.publish_rows([t[t != -1] for t in (tags[wo[k]:wo[k + 1]] for k in range(self.ctx.T))])
         self.planned = None
 
     def close(self):

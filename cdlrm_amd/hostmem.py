@@ -60,11 +60,14 @@ def memory_limit():
 REPLICA_LIMIT_FRACTION = 0.85       # W private copies + W x pinned staging may take this much of the job's memory limit
 
 
-def host_tables_mode(table_bytes: int, world: int, *, staging_bytes: int = 0, shm_free="ask", limit="ask"):
+def host_tables_mode(table_bytes: int, world: int, *, staging_bytes: int = 0, shm_free="ask", limit="ask",
+                     can_register: bool = True):
     """How `world` ranks of one node get the host tables -- ONE decision for make_host_tables (the run) and bench.py --plan-only
     (the plan), so the two cannot disagree: returns (mode, error) with mode "private" (one rank), "shared" (one tmpfs mapping,
     rank 0 writes evictions back) or "replicas" (a private pinned copy per rank, every rank writes back), error a message when the
-    chosen mode cannot hold (else None).  CDLRM_HOST_TABLES = shared | replicas | auto (default) forces or leaves the choice."""
+    chosen mode cannot hold (else None).  CDLRM_HOST_TABLES = shared | replicas | auto (default) forces or leaves the choice.
+    can_register=False: this machine cannot register host memory (_lib.host_register_supported), so a shared mapping cannot be
+    made GPU-visible -- auto takes replicas, a forced "shared" is an error."""
     if world <= 1:
         return "private", None
     forced = os.environ.get("CDLRM_HOST_TABLES", "auto")
@@ -75,9 +78,12 @@ def host_tables_mode(table_bytes: int, world: int, *, staging_bytes: int = 0, sh
     if limit == "ask":
         limit = memory_limit()
     fits_shm = shm_free is None or shm_free >= table_bytes + (1 << 30)
-    mode = forced if forced != "auto" else ("shared" if fits_shm else "replicas")
+    mode = forced if forced != "auto" else ("shared" if fits_shm and can_register else "replicas")
     err = None
-    if mode == "shared" and not fits_shm:
+    if mode == "shared" and not can_register:
+        err = ("the shared host tables have to be registered by every rank, and this machine cannot register host memory "
+               "(hipHostRegister is not supported here): CDLRM_HOST_TABLES=replicas, or leave the choice to auto")
+    elif mode == "shared" and not fits_shm:
         err = ("the shared host tables (%.0f GB) do not fit %s (%.0f GB free): CDLRM_SHM_DIR=<larger tmpfs>, "
                "CDLRM_HOST_TABLES=replicas, or cap the tables (--max-ind-range)" % (table_bytes / 1e9, shared_table_dir(), shm_free / 1e9))
     if mode == "replicas" and limit and world * (table_bytes + staging_bytes) > REPLICA_LIMIT_FRACTION * limit:
@@ -102,6 +108,40 @@ def fill_uniform_from_device(dst: torch.Tensor, n_rows: int, device, seed: int, 
         dst[r0:r1].copy_(t, non_blocking=False)
 
 
+# What the window plan's pinned staging (winners' and victims' rows, engine.WindowPipeline) may come to take beside the tables
+# at the Terabyte shapes; place_tables leaves this much pinned memory free on a machine that runs out of it.
+PINNED_STAGING_RESERVE = 28 << 30
+
+
+def place_tables(ln: Sequence[int], m_spa: int, device) -> List[torch.Tensor]:
+    """Uninitialised fp32 [n_k, m_spa] storage for every table: pinned host memory at its exact size.  A machine may grant a
+    process less pinned memory than the tables need (a guest that pins from a fixed pool: 66 GB where the Terabyte shapes
+    take 96): there the tables that do not fit -- and, largest first, as many more as it takes to leave
+    PINNED_STAGING_RESERVE for the plan's staging -- are placed in HBM instead.  The kernels read and write a table through
+    its address wherever it lives; the plan's CPU row gather serves the pinned tables only (WindowPipeline._fetch_list)."""
+    from . import _lib
+    out: List[torch.Tensor] = [None] * len(ln)
+    short = False
+    for k, n in enumerate(ln):
+        try:
+            out[k] = _lib.PinnedBlock(n * m_spa * 4).tensor((n, m_spa))
+        except MemoryError:
+            short = True
+    while short:
+        try:
+            _lib.PinnedBlock(PINNED_STAGING_RESERVE)        # (freed at once: only whether it can be had)
+            break
+        except MemoryError:
+            pinned = [k for k, w in enumerate(out) if w is not None and ln[k] * m_spa * 4 >= (1 << 30)]
+            if not pinned:
+                break
+            out[max(pinned, key=lambda k: ln[k])] = None
+    for k, n in enumerate(ln):
+        if out[k] is None:
+            out[k] = torch.empty(n, m_spa, dtype=torch.float32, device=device)
+    return out
+
+
 def make_host_tables(ln_emb: Sequence[int], m_spa: int, *, device, seed: int = 123, rank: int = 0, world: int = 1,
                      shm_name: str = "cdlrm_host_tables", barrier=None) -> Embedding_Table_Group:
     """Synthetic host tables for bench / Run on synthetic data."""
@@ -109,9 +149,8 @@ def make_host_tables(ln_emb: Sequence[int], m_spa: int, *, device, seed: int = 1
     eg = Embedding_Table_Group(m_spa, np.array(ln), init="empty_meta")
 
     def private_copy():
-        for k, n in enumerate(ln):
-            w = torch.empty(n, m_spa, dtype=torch.float32, pin_memory=True)
-            fill_uniform_from_device(w, n, device, seed * 1009 + k)
+        for k, w in enumerate(place_tables(ln, m_spa, device)):
+            fill_uniform_from_device(w, ln[k], device, seed * 1009 + k)
             eg.emb_l[k].weight.data = w
         eg._pinned = True
         return eg
@@ -128,7 +167,9 @@ def make_host_tables(ln_emb: Sequence[int], m_spa: int, *, device, seed: int = 1
     import torch.distributed as dist
     mode = ["auto"]
     if rank == 0:           # rank 0 decides (host_tables_mode: the same function bench.py --plan-only prints), everybody follows
-        m, err = host_tables_mode(total * 4, world, staging_bytes=int(os.environ.get("CDLRM_PLAN_STAGING_BYTES", "0")))
+        from . import _lib
+        m, err = host_tables_mode(total * 4, world, staging_bytes=int(os.environ.get("CDLRM_PLAN_STAGING_BYTES", "0")),
+                                  can_register=_lib.host_register_supported())
         mode[0] = ("error: " + err) if err else m
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dist.broadcast_object_list(mode, src=0)

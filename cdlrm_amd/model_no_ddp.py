@@ -64,6 +64,7 @@ class Embedding_Table_Group(nn.Module):
         super().__init__()
         self._pinned = False
         self._registered: List[int] = []
+        self._shared: List[torch.Tensor] = []       # the shared tensors behind private pinned copies (_mirror_shared)
         if (m_spa is not None) and (ln_emb is not None):
             self.qr_flag = qr_flag
             if self.qr_flag:
@@ -141,6 +142,8 @@ class Embedding_Table_Group(nn.Module):
         page-lock them in THIS process and make them GPU-visible (hipHostRegister)."""
         from . import _lib
         import ctypes as C
+        if not _lib.host_register_supported():
+            return self._mirror_shared()
         for E in self.emb_l:
             w = E.weight.data
             if w.data_ptr() in self._registered or w.is_pinned():
@@ -152,6 +155,34 @@ class Embedding_Table_Group(nn.Module):
             self._registered.append(w.data_ptr())
         self._pinned = True
         return self
+
+    def _mirror_shared(self):
+        """register_shared() on a machine that cannot register host memory: the GPU of THIS process works on a pinned private
+        copy of every table (hostmem's "replicas": every rank applies the eviction write-backs to its own copy, identical on all
+        ranks), and the shared tensors are kept in step by hand -- rows this process's GPU has written to its copy are carried
+        to them (publish_rows), and every hand-out of the tables' addresses (device_pointers) first takes over what the shared
+        tensors hold, so a row another rank published, or anybody wrote on the CPU, is seen as through a registered mapping."""
+        if not self._shared:
+            for E in self.emb_l:
+                w = E.weight.data
+                p = torch.empty(w.shape, dtype=w.dtype, pin_memory=True)
+                p.copy_(w)
+                self._shared.append(w)
+                E.weight.data = p
+            self._replicated = True
+        self._pinned = True
+        return self
+
+    def publish_rows(self, rows_per_table):
+        """After this process's GPU has written rows of the tables (an eviction write-back, a flush) and the write has been
+        waited for: rows_per_table[k] = their indices (a tensor, or None).  Nothing to do unless the tables are private copies of
+        shared tensors (_mirror_shared), which then receive those rows."""
+        if not self._shared:
+            return
+        for k, idx in enumerate(rows_per_table):
+            if idx is not None and idx.numel():
+                i = idx.to("cpu", torch.int64)
+                self._shared[k][i] = self.emb_l[k].weight.data[i]
 
     def _plain(self, E, k):
         if not hasattr(E, "weight"):
@@ -180,6 +211,8 @@ class Embedding_Table_Group(nn.Module):
         """The host rows the cache is fed from, per table: a plain table's rows, a quotient-remainder table's QUOTIENT rows."""
         if not self._pinned:
             self.pin()
+        for E, w in zip(self.emb_l, self._shared):      # private copies of shared tensors (_mirror_shared): what those hold now
+            E.weight.data.copy_(w)
         return [int((E.weight_q if hasattr(E, "weight_q") else self._plain(E, k).weight).data.data_ptr())
                 for k, E in enumerate(self.emb_l)]
 
@@ -370,6 +403,7 @@ class Embedding_Table_Cache_Group(nn.Module):
         copies and are not written.  Synchronises.  (Quotient-remainder mode: the rows are quotient rows; the remainder tables
         belong to the engine, TrainEngine.flush_wr writes them back.)"""
         ptrs = emb_tables.device_pointers()
+        written = [None] * len(self.cache_sizes)
         for k in range(len(self.cache_sizes)):
             P = self.cache_sizes[k]
             tags = self.occupancy_tables[k].t().reshape(-1)                  # way-major: element w*P + s = slot id
@@ -377,8 +411,10 @@ class Embedding_Table_Cache_Group(nn.Module):
             if valid.numel() == 0:
                 continue
             rows = self.weight.data[self.row_base[k]:self.row_base[k] + self.num_ways * P].index_select(0, valid)
-            ops.scatter_rows(ptrs[k], tags.index_select(0, valid).contiguous(), rows.contiguous(), average)
+            written[k] = tags.index_select(0, valid).contiguous()
+            ops.scatter_rows(ptrs[k], written[k], rows.contiguous(), average)
         torch.cuda.synchronize(self.weight.device)
+        emb_tables.publish_rows(written)
 
     @property
     def touched(self) -> torch.Tensor:

@@ -589,9 +589,14 @@ def host_gather_rows(table_ptrs: Sequence[int], idx: torch.Tensor, off: Sequence
     check(_lib.lib().cdlrm_host_gather_rows(tp, idx.data_ptr(), oa, T, int(dim), dst.data_ptr(), int(threads)))
 
 
-def gather_rows(src_ptr: int, index: torch.Tensor, dim: int, stream=None) -> torch.Tensor:
+def gather_rows(src_ptr: int, index: torch.Tensor, dim: int, stream=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _require_cuda(index, "index")
-    out = torch.empty((index.numel(), dim), dtype=torch.float32, device=index.device)
+    if out is None:
+        out = torch.empty((index.numel(), dim), dtype=torch.float32, device=index.device)
+    else:
+        _require_cuda(out, "out")
+        assert index.dtype == torch.int64 and index.is_contiguous()
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (index.numel(), dim)
     check(_lib.lib().cdlrm_gather_rows(int(src_ptr), index.data_ptr(), index.numel(), dim, out.data_ptr(),
                                        stream_ptr(stream)))
     return out

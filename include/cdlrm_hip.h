@@ -78,6 +78,12 @@ int cdlrm_ctx_bind_host_tables(cdlrm_ctx* ctx, float* const* host_rows);
 /* Pin an existing host allocation so kernels can read/write it over PCIe; returns its device alias. */
 int cdlrm_host_register(void* host_ptr, uint64_t bytes, void** device_alias);
 int cdlrm_host_unregister(void* host_ptr);
+/* 1 when this machine can register host memory at all (asked once per process, with a page of the library's own), else 0. */
+int cdlrm_host_register_supported(void);
+
+/* Pinned, GPU-visible host memory of exactly `bytes`; CDLRM_ENOMEM when the machine has no more pinned memory to give. */
+int cdlrm_host_alloc(uint64_t bytes, void** out);
+int cdlrm_host_free(void* ptr);
 
 /* Read (and clear) the device error word set by kernels on out-of-range input (CDLRM_ERANGE). */
 int cdlrm_ctx_check_sync(cdlrm_ctx* ctx, void* stream);

@@ -271,7 +271,7 @@ def _run_window_boundary(host, L, gather_alone_min, steps_after=6):
     for k in range(T):
         if expect[k] is not None:
             tags_s, rows = expect[k]
-            assert torch.equal(host.emb_l[k].weight.data[tags_s], rows), "table %d: host rows of evicted tags != the cache rows they left" % k
+            assert torch.equal(host.emb_l[k].weight.data[tags_s].cpu(), rows), "table %d: host rows of evicted tags != the cache rows they left" % k
             # ... and an evicted tag is gone from its set
             P = int(cg.cache_sizes[k])
             assert not bool((cg.occupancy_tables[k][tags_s.to(DEV) % P] == tags_s.to(DEV).view(-1, 1)).any())
