@@ -1,0 +1,23 @@
+// The pair layout and the LDS footprints of the interaction kernels, shared by dense.hip (k_interact_*) and
+// bag_interact.hip (k_bag_interact_*).
+#pragma once
+#include "common.h"
+
+__device__ __forceinline__ int pair_base(int i, int itself) { return itself ? i * (i + 1) / 2 : i * (i - 1) / 2; }
+
+// ---- LDS footprints of the interaction kernels, floats per wave (a workgroup is four waves, each with a slice of its own) ----
+// Written down ONCE: the kernels carve their slices with these and interact_plan() sizes the launch's dynamic LDS from them.
+// Generic pair (any D): the feature tile [32][D + 1] + 32; the backward stages the pair gradients (padded to 4) behind it.
+__host__ __device__ constexpr int ia_generic_tile(int D) { return 32 * (D + 1) + 32; }
+__host__ __device__ constexpr int ia_generic_bwd_floats(int D, int npairs) { return ia_generic_tile(D) + ((npairs + 3) & ~3); }
+// Pipelined kernels (D = 4 D4 in 32 / 64 / 128 / 256).  A whole-row tile is [32][D + 4], a column slab's slice [32][D / NS + 4];
+// a staged dR row is the dense part + up to 32 * 33 / 2 pair gradients, a staged output row that + the pad word.
+__host__ __device__ constexpr int ia_row_tile(int D4) { return 32 * (4 * D4 + 4); }
+__host__ __device__ constexpr int ia_slab_slice(int D4, int NS) { return 32 * (4 * D4 / NS + 4); }
+__host__ __device__ constexpr int ia_grad_row(int D4) { return 4 * D4 + 528; }
+__host__ __device__ constexpr int ia_out_row(int D4) { return 4 * D4 + 532; }
+__host__ __device__ constexpr int ia_fwd_p_floats(int D4) { return ia_row_tile(D4); }
+__host__ __device__ constexpr int ia_bwd_p_floats(int D4) { return ia_row_tile(D4) + ia_grad_row(D4); }
+__host__ __device__ constexpr int ia_fwd_s_slices(int D4, int NS, bool DB) { return (DB ? 2 : 1) * ia_slab_slice(D4, NS); }
+__host__ __device__ constexpr int ia_fwd_s_floats(int D4, int NS, bool DB) { return ia_fwd_s_slices(D4, NS, DB) + ia_out_row(D4); }
+__host__ __device__ constexpr int ia_bwd_s_floats(int D4, int NS) { return ia_slab_slice(D4, NS) + ia_grad_row(D4); }

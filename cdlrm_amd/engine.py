@@ -1467,8 +1467,12 @@ class TrainEngine:
         # Criteo layout + dot interaction: the gather IS the interaction's operand load (cdlrm_gather_interact_fwd / _bwd) -- the
         # [B, T, D] block between cached EmbeddingBag and interact_features is neither written nor read back (c3: 109 MB + 113 MB
         # per step), the backward reads the rows again from the cache, in front of the batch's embedding update.  Bit-identical
-        # to the two operators (False: gather + interaction as two launches; multi-hot bags and "cat" always take those).
+        # to the two operators (False: gather + interaction as two launches; "cat" always takes those, multi-hot bags unless fuse_bags).
         self.fuse_gather = True
+        # multi-hot bags (lS_o given) pooled inside the interaction kernels too (cdlrm_bag_interact_fwd / _bwd) instead of the two
+        # operators.  Opt-in (--fuse-bags): bit-identical, but its time against the two operators is recorded only stand-alone
+        # (tools/bag_interact_time.py), and the step-trace goldens pin the default multi-hot launch sequence
+        self.fuse_bags = False
         # (Where the sort of a batch's own slot ids and the top MLP's weight gradients start, the fold of the top-update wait
         #  and the take schedules were measured as knobs, rounds 1-6, and the losers removed: DESIGN_HISTORY.md.)
         # WindowResolver hands the NEXT step a look-ahead chunk to resolve (`_pending_resolve`, taken when `mark_next` is set): the
@@ -1731,7 +1735,10 @@ class TrainEngine:
     def _fused_gather(self, lS_o) -> bool:
         """This step's gather rides in the interaction kernels (fuse_gather)."""
         # (quotient-remainder mode composes the rows with Wr in the stand-alone gather: the fused kernels are a later step)
-        return bool(self.fuse_gather and lS_o is None and not self.cat and S.is_hip(self.dev) and self.qr is None
+        if lS_o is not None:        # multi-hot: the bags are pooled by the interaction kernels' operand producer (fuse_bags)
+            return bool(self.fuse_bags and not self.cat and S.is_hip(self.dev) and self.qr is None
+                        and ops.bag_interact_supported(self.ctx))
+        return bool(self.fuse_gather and not self.cat and S.is_hip(self.dev) and self.qr is None
                     and ops.gather_interact_supported(self.ctx))
 
     def _side_gather(self, B: int) -> bool:
@@ -2250,7 +2257,10 @@ class TrainEngine:
             if path.fwd_marked:
                 # the placed resolve (prefetch stream) waits for an event that completes WITH this launch
                 ops.event_attach_next(ev["fwd_mark"], main)
-            ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
+            if path.offsets:
+                ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R, n_bags=path.n_bags)
+            else:
+                ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         elif not self.cat:
             ops.interact_fwd(feat, self.itself, R)
         if path.resolve_cols is not None:
@@ -2337,6 +2347,8 @@ class TrainEngine:
             if once:
                 ops.gather_interact_bwd_sgd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, sv.once, sv.stride, self._rate_embeds(path),
                                             x_act=self.bot[-1][1])
+            elif fused and path.offsets:
+                ops.bag_interact_bwd(ctx, slots, lS_o, feat[:, 0, :], dR, self.itself, dfeat, n_bags=path.n_bags, x_act=self.bot[-1][1])
             elif fused:
                 ops.gather_interact_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
             else:
@@ -2443,7 +2455,9 @@ class TrainEngine:
             y = feat[:, 0, :] if i == len(self.bot) - 1 else buf["bot_y"][i]
             ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, **self._mm(l))
             cur = y
-        if self._fused_gather(lS_o):
+        if self._fused_gather(lS_o) and lS_o is not None:
+            ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R)
+        elif self._fused_gather(lS_o):
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         else:
             if self.qr is not None:         # (lS_i: quotients, r: the batch's remainders -- qr_split)

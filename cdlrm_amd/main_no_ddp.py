@@ -92,6 +92,8 @@ def ProcessArgs(argv=None):
     parser.add_argument("--num-ways", type=int, default=4)
     parser.add_argument("--average-on-writeback", action="store_true", default=False)
     parser.add_argument("--evict-victim-cache", action="store_true", default=False)
+    # multi-hot bags pooled inside the interaction kernels (cdlrm_bag_interact_fwd / _bwd) instead of gather + interaction
+    parser.add_argument("--fuse-bags", action="store_true", default=False)
     # ---- debugging and profiling ----
     parser.add_argument("--print-freq", type=int, default=1)
     parser.add_argument("--test-freq", type=int, default=-1)
@@ -540,6 +542,13 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                      "to the one host table)")
         lookahead_plan = False
         eng.evict_victim = True
+    if getattr(args, "fuse_bags", False):
+        eng.fuse_bags = True
+        if rank == 0:
+            fused = eng._fused_gather(True)
+            print("Multi-hot steps: %s" % ("bags pooled inside the interaction kernels (cdlrm_bag_interact_fwd / _bwd)" if fused else
+                                           "--fuse-bags has no kernel for this model (dot interaction, D in 32 / 64 / 128 / 256, "
+                                           "16 < tables + 1 <= 32, no QR): gather + interaction as two operators"))
     pipe = WindowPipeline(cache_group, emb_tables, L * aux_rows * 2, parity_rng=not args.device_rng,
                           seed=args.numpy_rand_seed, average_on_writeback=args.average_on_writeback, rank=rank,
                           world_size=world, host_gather=lookahead_plan,

@@ -692,6 +692,47 @@ def gather_interact_bwd_sgd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor,
                                                    dfeat.data_ptr(), int(once), int(ld_once), _rate(lr), stream_ptr(stream)))
 
 
+# ---- multi-hot bags pooled inside the interaction kernels (csrc/bag_interact.hip) ----
+
+BAG_INTERACT_U = 4      # CDLRM_BAG_INTERACT_U: lookups of one bag whose rows a lane has in flight at a time (D = 256: half)
+
+
+def bag_interact_supported(ctx: CacheCtx) -> bool:
+    """Shapes the fused bag pooling + interaction kernels take (D in 32 / 64 / 128 / 256, 16 < T + 1 <= 32)."""
+    return bool(_lib.raw().cdlrm_bag_interact_supported(ctx.handle))      # (a query: never on a step's tape)
+
+
+def _bag_args(ctx: CacheCtx, slots: torch.Tensor, offsets: torch.Tensor, n_bags: Optional[int], x: torch.Tensor):
+    assert slots.dtype == torch.int32 and slots.stride(1) == 1 and slots.stride(0) == slots.shape[1]
+    assert offsets.dtype == torch.int64 and offsets.stride(1) == 1 and x.stride(1) == 1
+    return (ctx.handle, slots.data_ptr(), slots.shape[1], offsets.data_ptr(), offsets.shape[1] if n_bags is None else int(n_bags),
+            offsets.stride(0), x.data_ptr(), x.stride(0))
+
+
+def bag_interact_fwd(ctx: CacheCtx, slots: torch.Tensor, offsets: torch.Tensor, x: torch.Tensor, itself: bool, R: torch.Tensor,
+                     n_bags: Optional[int] = None, stream=None):
+    """Cached EmbeddingBag forward of multi-hot bags (offsets int64 [T, n_bags], n_bags = B or B + 1) + dot interaction in one
+    launch: x [B, D] (any row pitch) is feature 0, feature t + 1 the sum-pool of bag b of table t over the cache rows `slots`
+    [T, n] names.  Bit-identical to embbag_fwd + interact_fwd."""
+    check(_lib.lib().cdlrm_bag_interact_fwd(*_bag_args(ctx, slots, offsets, n_bags, x), x.shape[0], int(bool(itself)),
+                                            R.data_ptr(), R.stride(0), stream_ptr(stream)))
+
+
+def bag_interact_bwd(ctx: CacheCtx, slots: torch.Tensor, offsets: torch.Tensor, x: torch.Tensor, dR: torch.Tensor, itself: bool,
+                     dfeat: torch.Tensor, n_bags: Optional[int] = None, stream=None, x_act: int = 0):
+    """interact_bwd with the bags pooled again from the cache (before the batch's embedding update rewrites the rows)."""
+    assert dfeat.is_contiguous()
+    check(_lib.lib().cdlrm_bag_interact_bwd(*_bag_args(ctx, slots, offsets, n_bags, x), dR.data_ptr(), dR.stride(0), x.shape[0],
+                                            int(bool(itself)), int(x_act), dfeat.data_ptr(), stream_ptr(stream)))
+
+
+def bag_interact_grid(op: int, B: int, D: int):
+    """(workgroups, dynamic LDS bytes) of a bag_interact_fwd (op 0) / _bwd (op 1) launch.  No device is touched."""
+    grid, lds = C.c_int64(), C.c_int64()
+    check(_lib.raw().cdlrm_bag_interact_grid(int(op), int(B), int(D), C.byref(grid), C.byref(lds)))
+    return grid.value, lds.value
+
+
 IA_OPS = {"fwd": 0, "bwd": 1, "gather_fwd": 2, "gather_bwd": 3, "gather_bwd_sgd": 4}
 IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db"}
 

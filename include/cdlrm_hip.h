@@ -537,6 +537,31 @@ int cdlrm_gather_interact_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, c
 int cdlrm_gather_interact_bwd_sgd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
                                   const float* dR, int64_t ld_r, int64_t B, int32_t itself, int32_t x_act, float* dfeat,
                                   const uint8_t* once, int64_t ld_once, float lr, void* stream);
+/* The same fusion for MULTI-HOT bags: cached EmbeddingBag forward with offsets (mode "sum", model_no_ddp.py:200-203) +
+ * interact_features "dot" (:272-293) in one launch -- the bags are pooled inside the interaction kernel, from +0 in lookup
+ * order (an empty bag is a zero row), and the pooled [B, T, D] block is never written or read back.
+ *   slots    device int32 [T, n]: the slot ids of the batch's lookups (cdlrm_embbag_probe / cdlrm_embbag_take), n >= 1
+ *   offsets  device int64 [T, ld_off]: bag b of table t is lookups offsets[t, b] .. offsets[t, b + 1] (n behind the last bag);
+ *            n_bags is B, or B + 1 for squared-off ragged bags -- only bags b < B are read, the scratch bag and its padding
+ *            lookups never are
+ *   x, R     as cdlrm_gather_interact_fwd's
+ * Bit-identical to cdlrm_embbag_fwd + cdlrm_interact_fwd.  Shapes: cdlrm_bag_interact_supported() (D in 32 / 64 / 128 / 256,
+ * 16 < T + 1 <= 32); anything else is refused -- the caller issues the two operators.  The forward carries a timed pair
+ * (cdlrm_ctx_time_next_gather) and an attached completion event like cdlrm_gather_interact_fwd.
+ * The backward (main_no_ddp.py:376 through :272-293) is cdlrm_interact_bwd on the bags pooled AGAIN from the cache -- call it
+ * BEFORE the batch's embedding update --: dfeat fp32 [B, T + 1, D], a row B behind it is not touched;
+ * cdlrm_embbag_bwd_apply with the same offsets consumes it.  It carries an attached completion event like cdlrm_interact_bwd.
+ * CDLRM_BAG_INTERACT_U: lookups of one bag whose rows a lane has in flight at a time. */
+#define CDLRM_BAG_INTERACT_U 4
+int cdlrm_bag_interact_supported(cdlrm_ctx* ctx);
+int cdlrm_bag_interact_fwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const int64_t* offsets, int64_t n_bags,
+                           int64_t ld_off, const float* x, int64_t ld_x, int64_t B, int32_t itself, float* R, int64_t ld_r,
+                           void* stream);
+int cdlrm_bag_interact_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const int64_t* offsets, int64_t n_bags,
+                           int64_t ld_off, const float* x, int64_t ld_x, const float* dR, int64_t ld_r, int64_t B,
+                           int32_t itself, int32_t x_act, float* dfeat, void* stream);
+/* Grid (workgroups of 256 lanes) and dynamic LDS of such a launch: op 0 forward, 1 backward.  No device is touched. */
+int cdlrm_bag_interact_grid(int32_t op, int64_t B, int32_t D, int64_t* grid, int64_t* lds_bytes);
 /* Which kernel an interaction call launches (cdlrm_interact_route below). */
 #define CDLRM_IA_GENERIC 1      /* k_interact_fwd / k_interact_bwd: any D, a barrier per sample */
 #define CDLRM_IA_ROW 2          /* k_interact_fwd_p / _bwd_p<d4>: software-pipelined, the sample's whole rows staged */
