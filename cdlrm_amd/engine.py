@@ -1473,6 +1473,11 @@ class TrainEngine:
         # operators.  Opt-in (--fuse-bags): bit-identical, but its time against the two operators is recorded only stand-alone
         # (tools/bag_interact_time.py), and the step-trace goldens pin the default multi-hot launch sequence
         self.fuse_bags = False
+        # quotient-remainder mode: the compose with Wr inside the interaction kernels (cdlrm_qr_interact_fwd / _bwd) instead of
+        # cdlrm_qr_cached_fwd + the interaction on the composed block; cdlrm_qr_cached_bwd / _bwd_finish follow as before.  Opt-in
+        # (--qr-fuse-gather): bit-identical, measured stand-alone only (tools/qr_interact_time.py), and existing
+        # tests pin the default QR launch sequence
+        self.fuse_qr = False
         # (Where the sort of a batch's own slot ids and the top MLP's weight gradients start, the fold of the top-update wait
         #  and the take schedules were measured as knobs, rounds 1-6, and the losers removed: DESIGN_HISTORY.md.)
         # WindowResolver hands the NEXT step a look-ahead chunk to resolve (`_pending_resolve`, taken when `mark_next` is set): the
@@ -1734,7 +1739,10 @@ class TrainEngine:
 
     def _fused_gather(self, lS_o) -> bool:
         """This step's gather rides in the interaction kernels (fuse_gather)."""
-        # (quotient-remainder mode composes the rows with Wr in the stand-alone gather: the fused kernels are a later step)
+        if self.qr is not None:     # quotient-remainder mode: the compose rides in the interaction kernels too (fuse_qr), else
+            #                         the stand-alone gather composes the rows with Wr (cdlrm_qr_cached_fwd)
+            return bool(self.fuse_qr and lS_o is None and not self.cat and S.is_hip(self.dev)
+                        and ops.qr_interact_supported(self.ctx))
         if lS_o is not None:        # multi-hot: the bags are pooled by the interaction kernels' operand producer (fuse_bags)
             return bool(self.fuse_bags and not self.cat and S.is_hip(self.dev) and self.qr is None
                         and ops.bag_interact_supported(self.ctx))
@@ -1797,7 +1805,8 @@ class TrainEngine:
             next_resolved=self._next_res is not None, two_phase=two_phase, chain=chain, side_gather=side_gather,
             gather_alone=B >= self.gather_alone_min, fused=fused, sorted=None if sv is None else sv.stride,
             # (row-wise Adagrad: the once-only fold is an SGD step -- the sorted apply takes every slot)
-            once=bool(self.fuse_once and fused and sv is not None and self.embed_optimizer == "sgd"), next_sorted=self._next_sorted is not None,
+            # (quotient-remainder mode: the gradient rows are rewritten by cdlrm_qr_cached_bwd first -- no fold)
+            once=bool(self.fuse_once and fused and sv is not None and self.embed_optimizer == "sgd" and self.qr is None), next_sorted=self._next_sorted is not None,
             chain_sort=chain and self._next_sorted is None, chained_top=chain and self.defer_top and not self.multi,
             next_bufs=(1 - phase) if two_phase else 2 + (self.iter & 1), emb_done_seen=self._emb_done is not None,
             timed=self._gslot is not None, loss_sync=self.loss_sync, resolve_cols=None if pr is None else int(pr["cols"].shape[1]),
@@ -2257,7 +2266,9 @@ class TrainEngine:
             if path.fwd_marked:
                 # the placed resolve (prefetch stream) waits for an event that completes WITH this launch
                 ops.event_attach_next(ev["fwd_mark"], main)
-            if path.offsets:
+            if self.qr is not None:
+                ops.qr_interact_fwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, feat[:, 0, :], self.itself, R)
+            elif path.offsets:
                 ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R, n_bags=path.n_bags)
             else:
                 ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
@@ -2347,6 +2358,9 @@ class TrainEngine:
             if once:
                 ops.gather_interact_bwd_sgd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, sv.once, sv.stride, self._rate_embeds(path),
                                             x_act=self.bot[-1][1])
+            elif fused and self.qr is not None:
+                ops.qr_interact_bwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, feat[:, 0, :], dR, self.itself, dfeat,
+                                    x_act=self.bot[-1][1])
             elif fused and path.offsets:
                 ops.bag_interact_bwd(ctx, slots, lS_o, feat[:, 0, :], dR, self.itself, dfeat, n_bags=path.n_bags, x_act=self.bot[-1][1])
             elif fused:
@@ -2455,7 +2469,10 @@ class TrainEngine:
             y = feat[:, 0, :] if i == len(self.bot) - 1 else buf["bot_y"][i]
             ops.linear_fwd(cur, self.W[l], l.bias.data, y, act, **self._mm(l))
             cur = y
-        if self._fused_gather(lS_o) and lS_o is not None:
+        if self._fused_gather(lS_o) and self.qr is not None:
+            assert r is not None and r.dtype == torch.uint8 and tuple(r.shape) == (self.T, n) and r.stride(1) == 1
+            ops.qr_interact_fwd(ctx, slots, r, self.Wr, self.qr_coll, self.qr_op, feat[:, 0, :], self.itself, R)
+        elif self._fused_gather(lS_o) and lS_o is not None:
             ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R)
         elif self._fused_gather(lS_o):
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)

@@ -94,6 +94,9 @@ def ProcessArgs(argv=None):
     parser.add_argument("--evict-victim-cache", action="store_true", default=False)
     # multi-hot bags pooled inside the interaction kernels (cdlrm_bag_interact_fwd / _bwd) instead of gather + interaction
     parser.add_argument("--fuse-bags", action="store_true", default=False)
+    # --qr-flag: the compose with the remainder rows inside the interaction kernels (cdlrm_qr_interact_fwd / _bwd) instead of
+    # cdlrm_qr_cached_fwd + interaction
+    parser.add_argument("--qr-fuse-gather", action="store_true", default=False)
     # ---- debugging and profiling ----
     parser.add_argument("--print-freq", type=int, default=1)
     parser.add_argument("--test-freq", type=int, default=-1)
@@ -188,6 +191,8 @@ def ProcessArgs(argv=None):
         # padding would inflate that index's priority
         sys.exit("ERROR: --insert-policy=fill counts the window's lookups, and --data-generation=%s pads the plan's "
                  "window with a repeated index (dataset | criteo-synthetic only)" % args.data_generation)
+    if args.qr_fuse_gather and not args.qr_flag:
+        sys.exit("ERROR: --qr-fuse-gather composes quotient-remainder rows inside the interaction kernels: it needs --qr-flag")
     if args.qr_flag:
         # quotient-remainder tables train through the cache: one lookup per bag, rows of one width
         if args.qr_operation not in ("mult", "add"):
@@ -549,6 +554,15 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             print("Multi-hot steps: %s" % ("bags pooled inside the interaction kernels (cdlrm_bag_interact_fwd / _bwd)" if fused else
                                            "--fuse-bags has no kernel for this model (dot interaction, D in 32 / 64 / 128 / 256, "
                                            "16 < tables + 1 <= 32, no QR): gather + interaction as two operators"))
+    if eng.qr is not None:
+        eng.fuse_qr = bool(getattr(args, "qr_fuse_gather", False))
+        if rank == 0:
+            why = ("--qr-fuse-gather not given" if not eng.fuse_qr else
+                   "--arch-interaction-op=cat" if eng.cat else
+                   "unsupported D / T (D in 32 / 64 / 128 / 256, 16 < tables + 1 <= 32)")
+            print("Quotient-remainder steps: %s" % ("compose inside the interaction kernels (cdlrm_qr_interact_fwd / _bwd)"
+                                                     if eng._fused_gather(None) else
+                                                     "cdlrm_qr_cached_fwd + interaction as two operators (%s)" % why), flush=True)
     pipe = WindowPipeline(cache_group, emb_tables, L * aux_rows * 2, parity_rng=not args.device_rng,
                           seed=args.numpy_rand_seed, average_on_writeback=args.average_on_writeback, rank=rank,
                           world_size=world, host_gather=lookahead_plan,

@@ -733,6 +733,45 @@ def bag_interact_grid(op: int, B: int, D: int):
     return grid.value, lds.value
 
 
+# ---- the quotient-remainder compose inside the interaction kernels (csrc/qr_interact.hip) ----
+
+def qr_interact_supported(ctx: CacheCtx) -> bool:
+    """Shapes the fused QR compose + interaction kernels take (D in 32 / 64 / 128 / 256, 16 < T + 1 <= 32)."""
+    return bool(_lib.raw().cdlrm_qr_interact_supported(ctx.handle))      # (a query: never on a step's tape)
+
+
+def _qr_interact_args(ctx: CacheCtx, slots, r, Wr, collisions, op, x):
+    n, ld_r, c = _qr_args(ctx, slots, r, Wr, collisions)
+    assert x.stride(1) == 1
+    return (ctx.handle, slots.data_ptr(), n, r.data_ptr(), ld_r, Wr.data_ptr(), collisions.data_ptr(), c, int(op), x.data_ptr(),
+            x.stride(0))
+
+
+def qr_interact_fwd(ctx: CacheCtx, slots: torch.Tensor, r: torch.Tensor, Wr: torch.Tensor, collisions: torch.Tensor, op: int,
+                    x: torch.Tensor, itself: bool, R: torch.Tensor, stream=None):
+    """qr_cached_fwd + dot interaction in one launch: x [B, D] (any row pitch) is feature 0, feature t + 1 the cache row of
+    slots[t, b] composed (op 0: *, 1: +) with Wr[t][r[t, b]]; a table with collisions[t] == 0 passes its row through.
+    Bit-identical to qr_cached_fwd + interact_fwd."""
+    check(_lib.lib().cdlrm_qr_interact_fwd(*_qr_interact_args(ctx, slots, r, Wr, collisions, op, x), x.shape[0],
+                                           int(bool(itself)), R.data_ptr(), R.stride(0), stream_ptr(stream)))
+
+
+def qr_interact_bwd(ctx: CacheCtx, slots: torch.Tensor, r: torch.Tensor, Wr: torch.Tensor, collisions: torch.Tensor, op: int,
+                    x: torch.Tensor, dR: torch.Tensor, itself: bool, dfeat: torch.Tensor, stream=None, x_act: int = 0):
+    """interact_bwd with the rows composed again from the cache and Wr (before the batch's updates rewrite them): dfeat gets the
+    raw gradient rows dL/dE; qr_cached_bwd / qr_cached_bwd_finish on dfeat[:, 1:, :] follow."""
+    assert dfeat.is_contiguous()
+    check(_lib.lib().cdlrm_qr_interact_bwd(*_qr_interact_args(ctx, slots, r, Wr, collisions, op, x), dR.data_ptr(), dR.stride(0),
+                                           x.shape[0], int(bool(itself)), int(x_act), dfeat.data_ptr(), stream_ptr(stream)))
+
+
+def qr_interact_grid(op: int, B: int, D: int):
+    """(workgroups, dynamic LDS bytes) of a qr_interact_fwd (op 0) / _bwd (op 1) launch.  No device is touched."""
+    grid, lds = C.c_int64(), C.c_int64()
+    check(_lib.raw().cdlrm_qr_interact_grid(int(op), int(B), int(D), C.byref(grid), C.byref(lds)))
+    return grid.value, lds.value
+
+
 IA_OPS = {"fwd": 0, "bwd": 1, "gather_fwd": 2, "gather_bwd": 3, "gather_bwd_sgd": 4}
 IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db"}
 

@@ -562,6 +562,30 @@ int cdlrm_bag_interact_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, cons
                            int32_t itself, int32_t x_act, float* dfeat, void* stream);
 /* Grid (workgroups of 256 lanes) and dynamic LDS of such a launch: op 0 forward, 1 backward.  No device is touched. */
 int cdlrm_bag_interact_grid(int32_t op, int64_t B, int32_t D, int64_t* grid, int64_t* lds_bytes);
+/* The same fusion for QUOTIENT-REMAINDER tables: cdlrm_qr_cached_fwd + interact_features "dot" in one launch -- the compose
+ * happens inside the interaction kernel and the composed [B, T, D] block is never written or read back.  Single-pass, read-only
+ * on the cache rows and on Wr.
+ *   slots       device int32 [T, n]: the slot ids of the batch's lookups, one per sample (n == B); a miss reads its auxiliary row
+ *   r           device uint8 [T, ld_r]: the remainders (cdlrm_qr_split), clamped to c - 1
+ *   Wr          device fp32 [T, c, D], 16-byte aligned; c in 2 .. 16
+ *   collisions  device int32 [T]; 0: a plain table -- its rows pass through and no Wr value is used for them
+ *   op          0: mult, 1: add (qrc_compose of cdlrm_qr_cached_fwd: one fp32 operation per element)
+ *   x, R        as cdlrm_gather_interact_fwd's (row pitches ld_x, ld_R)
+ * Bit-identical to cdlrm_qr_cached_fwd + cdlrm_interact_fwd.  Shapes: cdlrm_qr_interact_supported() (D in 32 / 64 / 128 / 256,
+ * 16 < T + 1 <= 32); anything else is refused -- the caller issues the two operators.  The forward carries a timed pair
+ * (cdlrm_ctx_time_next_gather) and an attached completion event like cdlrm_gather_interact_fwd.
+ * The backward is cdlrm_interact_bwd on the rows composed AGAIN from the cache and Wr -- call it BEFORE the batch's embedding and
+ * Wr updates --: dfeat fp32 [B, T + 1, D] receives the RAW gradient rows g = dL/dE; cdlrm_qr_cached_bwd / _bwd_finish on
+ * dfeat[:, 1:, :] follow unchanged.  It carries an attached completion event like cdlrm_interact_bwd. */
+int cdlrm_qr_interact_supported(cdlrm_ctx* ctx);
+int cdlrm_qr_interact_fwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const uint8_t* r, int64_t ld_r, const float* Wr,
+                          const int32_t* collisions, int32_t c, int32_t op, const float* x, int64_t ld_x, int64_t B,
+                          int32_t itself, float* R, int64_t ld_R, void* stream);
+int cdlrm_qr_interact_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const uint8_t* r, int64_t ld_r, const float* Wr,
+                          const int32_t* collisions, int32_t c, int32_t op, const float* x, int64_t ld_x, const float* dR,
+                          int64_t ld_dR, int64_t B, int32_t itself, int32_t x_act, float* dfeat, void* stream);
+/* Grid (workgroups of 256 lanes) and dynamic LDS of such a launch: op 0 forward, 1 backward.  No device is touched. */
+int cdlrm_qr_interact_grid(int32_t op, int64_t B, int32_t D, int64_t* grid, int64_t* lds_bytes);
 /* Which kernel an interaction call launches (cdlrm_interact_route below). */
 #define CDLRM_IA_GENERIC 1      /* k_interact_fwd / k_interact_bwd: any D, a barrier per sample */
 #define CDLRM_IA_ROW 2          /* k_interact_fwd_p / _bwd_p<d4>: software-pipelined, the sample's whole rows staged */
