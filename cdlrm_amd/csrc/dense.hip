@@ -1783,31 +1783,7 @@ static IaPlan interact_plan(int op, int64_t B, int F, int D, int itself, int64_t
     return p;
 }
 
-// run-time D4 of the pipelined kernels -> compile-time: fn(std::integral_constant<int, D4>{})
-template <typename Fn>
-static int ia_with_d4(int d4, Fn&& fn) {
-    switch (d4) {
-        case 8: return fn(std::integral_constant<int, 8>{});
-        case 16: return fn(std::integral_constant<int, 16>{});
-        case 32: return fn(std::integral_constant<int, 32>{});
-        case 64: return fn(std::integral_constant<int, 64>{});
-    }
-    cdlrm_set_error("interaction: no pipelined kernel at D = %d", 4 * d4);
-    return CDLRM_EINVAL;
-}
-
-// carry: an attached completion event (CdlrmStopScope of the entry point) rides on the launch as its stop event
-template <auto Kernel, typename... Args>
-static int ia_launch(const IaPlan& p, void* stream, bool carry, Args... args) {
-    const int rc = cdlrm_grant_dynamic_lds<Kernel>(p.lds);
-    if (rc) return rc;
-    const dim3 grid((unsigned)p.grid), block(256);
-    if (carry) CDLRM_LAUNCH_EV(Kernel, grid, block, p.lds, (hipStream_t)stream, args...);
-    else hipLaunchKernelGGL(Kernel, grid, block, p.lds, (hipStream_t)stream, args...);
-    CDLRM_LAUNCH_CHECK();
-    return 0;
-}
-
+// (ia_with_d4, ia_launch: interact_lds.h, shared with interact_wide.hip)
 extern "C" int cdlrm_interact_fwd(const float* feat, int64_t B, int32_t F, int32_t D, int32_t itself, float* R,
                                   int64_t ld_r, void* stream) {
     CDLRM_REQUIRE(feat && R && F >= 1 && F <= 32 && D >= 4 && D % 4 == 0 && D <= 512, "unsupported shape (F<=32, D%4==0)");

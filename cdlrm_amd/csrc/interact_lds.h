@@ -21,3 +21,41 @@ __host__ __device__ constexpr int ia_bwd_p_floats(int D4) { return ia_row_tile(D
 __host__ __device__ constexpr int ia_fwd_s_slices(int D4, int NS, bool DB) { return (DB ? 2 : 1) * ia_slab_slice(D4, NS); }
 __host__ __device__ constexpr int ia_fwd_s_floats(int D4, int NS, bool DB) { return ia_fwd_s_slices(D4, NS, DB) + ia_out_row(D4); }
 __host__ __device__ constexpr int ia_bwd_s_floats(int D4, int NS) { return ia_slab_slice(D4, NS) + ia_grad_row(D4); }
+// Wide kernels (interact_wide.hip, 32 < F <= 64): the Gram matrix is 64 x 64.  Pipelined pair (D = 4 D4 in 32 / 64 / 128 / 256):
+// a slab's slice is [64][32 + 4]; a staged dR row is the dense part + up to 64 * 65 / 2 pair gradients, a staged output row
+// that + the pad word.  Whole-row pair (any D): the feature tile [64][D + 1] + 32; the backward stages the pair gradients
+// (padded to 4) behind it.
+__host__ __device__ constexpr int iw_slab_slice() { return 64 * 36; }
+__host__ __device__ constexpr int iw_grad_row(int D4) { return 4 * D4 + 2080; }
+__host__ __device__ constexpr int iw_out_row(int D4) { return 4 * D4 + 2084; }
+__host__ __device__ constexpr int iw_fwd_floats(int D4) { return iw_slab_slice() + iw_out_row(D4); }
+__host__ __device__ constexpr int iw_bwd_floats(int D4) { return iw_slab_slice() + iw_grad_row(D4); }
+__host__ __device__ constexpr int iw_row_tile(int D) { return 64 * (D + 1) + 32; }
+__host__ __device__ constexpr int iw_row_bwd_floats(int D, int npairs) { return iw_row_tile(D) + ((npairs + 3) & ~3); }
+
+// ---- host helpers of the entry points in dense.hip and interact_wide.hip --------------------------------------------------------
+// run-time D4 of the pipelined kernels -> compile-time: fn(std::integral_constant<int, D4>{})
+template <typename Fn>
+static int ia_with_d4(int d4, Fn&& fn) {
+    switch (d4) {
+        case 8: return fn(std::integral_constant<int, 8>{});
+        case 16: return fn(std::integral_constant<int, 16>{});
+        case 32: return fn(std::integral_constant<int, 32>{});
+        case 64: return fn(std::integral_constant<int, 64>{});
+    }
+    cdlrm_set_error("interaction: no pipelined kernel at D = %d", 4 * d4);
+    return CDLRM_EINVAL;
+}
+
+// One launch of a plan (its .grid workgroups of 256 lanes, its .lds bytes of dynamic LDS).
+// carry: an attached completion event (CdlrmStopScope of the entry point) rides on the launch as its stop event
+template <auto Kernel, typename Plan, typename... Args>
+static int ia_launch(const Plan& p, void* stream, bool carry, Args... args) {
+    const int rc = cdlrm_grant_dynamic_lds<Kernel>(p.lds);
+    if (rc) return rc;
+    const dim3 grid((unsigned)p.grid), block(256);
+    if (carry) CDLRM_LAUNCH_EV(Kernel, grid, block, p.lds, (hipStream_t)stream, args...);
+    else hipLaunchKernelGGL(Kernel, grid, block, p.lds, (hipStream_t)stream, args...);
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}

@@ -642,18 +642,22 @@ def agg_split(ctx: CacheCtx, rows: torch.Tensor, count: int, tier: torch.Tensor,
 
 # ---- dense model -------------------------------------------------------------------------------------
 
+IA_NARROW_F = 32          # features one 32x32 Gram tile holds; 33 .. 64 go to the wide kernels (csrc/interact_wide.hip)
+
+
 def interact_fwd(feat: torch.Tensor, itself: bool, R: torch.Tensor, stream=None):
     B, F, D = feat.shape
-    check(_lib.lib().cdlrm_interact_fwd(feat.data_ptr(), B, F, D, int(bool(itself)), R.data_ptr(), R.stride(0),
-                                        stream_ptr(stream)))
+    fn = _lib.lib().cdlrm_interact_wide_fwd if F > IA_NARROW_F else _lib.lib().cdlrm_interact_fwd
+    check(fn(feat.data_ptr(), B, F, D, int(bool(itself)), R.data_ptr(), R.stride(0), stream_ptr(stream)))
 
 
 def interact_bwd(feat: torch.Tensor, dR: torch.Tensor, itself: bool, dfeat: torch.Tensor, stream=None, x_act: int = 0):
     """x_act: activation that produced feature 0 (the bottom MLP's output); its gradient row then leaves as the
     pre-activation gradient."""
     B, F, D = feat.shape
-    check(_lib.lib().cdlrm_interact_bwd(feat.data_ptr(), dR.data_ptr(), dR.stride(0), B, F, D, int(bool(itself)),
-                                        int(x_act), dfeat.data_ptr(), stream_ptr(stream)))
+    fn = _lib.lib().cdlrm_interact_wide_bwd if F > IA_NARROW_F else _lib.lib().cdlrm_interact_bwd
+    check(fn(feat.data_ptr(), dR.data_ptr(), dR.stride(0), B, F, D, int(bool(itself)), int(x_act), dfeat.data_ptr(),
+             stream_ptr(stream)))
 
 
 def gather_interact_supported(ctx: CacheCtx) -> bool:
@@ -773,7 +777,7 @@ def qr_interact_grid(op: int, B: int, D: int):
 
 
 IA_OPS = {"fwd": 0, "bwd": 1, "gather_fwd": 2, "gather_bwd": 3, "gather_bwd_sgd": 4}
-IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db"}
+IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db", 5: "wide_slab", 6: "wide_row"}
 
 
 def interact_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, aligned_r: bool = True,
@@ -785,6 +789,16 @@ def interact_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, ali
     out = _lib.InteractRoute()
     check(_lib.raw().cdlrm_interact_route(IA_OPS[op], int(B), int(F), int(D), int(bool(itself)), int(ld_r),
                                           int(bool(aligned_r)) | int(bool(aligned_dfeat)) << 1, C.byref(out)))
+    return {"family": IA_FAMILIES[out.family], "d4": out.d4, "ns": out.ns, "grid": out.grid, "lds_bytes": out.lds_bytes}
+
+
+def interact_wide_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, aligned_r: bool = True,
+                        aligned_dfeat: bool = True) -> dict:
+    """interact_route for the calls interact_fwd / interact_bwd make at 32 < F <= 64 (op "fwd" / "bwd"): family "wide_slab" (the
+    pipelined kernels) or "wide_row".  A shape those calls refuse raises their error.  No device is touched."""
+    out = _lib.InteractRoute()
+    check(_lib.raw().cdlrm_interact_wide_route(IA_OPS[op], int(B), int(F), int(D), int(bool(itself)), int(ld_r),
+                                               int(bool(aligned_r)) | int(bool(aligned_dfeat)) << 1, C.byref(out)))
     return {"family": IA_FAMILIES[out.family], "d4": out.d4, "ns": out.ns, "grid": out.grid, "lds_bytes": out.lds_bytes}
 
 

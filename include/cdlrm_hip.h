@@ -591,6 +591,8 @@ int cdlrm_qr_interact_grid(int32_t op, int64_t B, int32_t D, int64_t* grid, int6
 #define CDLRM_IA_ROW 2          /* k_interact_fwd_p / _bwd_p<d4>: software-pipelined, the sample's whole rows staged */
 #define CDLRM_IA_SLAB 3         /* k_interact_fwd_s / _bwd_s<d4, ns, gather>: column slabs of D / ns columns */
 #define CDLRM_IA_SLAB_DB 4      /* k_interact_fwd_s<d4, ns, true, true>: the slab slice double-buffered */
+#define CDLRM_IA_WIDE_SLAB 5    /* k_interact_wide_fwd / _bwd<d4> (32 < F <= 64): 32-column slabs, a register ring of loads */
+#define CDLRM_IA_WIDE_ROW 6     /* k_interact_wide_fwd_row / _bwd_row (32 < F <= 64): any D, the sample's whole rows staged */
 #define CDLRM_IA_OP_FWD 0               /* cdlrm_interact_fwd */
 #define CDLRM_IA_OP_BWD 1               /* cdlrm_interact_bwd */
 #define CDLRM_IA_OP_GATHER_FWD 2        /* cdlrm_gather_interact_fwd */
@@ -610,6 +612,20 @@ struct cdlrm_interact_route {   /* (a struct tag: the query below has the name) 
  * error.  No device is touched. */
 int cdlrm_interact_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r, int32_t aligned,
                          struct cdlrm_interact_route* out);
+/* interact_features "dot" for 33 to 64 features (F = T + 1, 32 <= T <= 63): the operands, layouts and results of
+ * cdlrm_interact_fwd / cdlrm_interact_bwd, on kernels that hold one sample's 64 x 64 Gram matrix (csrc/interact_wide.hip).
+ * D % 4 == 0, D <= 512, feat 16-byte aligned, ld_r >= D + the number of pairs; D in 32 / 64 / 128 / 256 with whole-float4 R / dR
+ * rows (and a 16-byte aligned dfeat) runs the pipelined kernels, everything else the whole-row ones, which need
+ * 16 * (64 * (D + 1) + 32) bytes of LDS (+ the pair gradients in the backward) inside 160 KiB.  F <= 32 is refused: that is
+ * cdlrm_interact_fwd / _bwd.  cdlrm_interact_wide_bwd carries an attached completion event like cdlrm_interact_bwd. */
+int cdlrm_interact_wide_fwd(const float* feat, int64_t B, int32_t F, int32_t D, int32_t itself,
+                            float* R, int64_t ld_r, void* stream);
+int cdlrm_interact_wide_bwd(const float* feat, const float* dR, int64_t ld_r, int64_t B, int32_t F,
+                            int32_t D, int32_t itself, int32_t x_act, float* dfeat, void* stream);
+/* cdlrm_interact_route for the two calls above: op CDLRM_IA_OP_FWD / CDLRM_IA_OP_BWD; family CDLRM_IA_WIDE_*.  A shape the
+ * entry point refuses is refused here with its error.  No device is touched. */
+int cdlrm_interact_wide_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r, int32_t aligned,
+                              struct cdlrm_interact_route* out);
 /* Linear + activation (create_mlp, model_no_ddp.py:244-270): Y = act(X W^T + b).
  * X [M, K] ld_x, W [N, K] row-major (nn.Linear.weight), Y [M, N] ld_y. act: 0 none, 1 ReLU, 2 sigmoid. */
 /* CDLRM_GEMM_ALONE, or-ed into `act` of cdlrm_linear_fwd / cdlrm_linear_bwd: the caller's promise that no other GEMM runs beside
