@@ -30,6 +30,8 @@ __host__ __device__ constexpr int iw_grad_row(int D4) { return 4 * D4 + 2080; }
 __host__ __device__ constexpr int iw_out_row(int D4) { return 4 * D4 + 2084; }
 __host__ __device__ constexpr int iw_fwd_floats(int D4) { return iw_slab_slice() + iw_out_row(D4); }
 __host__ __device__ constexpr int iw_bwd_floats(int D4) { return iw_slab_slice() + iw_grad_row(D4); }
+// The gather variants of the pipelined pair keep the row offsets of one sample (64 words) behind the wave's slice.
+__host__ __device__ constexpr int iw_gather_table() { return 64; }
 __host__ __device__ constexpr int iw_row_tile(int D) { return 64 * (D + 1) + 32; }
 __host__ __device__ constexpr int iw_row_bwd_floats(int D, int npairs) { return iw_row_tile(D) + ((npairs + 3) & ~3); }
 

@@ -23,10 +23,14 @@
 //
 //   whole-row (any D % 4 == 0 that fits the LDS budget; unaligned R / dR / dfeat, a pitch without whole words): the [64][D + 1]
 //   form of k_interact_fwd / k_interact_bwd, scalar LDS reads, outputs stored straight from the accumulator lanes.
+//
+// The pipelined pair also runs as the fused gather (cdlrm_gather_interact_wide_fwd / _bwd): the same kernels with
+// the ring's source switched (IwRing<D4, G>), the rows read from the cache by slot id.
 #include "interact_lds.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef int v4i __attribute__((ext_vector_type(4)));
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 #define IW_PITCH 36         // floats per slice row: 32 columns + 4 (an odd multiple of 16 B: conflict-free b128 writes and reads)
@@ -41,15 +45,48 @@ __device__ __forceinline__ void iw_each_slab(std::integer_sequence<int, S...>, F
     (fn(std::integral_constant<int, S>{}), ...);
 }
 
+// G (the fused gather, cdlrm_gather_interact_wide_fwd / _bwd): row 0 of a sample's block is the dense feature
+// x[b] (pitch ldx4 words), rows 1 .. F - 1 are the cache rows weight[tab[t].row_base + slots[t * n + b]], t = row - 1 -- the
+// [B, T, D] block cdlrm_embbag_fwd would write and the kernels above read back never exists.  Same operands in the same lanes,
+// same MFMA order: bit-identical to gather + interaction.
+struct IwGather {
+    const TableDesc* tab;       // row_base of every table's cache rows
+    const v4f* weight;          // cache rows (and the auxiliary rows behind them), D4 float4 words each; fewer than 2^31 words
+    const int32_t* slots;       // [T, n] slot ids of the batch (T * n < 2^31, checked by the host)
+    int n;
+    int64_t ldx4;               // pitch of the dense-feature rows, float4 words
+};
+
 // the register ring of both pipelined kernels: lane = (row lane / 8 + 8 i, word lane % 8) of a slab, i < 8
-template <int D4>
+//
+// G: soff[] holds, per register, the float4 words from `weight` to the row's start -- of ONE sample at a time.  The ring walks
+// across the sample boundary, so the addresses of the wave's next sample must be in registers before this sample's last refills
+// (NS <= RD: before its first), and slot id -> address -> row is a dependent chain of two memory round trips.  It is taken apart
+// over three samples: lane r loads the slot id of row r (clamped to 1 .. F - 1) of the sample a whole sample before it is
+// needed (fetch_ids, one register), turns it into a word offset and posts it into the wave's 64-word LDS table at the head of
+// the next sample (post_ids), and behind the last refill that still needs the old addresses every lane takes the offsets of its
+// eight rows out of the table with two ds_read_b128 (take_offsets; the table is ordered [lane / 8][i]) -- in front of a slab's
+// MFMAs, which hide the LDS round trip.  No load ever waits for an address.  The table needs no second buffer (the register
+// holds the sample in between) and no barrier (each wave owns its table; a wave's LDS operations complete in order).
+template <int D4, bool G = false>
 struct IwRing {
     static constexpr int NS = D4 / 8, RD = NS >= 2 ? 2 : 1;
+    // G: at the head of the wave's k-th sample soff[] holds the offsets of sample k + LA - 1 and `sid` the slot ids of sample
+    // k + LA.  NS > RD: the first NS - RD refills still read this sample, the offsets of the next are taken behind the last of
+    // them.  NS <= RD: every refill reads the next sample, the offsets of the one after it are taken behind the last refill.
+    static constexpr int LA = NS > RD ? 1 : 2, TAKE = NS > RD ? NS - RD - 1 : NS - 1;
     v4f v[RD][IW_NR];
     int soff[IW_NR];        // float4 words from the sample's start to this lane's word of slab 0; the row clamped to F - 1
     int doff;               // where register 0 goes in the slice; register i is 8 rows further down
-    const v4f* feat4;
+    const v4f* feat4;       // G: word lane % 8 of x[0]
     int FD4;
+    const v4f* w4;          // G: word lane % 8 of weight[0]
+    int64_t ldx4;
+    const int32_t* slots;
+    int srow, rbase, sid;   // lane r: where its table's slot ids start, row_base * D4 of that table, the id in flight
+    int* tpost;             // this lane's word of the table (row r at [r % 8][r / 8])
+    const v4i* ttake;       // the eight offsets of rows lane / 8 + 8 i
+    bool row0;              // register 0 of this lane is the dense feature
 
     __device__ __forceinline__ void init(const float* feat, int F, int lane) {
         feat4 = reinterpret_cast<const v4f*>(feat);
@@ -58,11 +95,62 @@ struct IwRing {
         for (int i = 0; i < IW_NR; ++i) soff[i] = min((lane >> 3) + 8 * i, F - 1) * D4 + (lane & 7);
         doff = (lane >> 3) * IW_PITCH + 4 * (lane & 7);
     }
+    __device__ __forceinline__ void init(const float* x, const IwGather& ga, int F, int lane, float* table) {
+        feat4 = reinterpret_cast<const v4f*>(x) + (lane & 7);
+        w4 = ga.weight + (lane & 7);
+        ldx4 = ga.ldx4;
+        slots = ga.slots;
+        const int t = min(max(lane, 1), F - 1) - 1;        // rows F .. 63 repeat row F - 1; row 0's word is never used
+        srow = t * ga.n;
+        rbase = (int)ga.tab[t].row_base * D4;
+        tpost = reinterpret_cast<int*>(table) + (lane & 7) * 8 + (lane >> 3);
+        ttake = reinterpret_cast<const v4i*>(table) + (lane >> 3) * 2;
+        row0 = lane < 8;
+        doff = (lane >> 3) * IW_PITCH + 4 * (lane & 7);
+    }
+    __device__ __forceinline__ void fetch_ids(int64_t b) { sid = slots[srow + b]; }
+    __device__ __forceinline__ void post_ids() { *tpost = rbase + sid * D4; }
+    __device__ __forceinline__ void take_offsets() {
+        const v4i lo = ttake[0], hi = ttake[1];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            soff[i] = lo[i];
+            soff[4 + i] = hi[i];
+        }
+    }
     template <int SLOT>
     __device__ __forceinline__ void load(int s, int64_t b) {
+        if constexpr (G) {      // (soff[] must be sample b's)
+#pragma unroll
+            for (int i = 0; i < IW_NR; ++i) {
+                const v4f* src = w4 + (uint32_t)soff[i];
+                if (i == 0) src = row0 ? feat4 + b * ldx4 : src;
+                v[SLOT][i] = src[s * 8];
+            }
+            return;
+        }
         const v4f* src = feat4 + b * FD4 + s * 8;
 #pragma unroll
         for (int i = 0; i < IW_NR; ++i) v[SLOT][i] = src[soff[i]];
+    }
+    // G: the first sample's addresses and rows, the chain exposed once; leaves the registers as the head of a sample finds them
+    __device__ __forceinline__ void prime(int64_t b, int64_t nw, int64_t B) {
+        fetch_ids(b);
+        post_ids();
+        take_offsets();
+        load<0>(0, b);
+        if constexpr (RD == 2) load<1>(1, b);
+        if constexpr (LA == 2) {
+            fetch_ids(min(b + nw, B - 1));
+            post_ids();
+            take_offsets();
+        }
+        fetch_ids(min(b + LA * nw, B - 1));
+    }
+    // G, at the head of sample b: the ids fetched a sample ago become offsets in the table, the ids of the sample after go out
+    __device__ __forceinline__ void advance(int64_t b, int64_t nw, int64_t B) {
+        post_ids();
+        fetch_ids(min(b + (LA + 1) * nw, B - 1));
     }
     template <int SLOT>
     __device__ __forceinline__ void stage(float* __restrict__ Ts) const {
@@ -74,17 +162,21 @@ struct IwRing {
     __device__ __forceinline__ void refill(int64_t b, int64_t bn) {
         if constexpr (S + RD < NS) load<S % RD>(S + RD, b);
         else load<S % RD>(S + RD - NS, bn);
+        if constexpr (G && S == TAKE) take_offsets();       // (the refills behind slab TAKE read another sample than this one)
     }
 };
 
-template <int D4>
-__global__ void __launch_bounds__(256, 2) k_interact_wide_fwd(const float* __restrict__ feat, int64_t B, int F, int itself,
-                                                              float* __restrict__ R, int64_t ld_r) {
-    using Ring = IwRing<D4>;
+// G = false: feat is the [B, F, D] block, ga is not read.  G (cdlrm_gather_interact_wide_fwd): feat is x, the rows come through
+// ga.  One body; the ring alone knows the difference.
+template <int D4, bool G = false>
+__global__ void __launch_bounds__(256, 2) k_interact_wide_fwd(const float* __restrict__ feat, IwGather ga, int64_t B, int F,
+                                                              int itself, float* __restrict__ R, int64_t ld_r) {
+    using Ring = IwRing<D4, G>;
     constexpr int D = 4 * D4, NS = Ring::NS, RD = Ring::RD;
+    constexpr int WF = iw_fwd_floats(D4) + (G ? iw_gather_table() : 0);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* Ts = smem + wave * iw_fwd_floats(D4);
+    float* Ts = smem + wave * WF;
     float* Os = Ts + iw_slab_slice();           // the output row [dense D | pairs | pad word]
     const int64_t nw = (int64_t)gridDim.x * 4;
     int64_t b = (int64_t)blockIdx.x * 4 + wave;
@@ -93,9 +185,14 @@ __global__ void __launch_bounds__(256, 2) k_interact_wide_fwd(const float* __res
     const int off = itself ? 1 : 0;
     const int width = D + pair_base(F, itself), W4 = (width + 3) >> 2;
     Ring ring;
-    ring.init(feat, F, lane);
-    ring.template load<0>(0, b);
-    if constexpr (RD == 2) ring.template load<1>(1, b);
+    if constexpr (G) {
+        ring.init(feat, ga, F, lane, Ts + iw_fwd_floats(D4));
+        ring.prime(b, nw, B);
+    } else {
+        ring.init(feat, F, lane);
+        ring.template load<0>(0, b);
+        if constexpr (RD == 2) ring.template load<1>(1, b);
+    }
     const float* tp = Ts + lr * IW_PITCH + 4 * lk;      // lane half lk: contraction indices 8 g + 4 lk .. + 3 of a group
     auto slab = [&](auto s_, int64_t b, int64_t bn, f32x16& a00, f32x16& a10, f32x16& a11) __attribute__((always_inline)) {
         constexpr int S = decltype(s_)::value;
@@ -126,6 +223,7 @@ __global__ void __launch_bounds__(256, 2) k_interact_wide_fwd(const float* __res
     };
     auto one = [&](int64_t b) __attribute__((always_inline)) {
         const int64_t bn = min(b + nw, B - 1);
+        if constexpr (G) ring.advance(b, nw, B);
         f32x16 a00, a10, a11;
 #pragma unroll
         for (int r = 0; r < 16; ++r) a00[r] = a10[r] = a11[r] = 0.f;
@@ -154,18 +252,21 @@ __global__ void __launch_bounds__(256, 2) k_interact_wide_fwd(const float* __res
 
 // One wave per SIMD: beside 64 fragment and 32 accumulator registers the ring and the next sample's dR row (NG float4) do not fit
 // a half register file -- bounded to two waves per SIMD every instance spills (124 to 632 bytes per lane).
-template <int D4>
-__global__ void __launch_bounds__(256, 1) k_interact_wide_bwd(const float* __restrict__ feat,
+// G (cdlrm_gather_interact_wide_bwd): as in the forward kernel; the rows are read again from the cache, so the launch goes in
+// front of the batch's embedding update.
+template <int D4, bool G = false>
+__global__ void __launch_bounds__(256, 1) k_interact_wide_bwd(const float* __restrict__ feat, IwGather ga,
                                                         const float* __restrict__ dR, int64_t ld_r, int64_t B, int F,
                                                         int itself, int x_act, float* __restrict__ dfeat) {
-    using Ring = IwRing<D4>;
+    using Ring = IwRing<D4, G>;
     constexpr int D = 4 * D4, NS = Ring::NS, RD = Ring::RD;
     constexpr int GMAX = iw_grad_row(D4);       // dense part + up to 64 * 65 / 2 pair gradients
     constexpr int NG = (GMAX / 4 + 63) / 64;
+    constexpr int WF = iw_bwd_floats(D4) + (G ? iw_gather_table() : 0);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int lr = lane & 31, lk = lane >> 5;
-    float* Ts = smem + wave * iw_bwd_floats(D4);
+    float* Ts = smem + wave * WF;
     float* Gs = Ts + iw_slab_slice();
     float* Os = Gs + D;                         // [16][32] output staging: the pair part of the dR row (>= 528 floats), dead once S is built
     const int npairs = pair_base(F, itself);
@@ -174,12 +275,17 @@ __global__ void __launch_bounds__(256, 1) k_interact_wide_bwd(const float* __res
     int64_t b = (int64_t)blockIdx.x * 4 + wave;
     if (b >= B) return;
     Ring ring;
-    ring.init(feat, F, lane);
+    if constexpr (G) ring.init(feat, ga, F, lane, Ts + iw_bwd_floats(D4));
+    else ring.init(feat, F, lane);
     v4f gn[NG];
 #pragma unroll
     for (int i = 0; i < NG; ++i) gn[i] = reinterpret_cast<const v4f*>(dR + b * ld_r)[min(lane + 64 * i, G4 - 1)];
-    ring.template load<0>(0, b);
-    if constexpr (RD == 2) ring.template load<1>(1, b);
+    if constexpr (G) {
+        ring.prime(b, nw, B);
+    } else {
+        ring.template load<0>(0, b);
+        if constexpr (RD == 2) ring.template load<1>(1, b);
+    }
     const float* tp = Ts + lk * IW_PITCH + lr;
     auto slab = [&](auto s_, int64_t b, int64_t bn, const float (&sreg)[2][32]) __attribute__((always_inline)) {
         constexpr int S = decltype(s_)::value;
@@ -220,6 +326,7 @@ __global__ void __launch_bounds__(256, 1) k_interact_wide_bwd(const float* __res
     };
     auto one = [&](int64_t b) __attribute__((always_inline)) {
         const int64_t bn = min(b + nw, B - 1);
+        if constexpr (G) ring.advance(b, nw, B);
 #pragma unroll
         for (int i = 0; i < NG; ++i) *reinterpret_cast<v4f*>(Gs + 4 * min(lane + 64 * i, GMAX / 4 - 1)) = gn[i];
 #pragma unroll
@@ -406,7 +513,7 @@ extern "C" int cdlrm_interact_wide_fwd(const float* feat, int64_t B, int32_t F, 
     if (B == 0) return 0;
     if (p.family == CDLRM_IA_WIDE_SLAB)
         return ia_with_d4(p.d4, [&](auto d4) {
-            return ia_launch<k_interact_wide_fwd<decltype(d4)::value>>(p, stream, false, feat, B, F, itself, R, ld_r);
+            return ia_launch<k_interact_wide_fwd<decltype(d4)::value>>(p, stream, false, feat, IwGather{}, B, F, itself, R, ld_r);
         });
     return ia_launch<k_interact_wide_fwd_row>(p, stream, false, feat, B, F, D, itself, R, ld_r);
 }
@@ -421,7 +528,7 @@ extern "C" int cdlrm_interact_wide_bwd(const float* feat, const float* dR, int64
     if (B == 0) return 0;
     if (p.family == CDLRM_IA_WIDE_SLAB)
         return ia_with_d4(p.d4, [&](auto d4) {
-            return ia_launch<k_interact_wide_bwd<decltype(d4)::value>>(p, stream, true, feat, dR, ld_r, B, F, itself, x_act, dfeat);
+            return ia_launch<k_interact_wide_bwd<decltype(d4)::value>>(p, stream, true, feat, IwGather{}, dR, ld_r, B, F, itself, x_act, dfeat);
         });
     return ia_launch<k_interact_wide_bwd_row>(p, stream, true, feat, dR, ld_r, B, F, D, itself, x_act, dfeat);
 }
@@ -436,4 +543,90 @@ extern "C" int cdlrm_interact_wide_route(int32_t op, int64_t B, int32_t F, int32
     out->family = p.family; out->d4 = p.d4; out->ns = p.ns; out->reserved = 0;
     out->grid = p.grid; out->lds_bytes = (int64_t)p.lds;
     return 0;
+}
+
+// ---- fused gather + interaction at 33 to 64 features (Criteo layout: one index per bag, so a bag's sum-pool is its cache row) ----
+// cached EmbeddingBag forward (model_no_ddp.py:200-203) + interact_features "dot" (:272-293) in one launch, and the interaction
+// backward reading the same rows again.  The pipelined family only: D in 32 / 64 / 128 / 256, whole-float4 R / dR rows, aligned dfeat.
+// The plan of both launches and of the query: wide_plan's grid for an aligned call, the offset table behind every wave's slice.
+// family 0: no kernel -- F outside 33 .. 64, another D, or a cache whose rows a 32-bit float4-word offset cannot name.
+static IwPlan gather_wide_plan(int op, int64_t B, const cdlrm_ctx* ctx) {
+    const int F = ctx->T + 1, D = ctx->D;
+    if (!(F > 32 && F <= 64 && (D == 32 || D == 64 || D == 128 || D == 256) && ctx->total_rows * (D / 4) < INT32_MAX)) return IwPlan{};
+    IwPlan p = wide_plan(op, B, F, D, 1, (IW_WIDTH(F, D, 1) + 3) & ~3, true, true);     // (whole-float4 rows: the pipelined family)
+    p.lds += (size_t)4 * iw_gather_table() * sizeof(float);
+    return p;
+}
+
+extern "C" int cdlrm_gather_interact_wide_supported(cdlrm_ctx* ctx) {
+    return ctx && gather_wide_plan(CDLRM_IA_OP_FWD, 1, ctx).family ? 1 : 0;
+}
+
+extern "C" int cdlrm_gather_interact_wide_grid(cdlrm_ctx* ctx, int32_t op, int64_t B, int64_t* grid, int64_t* lds_bytes) {
+    CDLRM_REQUIRE(ctx && grid && lds_bytes && (op == CDLRM_IA_OP_FWD || op == CDLRM_IA_OP_BWD) && B >= 0, "bad argument");
+    const IwPlan p = gather_wide_plan(op, B, ctx);
+    CDLRM_REQUIRE(p.family, "unsupported shape (D in 32/64/128/256, 32 < T + 1 <= 64, cache rows * D / 4 < 2^31)");
+    *grid = p.grid;
+    *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+// what both entry points ask of the slots, the dense feature and the R / dR rows (the checks of cdlrm_gather_interact_fwd / _bwd)
+static int gather_wide_check(const cdlrm_ctx* ctx, const IwPlan& p, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
+                             const float* r, int64_t ld_r, int64_t B, int32_t itself) {
+    CDLRM_REQUIRE(p.family, "unsupported shape (D in 32/64/128/256, 32 < T + 1 <= 64, cache rows * D / 4 < 2^31): gather + interaction as two calls");
+    CDLRM_REQUIRE(B >= 0 && n >= B && (int64_t)ctx->T * n < INT32_MAX && aligned16(x) && ld_x % 4 == 0 && ld_x >= ctx->D,
+                  "slot pitch / dense-feature rows");
+    const int width = IW_WIDTH(ctx->T + 1, ctx->D, itself);
+    CDLRM_REQUIRE(ld_r % 4 == 0 && aligned16(r) && ld_r >= ((width + 3) & ~3), "whole-float4 rows of R / dR (ld_r)");
+    return 0;
+}
+
+extern "C" int cdlrm_gather_interact_wide_fwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
+                                              int64_t B, int32_t itself, float* R, int64_t ld_r, void* stream) {
+    CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
+    CDLRM_CLEAR_STALE();
+    CDLRM_REQUIRE(ctx && slots && x && R, "null argument");
+    CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
+    const IwPlan p = gather_wide_plan(CDLRM_IA_OP_FWD, B, ctx);
+    const int rc = gather_wide_check(ctx, p, slots, n, x, ld_x, R, ld_r, B, itself);
+    if (rc) return rc;
+    if (B == 0) return 0;       // (an armed event pair stays armed for the next launch that can carry it)
+    // a timed pair (cdlrm_ctx_time_next_gather) and an attached completion event, as cdlrm_gather_interact_fwd carries them
+    hipEvent_t ev0 = (hipEvent_t)ctx->ev_start, ev1 = (hipEvent_t)ctx->ev_stop;
+    ctx->ev_start = ctx->ev_stop = nullptr;
+    hipEvent_t se = cdlrm_take_stop_event((hipStream_t)stream);
+    if (!ev1 && se) { ev1 = se; se = nullptr; }
+    const IwGather ga{ctx->d_tab, reinterpret_cast<const v4f*>(ctx->weight), slots, (int)n, ld_x / 4};
+    const int F = ctx->T + 1;
+    const int rl = ia_with_d4(p.d4, [&](auto d4) {
+        constexpr auto kernel = k_interact_wide_fwd<decltype(d4)::value, true>;
+        const int rg = cdlrm_grant_dynamic_lds<kernel>(p.lds);
+        if (rg) return rg;
+        hipExtLaunchKernelGGL(kernel, dim3((unsigned)p.grid), dim3(256), p.lds, (hipStream_t)stream, ev0, ev1, 0, x, ga, B, F, itself,
+                              R, ld_r);
+        return 0;
+    });
+    if (rl) return rl;
+    if (se) CDLRM_HIP_CHECK(hipEventRecord(se, (hipStream_t)stream));
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cdlrm_gather_interact_wide_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
+                                              const float* dR, int64_t ld_r, int64_t B, int32_t itself, int32_t x_act,
+                                              float* dfeat, void* stream) {
+    CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
+    CDLRM_REQUIRE(ctx && slots && x && dR && dfeat, "null argument");
+    CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
+    const IwPlan p = gather_wide_plan(CDLRM_IA_OP_BWD, B, ctx);
+    const int rc = gather_wide_check(ctx, p, slots, n, x, ld_x, dR, ld_r, B, itself);
+    if (rc) return rc;
+    CDLRM_REQUIRE(aligned16(dfeat), "whole-float4 gradient rows (dfeat)");
+    if (B == 0) return 0;
+    const IwGather ga{ctx->d_tab, reinterpret_cast<const v4f*>(ctx->weight), slots, (int)n, ld_x / 4};
+    const int F = ctx->T + 1;
+    return ia_with_d4(p.d4, [&](auto d4) {
+        return ia_launch<k_interact_wide_bwd<decltype(d4)::value, true>>(p, stream, true, x, ga, dR, ld_r, B, F, itself, x_act, dfeat);
+    });
 }

@@ -717,6 +717,7 @@ class StepPath(NamedTuple):
     lr: float
     lr_embeds: float
     lr_cells: bool = False          # the rate arguments are the engine's two rate cells, not literals
+    gather_wide: bool = False       # `fused` on the wide pair (cdlrm_gather_interact_wide_fwd / _bwd)
     embed_optimizer: str = "sgd"    # the cache rows' update: "sgd" or "rowwise_adagrad" 
     adagrad_eps: float = 0.0
     dense_optimizer: str = "sgd"    # the MLP parameters' update: "sgd" or "adagrad" 
@@ -1478,6 +1479,11 @@ class TrainEngine:
         # (--qr-fuse-gather): bit-identical, measured stand-alone only (tools/qr_interact_time.py), and existing
         # tests pin the default QR launch sequence
         self.fuse_qr = False
+        # 32 to 63 tables: the same fusion on the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd) instead of
+        # cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd on a materialised block.  Opt-in (--fuse-gather-wide): bit-identical,
+        # measured stand-alone only (tools/gather_interact_wide_time.py), and existing tests pin the default
+        # launch sequence at 32 and 63 tables.  No once-only fold there: the sorted embedding backward does every slot
+        self.fuse_gather_wide = False
         # (Where the sort of a batch's own slot ids and the top MLP's weight gradients start, the fold of the top-update wait
         #  and the take schedules were measured as knobs, rounds 1-6, and the losers removed: DESIGN_HISTORY.md.)
         # WindowResolver hands the NEXT step a look-ahead chunk to resolve (`_pending_resolve`, taken when `mark_next` is set): the
@@ -1747,7 +1753,13 @@ class TrainEngine:
             return bool(self.fuse_bags and not self.cat and S.is_hip(self.dev) and self.qr is None
                         and ops.bag_interact_supported(self.ctx))
         return bool(self.fuse_gather and not self.cat and S.is_hip(self.dev) and self.qr is None
-                    and ops.gather_interact_supported(self.ctx))
+                    and ops.gather_interact_supported(self.ctx)) or self._gather_wide(lS_o)
+
+    def _gather_wide(self, lS_o) -> bool:
+        """One index per bag at 32 to 63 tables, opted in (fuse_gather_wide): the gather rides in the wide interaction kernels.
+        Multi-hot bags and quotient-remainder tables stay on two operators there."""
+        return bool(self.fuse_gather_wide and lS_o is None and self.qr is None and not self.cat and S.is_hip(self.dev)
+                    and self.F > ops.IA_NARROW_F and ops.gather_interact_wide_supported(self.ctx))
 
     def _side_gather(self, B: int) -> bool:
         """Short local batches run the gather on the side stream (see _fwd_bwd)."""
@@ -1779,6 +1791,7 @@ class TrainEngine:
         chain = self._chain(B, next_idx, lS_o)
         two_phase = self.ctx.aux_phases >= 2 and not chain
         fused = self._fused_gather(lS_o)
+        gather_wide = fused and self._gather_wide(lS_o)     # (the wide pair has no once-only fold: `once` stays off)
         # this batch's slot lists were sorted with its look-ahead chunk (WindowResolver.ensure_sorted): no sort in the step, and
         # the once-only slots can be updated by the interaction backward (it reads the sort's flags)
         # (the flags of a batch's OWN sort would cost the training queue a wait for the side stream in front of the interaction
@@ -1806,7 +1819,7 @@ class TrainEngine:
             gather_alone=B >= self.gather_alone_min, fused=fused, sorted=None if sv is None else sv.stride,
             # (row-wise Adagrad: the once-only fold is an SGD step -- the sorted apply takes every slot)
             # (quotient-remainder mode: the gradient rows are rewritten by cdlrm_qr_cached_bwd first -- no fold)
-            once=bool(self.fuse_once and fused and sv is not None and self.embed_optimizer == "sgd" and self.qr is None), next_sorted=self._next_sorted is not None,
+            once=bool(self.fuse_once and fused and not gather_wide and sv is not None and self.embed_optimizer == "sgd" and self.qr is None), next_sorted=self._next_sorted is not None,
             chain_sort=chain and self._next_sorted is None, chained_top=chain and self.defer_top and not self.multi,
             next_bufs=(1 - phase) if two_phase else 2 + (self.iter & 1), emb_done_seen=self._emb_done is not None,
             timed=self._gslot is not None, loss_sync=self.loss_sync, resolve_cols=None if pr is None else int(pr["cols"].shape[1]),
@@ -1815,7 +1828,8 @@ class TrainEngine:
             matmul_precision=self.matmul_precision, lr=self.lr, lr_embeds=self.lr_embeds,
             embed_optimizer=self.embed_optimizer, adagrad_eps=self.adagrad_eps if self.embed_optimizer != "sgd" else 0.0,
             dense_optimizer=self.dense_optimizer,
-            dense_adagrad_eps=self.dense_adagrad_eps if self.dense_optimizer != "sgd" else 0.0, lr_cells=bool(self.lr_cells))
+            dense_adagrad_eps=self.dense_adagrad_eps if self.dense_optimizer != "sgd" else 0.0, lr_cells=bool(self.lr_cells),
+            gather_wide=gather_wide)
 
     def _take(self, idx, res, phase: int, which, st):
         """A batch's (slots, miss_pos, miss_count) into the probe buffers `which`, misses into aux region `phase`, on stream st:
@@ -2270,6 +2284,8 @@ class TrainEngine:
                 ops.qr_interact_fwd(ctx, slots, self._r, self.Wr, self.qr_coll, self.qr_op, feat[:, 0, :], self.itself, R)
             elif path.offsets:
                 ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R, n_bags=path.n_bags)
+            elif path.gather_wide:
+                ops.gather_interact_wide_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
             else:
                 ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         elif not self.cat:
@@ -2363,6 +2379,8 @@ class TrainEngine:
                                     x_act=self.bot[-1][1])
             elif fused and path.offsets:
                 ops.bag_interact_bwd(ctx, slots, lS_o, feat[:, 0, :], dR, self.itself, dfeat, n_bags=path.n_bags, x_act=self.bot[-1][1])
+            elif path.gather_wide:
+                ops.gather_interact_wide_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
             elif fused:
                 ops.gather_interact_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
             else:
@@ -2474,6 +2492,8 @@ class TrainEngine:
             ops.qr_interact_fwd(ctx, slots, r, self.Wr, self.qr_coll, self.qr_op, feat[:, 0, :], self.itself, R)
         elif self._fused_gather(lS_o) and lS_o is not None:
             ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R)
+        elif self._gather_wide(lS_o):
+            ops.gather_interact_wide_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         elif self._fused_gather(lS_o):
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         else:

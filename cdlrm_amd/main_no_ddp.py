@@ -97,6 +97,9 @@ def ProcessArgs(argv=None):
     # --qr-flag: the compose with the remainder rows inside the interaction kernels (cdlrm_qr_interact_fwd / _bwd) instead of
     # cdlrm_qr_cached_fwd + interaction
     parser.add_argument("--qr-fuse-gather", action="store_true", default=False)
+    # 32 to 63 tables, one index per bag: the gather inside the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd)
+    # instead of cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd
+    parser.add_argument("--fuse-gather-wide", action="store_true", default=False)
     # ---- debugging and profiling ----
     parser.add_argument("--print-freq", type=int, default=1)
     parser.add_argument("--test-freq", type=int, default=-1)
@@ -563,6 +566,15 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             print("Quotient-remainder steps: %s" % ("compose inside the interaction kernels (cdlrm_qr_interact_fwd / _bwd)"
                                                      if eng._fused_gather(None) else
                                                      "cdlrm_qr_cached_fwd + interaction as two operators (%s)" % why), flush=True)
+    if getattr(args, "fuse_gather_wide", False):
+        eng.fuse_gather_wide = True
+        if rank == 0:
+            why = ("--qr-flag" if eng.qr is not None else "--arch-interaction-op=cat" if eng.cat else
+                   "dot interaction, D in 32 / 64 / 128 / 256, 32 < tables + 1 <= 64, a cache of fewer than 2^31 float4 words")
+            print("One-index steps: %s" % ("gather inside the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd)"
+                                           if eng._gather_wide(None) else
+                                           "--fuse-gather-wide has no kernel for this model (%s): the route of a run without it" % why),
+                  flush=True)
     pipe = WindowPipeline(cache_group, emb_tables, L * aux_rows * 2, parity_rng=not args.device_rng,
                           seed=args.numpy_rand_seed, average_on_writeback=args.average_on_writeback, rank=rank,
                           world_size=world, host_gather=lookahead_plan,

@@ -696,6 +696,40 @@ def gather_interact_bwd_sgd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor,
                                                    dfeat.data_ptr(), int(once), int(ld_once), _rate(lr), stream_ptr(stream)))
 
 
+# ---- the fused gather at 33 to 64 features (csrc/interact_wide.hip) ----
+# Entry points of their own: gather_interact_fwd / _bwd keep refusing T + 1 > 32, the caller decides which pair a step issues.
+
+def gather_interact_wide_supported(ctx: CacheCtx) -> bool:
+    """Shapes the wide fused gather + interaction kernels take (D in 32 / 64 / 128 / 256, 32 < T + 1 <= 64, a cache of fewer
+    than 2^31 float4 words)."""
+    return bool(_lib.raw().cdlrm_gather_interact_wide_supported(ctx.handle))      # (a query: never on a step's tape)
+
+
+def gather_interact_wide_fwd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor, itself: bool, R: torch.Tensor, stream=None):
+    """gather_interact_fwd at 32 to 63 tables.  Bit-identical to embbag_fwd + interact_fwd."""
+    B = x.shape[0]
+    assert slots.dtype == torch.int32 and slots.stride(1) == 1 and x.stride(1) == 1
+    check(_lib.lib().cdlrm_gather_interact_wide_fwd(ctx.handle, slots.data_ptr(), slots.stride(0), x.data_ptr(), x.stride(0), B,
+                                                    int(bool(itself)), R.data_ptr(), R.stride(0), stream_ptr(stream)))
+
+
+def gather_interact_wide_bwd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor, dR: torch.Tensor, itself: bool,
+                             dfeat: torch.Tensor, stream=None, x_act: int = 0):
+    """gather_interact_bwd at 32 to 63 tables (before the batch's embedding update rewrites the rows)."""
+    B = x.shape[0]
+    assert slots.dtype == torch.int32 and slots.stride(1) == 1 and x.stride(1) == 1 and dfeat.is_contiguous()
+    check(_lib.lib().cdlrm_gather_interact_wide_bwd(ctx.handle, slots.data_ptr(), slots.stride(0), x.data_ptr(), x.stride(0),
+                                                    dR.data_ptr(), dR.stride(0), B, int(bool(itself)), int(x_act),
+                                                    dfeat.data_ptr(), stream_ptr(stream)))
+
+
+def gather_interact_wide_grid(ctx: CacheCtx, op: str, B: int):
+    """(workgroups, dynamic LDS bytes) of a gather_interact_wide_fwd (op "fwd") / _bwd ("bwd") launch.  No device is touched."""
+    grid, lds = C.c_int64(), C.c_int64()
+    check(_lib.raw().cdlrm_gather_interact_wide_grid(ctx.handle, IA_OPS[op], int(B), C.byref(grid), C.byref(lds)))
+    return grid.value, lds.value
+
+
 # ---- multi-hot bags pooled inside the interaction kernels (csrc/bag_interact.hip, DESIGN.md 4.8) ----
 
 BAG_INTERACT_U = 4      # CDLRM_BAG_INTERACT_U: lookups of one bag whose rows a lane has in flight at a time (D = 256: half)

@@ -626,6 +626,25 @@ int cdlrm_interact_wide_bwd(const float* feat, const float* dR, int64_t ld_r, in
  * entry point refuses is refused here with its error.  No device is touched. */
 int cdlrm_interact_wide_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r, int32_t aligned,
                               struct cdlrm_interact_route* out);
+/* Cached EmbeddingBag forward + interact_features "dot" in ONE launch (model_no_ddp.py:200-203 + :272-293) for 32 to 63 tables:
+ * cdlrm_gather_interact_fwd / _bwd on the pipelined kernels of csrc/interact_wide.hip, with the same arguments, the same checks
+ * (n >= B, T * n < 2^31, 16-byte aligned x with ld_x % 4 == 0, whole-float4 R / dR rows, 16-byte aligned dfeat) and the same
+ * results -- bit-identical to cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd; the [B, T, D] block between them is never
+ * written or read back.  Shapes: cdlrm_gather_interact_wide_supported() -- D in 32 / 64 / 128 / 256, 32 < T + 1 <= 64, and a
+ * cache of fewer than 2^31 float4 words (total rows * D / 4: the kernels address the rows by 32-bit word offsets); anything else
+ * is refused -- the caller issues the two operators.  The forward carries a timed pair (cdlrm_ctx_time_next_gather) and an
+ * attached completion event like cdlrm_gather_interact_fwd.  The backward (main_no_ddp.py:376 through :272-293) reads the rows
+ * again from the cache -- call it BEFORE the batch's embedding update --, writes dfeat [B, T + 1, D] as cdlrm_interact_wide_bwd
+ * does and carries an attached completion event like cdlrm_interact_bwd.  There is no once-only SGD fold at these widths. */
+int cdlrm_gather_interact_wide_supported(cdlrm_ctx* ctx);
+int cdlrm_gather_interact_wide_fwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x, int64_t B,
+                                   int32_t itself, float* R, int64_t ld_r, void* stream);
+int cdlrm_gather_interact_wide_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
+                                   const float* dR, int64_t ld_r, int64_t B, int32_t itself, int32_t x_act, float* dfeat,
+                                   void* stream);
+/* Grid (workgroups of 256 lanes: a wave per sample, striding) and dynamic LDS of such a launch on B samples: op CDLRM_IA_OP_FWD /
+ * CDLRM_IA_OP_BWD.  From the plan the two calls launch from; refused where they refuse the context.  No device is touched. */
+int cdlrm_gather_interact_wide_grid(cdlrm_ctx* ctx, int32_t op, int64_t B, int64_t* grid, int64_t* lds_bytes);
 /* Linear + activation (create_mlp, model_no_ddp.py:244-270): Y = act(X W^T + b).
  * X [M, K] ld_x, W [N, K] row-major (nn.Linear.weight), Y [M, N] ld_y. act: 0 none, 1 ReLU, 2 sigmoid. */
 /* CDLRM_GEMM_ALONE, or-ed into `act` of cdlrm_linear_fwd / cdlrm_linear_bwd: the caller's promise that no other GEMM runs beside
