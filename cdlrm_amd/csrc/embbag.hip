@@ -127,10 +127,10 @@ __global__ void __launch_bounds__(256) k_fill_aux(const TableDesc* __restrict__ 
     // front of the HBM traffic of whatever runs beside this kernel (measured: concurrent GEMMs 2-3x slower under a
     // 200-workgroup fill).  So: ONE small grid over the misses of all tables (most tables have none), FILL_U
     // independent 16-B reads per lane.
-    __shared__ int64_t first[65];           // first[t] = 16-B elements of the tables before t
-    __shared__ int64_t aux_base[64];        // first aux row of table t
-    __shared__ uint64_t hrow[64];           // host table of t (address)
-    __shared__ int64_t voff[65];            // victim list of table t: v_idx[voff[t] .. voff[t+1])
+    __shared__ int64_t first[129];          // first[t] = 16-B elements of the tables before t
+    __shared__ int64_t aux_base[128];       // first aux row of table t
+    __shared__ uint64_t hrow[128];          // host table of t (address)
+    __shared__ int64_t voff[129];           // victim list of table t: v_idx[voff[t] .. voff[t+1])
     __shared__ int search_steps;
     if (VICT) {
         if (threadIdx.x <= T) voff[threadIdx.x] = v_off[threadIdx.x];
@@ -367,7 +367,7 @@ extern "C" int cdlrm_embbag_probe(cdlrm_ctx* ctx, const int64_t* idx, int64_t n,
     if (ctx->aux > 0) {
         CDLRM_REQUIRE(ctx->h_host_rows[0] != nullptr, "cdlrm_ctx_bind_host_tables first");
         const int D4 = ctx->D / 4;
-        CDLRM_REQUIRE(ctx->T <= 64, "more than 64 tables");
+        CDLRM_REQUIRE(ctx->T <= 128, "more than 128 tables");
         // grid x reads-per-lane x 4 KB per workgroup-read = bytes in flight.  Measured on the MI355X box (random 512-B
         // rows of a 96 GB pinned table): a host read takes ~17 us round trip, so the ~50 GB/s link needs ~0.5-1 MB in
         // flight; 32 workgroups x 4 reads is the knee (16x8: 1.04 ms/step, 32x4: 0.96, 64x4: 0.98)

@@ -34,6 +34,17 @@ __host__ __device__ constexpr int iw_bwd_floats(int D4) { return iw_slab_slice()
 __host__ __device__ constexpr int iw_gather_table() { return 64; }
 __host__ __device__ constexpr int iw_row_tile(int D) { return 64 * (D + 1) + 32; }
 __host__ __device__ constexpr int iw_row_bwd_floats(int D, int npairs) { return iw_row_tile(D) + ((npairs + 3) & ~3); }
+// Extra-wide kernels (interact_xwide.hip, 64 < F <= 128): the four waves of a workgroup share ONE sample, so these are floats per
+// workgroup.  FP is F rounded up to 32.  Two [FP][32 + 4] slices (double-buffered slabs); the forward stages the pair row (pairs
+// padded to 4) behind them, the backward the whole dR row [D | pairs padded to 4] and a [32][36] output tile per wave.
+#define IX_PITCH 36
+__host__ __device__ constexpr int ix_slice(int FP) { return FP * IX_PITCH; }
+__host__ __device__ constexpr int ix_pair_row(int npairs) { return (npairs + 3) & ~3; }
+__host__ __device__ constexpr int ix_out_tile() { return 32 * IX_PITCH; }
+__host__ __device__ constexpr int ix_fwd_floats(int FP, int npairs) { return 2 * ix_slice(FP) + ix_pair_row(npairs); }
+__host__ __device__ constexpr int ix_bwd_floats(int FP, int D, int npairs) {
+    return 2 * ix_slice(FP) + D + ix_pair_row(npairs) + 4 * ix_out_tile();
+}
 
 // ---- host helpers of the entry points in dense.hip and interact_wide.hip --------------------------------------------------------
 // run-time D4 of the pipelined kernels -> compile-time: fn(std::integral_constant<int, D4>{})

@@ -997,9 +997,9 @@ def main(argv=None):
     m_spa = args.arch_sparse_feature_size
     num_fea = ln_emb.size + 1
     m_den_out = ln_bot[ln_bot.size - 1]
-    if args.arch_interaction_op == "dot" and num_fea > 64:
-        sys.exit("ERROR: --arch-interaction-op=dot takes at most 63 embedding tables (one sample's pair matrix is held as 64 x 64 "
-                 "on the matrix cores), and --arch-embedding-size names %d" % ln_emb.size)
+    if args.arch_interaction_op == "dot" and num_fea > 128:
+        sys.exit("ERROR: --arch-interaction-op=dot takes at most 127 embedding tables (one sample's pair matrix is held as 128 x "
+                 "128 on the matrix cores), and --arch-embedding-size names %d" % ln_emb.size)
     if args.arch_interaction_op == "dot":
         num_int = (num_fea * (num_fea + 1)) // 2 + m_den_out if args.arch_interaction_itself else \
             (num_fea * (num_fea - 1)) // 2 + m_den_out

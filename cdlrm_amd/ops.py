@@ -643,11 +643,18 @@ def agg_split(ctx: CacheCtx, rows: torch.Tensor, count: int, tier: torch.Tensor,
 # ---- dense model -------------------------------------------------------------------------------------
 
 IA_NARROW_F = 32          # features one 32x32 Gram tile holds; 33 .. 64 go to the wide kernels (csrc/interact_wide.hip)
+IA_WIDE_F = 64            # features one wave's 64x64 Gram matrix holds; 65 .. 128 go to csrc/interact_xwide.hip
+
+
+def _interact_entry(F: int, op: str):
+    """The C entry point interact_fwd (op "fwd") / interact_bwd ("bwd") calls at F features."""
+    width = "xwide_" if F > IA_WIDE_F else "wide_" if F > IA_NARROW_F else ""
+    return getattr(_lib.lib(), "cdlrm_interact_%s%s" % (width, op))
 
 
 def interact_fwd(feat: torch.Tensor, itself: bool, R: torch.Tensor, stream=None):
     B, F, D = feat.shape
-    fn = _lib.lib().cdlrm_interact_wide_fwd if F > IA_NARROW_F else _lib.lib().cdlrm_interact_fwd
+    fn = _interact_entry(F, "fwd")
     check(fn(feat.data_ptr(), B, F, D, int(bool(itself)), R.data_ptr(), R.stride(0), stream_ptr(stream)))
 
 
@@ -655,7 +662,7 @@ def interact_bwd(feat: torch.Tensor, dR: torch.Tensor, itself: bool, dfeat: torc
     """x_act: activation that produced feature 0 (the bottom MLP's output); its gradient row then leaves as the
     pre-activation gradient."""
     B, F, D = feat.shape
-    fn = _lib.lib().cdlrm_interact_wide_bwd if F > IA_NARROW_F else _lib.lib().cdlrm_interact_bwd
+    fn = _interact_entry(F, "bwd")
     check(fn(feat.data_ptr(), dR.data_ptr(), dR.stride(0), B, F, D, int(bool(itself)), int(x_act), dfeat.data_ptr(),
              stream_ptr(stream)))
 
@@ -811,7 +818,7 @@ def qr_interact_grid(op: int, B: int, D: int):
 
 
 IA_OPS = {"fwd": 0, "bwd": 1, "gather_fwd": 2, "gather_bwd": 3, "gather_bwd_sgd": 4}
-IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db", 5: "wide_slab", 6: "wide_row"}
+IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db", 5: "wide_slab", 6: "wide_row", 7: "xwide"}
 
 
 def interact_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, aligned_r: bool = True,
@@ -833,6 +840,17 @@ def interact_wide_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int
     out = _lib.InteractRoute()
     check(_lib.raw().cdlrm_interact_wide_route(IA_OPS[op], int(B), int(F), int(D), int(bool(itself)), int(ld_r),
                                                int(bool(aligned_r)) | int(bool(aligned_dfeat)) << 1, C.byref(out)))
+    return {"family": IA_FAMILIES[out.family], "d4": out.d4, "ns": out.ns, "grid": out.grid, "lds_bytes": out.lds_bytes}
+
+
+def interact_xwide_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, aligned_r: bool = True,
+                         aligned_dfeat: bool = True) -> dict:
+    """interact_route for the calls interact_fwd / interact_bwd make at 64 < F <= 128 (op "fwd" / "bwd"): family "xwide", ns the
+    32-column slabs of a sample, grid the workgroups (one sample each at a time).  A shape those calls refuse raises their error.
+    No device is touched."""
+    out = _lib.InteractRoute()
+    check(_lib.raw().cdlrm_interact_xwide_route(IA_OPS[op], int(B), int(F), int(D), int(bool(itself)), int(ld_r),
+                                                int(bool(aligned_r)) | int(bool(aligned_dfeat)) << 1, C.byref(out)))
     return {"family": IA_FAMILIES[out.family], "d4": out.d4, "ns": out.ns, "grid": out.grid, "lds_bytes": out.lds_bytes}
 
 

@@ -593,6 +593,7 @@ int cdlrm_qr_interact_grid(int32_t op, int64_t B, int32_t D, int64_t* grid, int6
 #define CDLRM_IA_SLAB_DB 4      /* k_interact_fwd_s<d4, ns, true, true>: the slab slice double-buffered */
 #define CDLRM_IA_WIDE_SLAB 5    /* k_interact_wide_fwd / _bwd<d4> (32 < F <= 64): 32-column slabs, a register ring of loads */
 #define CDLRM_IA_WIDE_ROW 6     /* k_interact_wide_fwd_row / _bwd_row (32 < F <= 64): any D, the sample's whole rows staged */
+#define CDLRM_IA_XWIDE 7        /* k_interact_xwide_fwd / _bwd<nb> (64 < F <= 128): a workgroup per sample, double-buffered slabs */
 #define CDLRM_IA_OP_FWD 0               /* cdlrm_interact_fwd */
 #define CDLRM_IA_OP_BWD 1               /* cdlrm_interact_bwd */
 #define CDLRM_IA_OP_GATHER_FWD 2        /* cdlrm_gather_interact_fwd */
@@ -626,6 +627,21 @@ int cdlrm_interact_wide_bwd(const float* feat, const float* dR, int64_t ld_r, in
  * entry point refuses is refused here with its error.  No device is touched. */
 int cdlrm_interact_wide_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r, int32_t aligned,
                               struct cdlrm_interact_route* out);
+/* interact_features "dot" for 65 to 128 features (F = T + 1, 64 <= T <= 127): the operands, layouts and results of
+ * cdlrm_interact_wide_fwd / _bwd, on kernels that give a whole 256-lane workgroup one sample (csrc/interact_xwide.hip): the
+ * Gram matrix is 3 x 3 or 4 x 4 blocks of 32 x 32 dealt to the four waves.  D % 4 == 0, D <= 512, feat 16-byte aligned,
+ * ld_r >= D + the number of pairs; one kernel pair for every such D.  Whole-float4 R / dR rows (16-byte aligned, ld_r % 4 == 0,
+ * ld_r >= the width rounded up to 4) and a 16-byte aligned dfeat take float4 stores, anything else scalar ones.  F <= 64 is
+ * refused: that is cdlrm_interact_wide_fwd / _bwd.  cdlrm_interact_xwide_bwd carries an attached completion event like
+ * cdlrm_interact_bwd. */
+int cdlrm_interact_xwide_fwd(const float* feat, int64_t B, int32_t F, int32_t D, int32_t itself,
+                             float* R, int64_t ld_r, void* stream);
+int cdlrm_interact_xwide_bwd(const float* feat, const float* dR, int64_t ld_r, int64_t B, int32_t F,
+                             int32_t D, int32_t itself, int32_t x_act, float* dfeat, void* stream);
+/* cdlrm_interact_route for the two calls above: op CDLRM_IA_OP_FWD / CDLRM_IA_OP_BWD; family CDLRM_IA_XWIDE, ns the 32-column
+ * slabs of a sample.  A shape the entry point refuses is refused here with its error.  No device is touched. */
+int cdlrm_interact_xwide_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r, int32_t aligned,
+                               struct cdlrm_interact_route* out);
 /* Cached EmbeddingBag forward + interact_features "dot" in ONE launch (model_no_ddp.py:200-203 + :272-293) for 32 to 63 tables:
  * cdlrm_gather_interact_fwd / _bwd on the pipelined kernels of csrc/interact_wide.hip, with the same arguments, the same checks
  * (n >= B, T * n < 2^31, 16-byte aligned x with ld_x % 4 == 0, whole-float4 R / dR rows, 16-byte aligned dfeat) and the same
