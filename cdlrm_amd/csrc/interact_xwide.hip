@@ -26,6 +26,9 @@
 //
 // Scalar tiers on workgroup-uniform branches: an R / dR that is not 16-byte aligned or has a pitch without whole float4 words,
 // an unaligned dfeat.
+//
+// The pair also runs as the fused gather (cdlrm_gather_interact_xwide_fwd / _bwd): the same kernels with the
+// loader's source switched (IxLoader<NB, G>), the rows read from the cache by slot id; the float4 tiers only.
 #include "interact_lds.h"
 
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -35,12 +38,39 @@ static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // accumulator register r of lane half lk: row of its 32x32 block
 __device__ __forceinline__ int ix_acc_row(int r, int lk) { return (r & 3) + 8 * (r >> 2) + 4 * lk; }
 
-// A lane's share of one slab: word lane % 8 of rows lane / 8 + 32 i.  Rows >= F and columns >= D are zeros.
-template <int NB>
+// G (the fused gather, cdlrm_gather_interact_xwide_fwd / _bwd): row 0 of a sample's block is the dense feature
+// x[b] (pitch ldx4 words), rows 1 .. F - 1 are the cache rows weight[tab[t].row_base + slots[t * n + b]], t = row - 1 -- the
+// [B, T, D] block cdlrm_embbag_fwd would write and the kernels below read back never exists.  Same operands in the same lanes,
+// same MFMA order: bit-identical to gather + interaction.
+struct IxGather {
+    const TableDesc* tab;       // row_base of every table's cache rows
+    const v4f* weight;          // cache rows (and the auxiliary rows behind them), D4 float4 words each; fewer than 2^31 words
+    const int32_t* slots;       // [T, n] slot ids of the batch (T * n < 2^31, checked by the host)
+    int n;
+    int64_t ldx4;               // pitch of the dense-feature rows, float4 words
+};
+
+// A lane's share of one slab: word lane % 8 of rows tid / 8 + 32 i.  Rows >= F and columns >= D are zeros.
+//
+// G: the rows come by slot id, and slot id -> address -> row is a dependent chain of two memory round trips.  It is taken apart
+// over three samples of the workgroup's walk, in registers: at the top of a sample's FIRST step a lane requests the NB slot ids of
+// its rows for the sample two ahead (idb; the eight lanes of a row read the same word) after moving the ids that request brought
+// a sample ago into ida; at the top of the sample's LAST step ida becomes off[] -- 32-bit float4-word offsets from `weight` -- right
+// in front of load(bn, 0), and off[] then serves slabs 1 .. NS - 1 of that sample.  A request is at least a whole step old when
+// its ids are touched (NS = 1: exactly one step; the stage() of that step has waited for younger loads already), so no lane waits
+// for a slot id inside the step that asked for it.  Row 0 comes from x by a select on register 0 of lanes 0 .. 7; the row slot
+// of rows 0 and >= F is clamped into 1 .. F - 1, so every id and row load is issued and the spare ones are replaced by zeros.
+template <int NB, bool G = false>
 struct IxLoader {
     v4f v[NB];
-    const v4f* feat4;
+    const v4f* feat4;           // G: x
     int F, D4, row, word;
+    const v4f* w4;              // G: the cache rows
+    int64_t ldx4;
+    const int32_t* slots;
+    int srow[NB], rbase[NB];    // where the row's table keeps its slot ids; row_base * D4 of that table
+    int ida[NB], idb[NB];       // slot ids of the sample one / two ahead of the one whose first step has begun
+    int off[NB];                // float4 words from `weight` to the rows of the sample that load() reads
 
     __device__ __forceinline__ void init(const float* feat, int F_, int D4_) {
         feat4 = reinterpret_cast<const v4f*>(feat);
@@ -49,15 +79,71 @@ struct IxLoader {
         row = threadIdx.x >> 3;
         word = threadIdx.x & 7;
     }
+    __device__ __forceinline__ void init(const float* x, const IxGather& ga, int F_, int D4_) {
+        init(x, F_, D4_);
+        w4 = ga.weight;
+        ldx4 = ga.ldx4;
+        slots = ga.slots;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int t = min(max(row + 32 * i, 1), F - 1) - 1;
+            srow[i] = t * ga.n;
+            rbase[i] = (int)ga.tab[t].row_base * D4;
+        }
+    }
+    __device__ __forceinline__ void fetch_ids(int64_t b) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) idb[i] = slots[srow[i] + b];
+    }
+    __device__ __forceinline__ void offsets(const int (&id)[NB]) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i) off[i] = rbase[i] + id[i] * D4;
+    }
     __device__ __forceinline__ void load(int64_t b, int s) {
         // every load is issued, from a clamped address inside the sample's block; what lies outside it becomes zeros
         const int c4 = 8 * s + word;
+        const v4f z = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (G) {      // (off[] must be sample b's)
+            const int c = min(c4, D4 - 1);
+#pragma unroll
+            for (int i = 0; i < NB; ++i) {
+                const v4f* src = w4 + (uint32_t)off[i];
+                if (i == 0) src = row == 0 ? feat4 + b * ldx4 : src;
+                const v4f x = src[c];
+                v[i] = row + 32 * i < F && c4 < D4 ? x : z;
+            }
+            return;
+        }
         const v4f* src = feat4 + b * F * D4 + min(c4, D4 - 1);
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            const v4f x = src[min(row + 32 * i, F - 1) * D4], z = {0.f, 0.f, 0.f, 0.f};
+            const v4f x = src[min(row + 32 * i, F - 1) * D4];
             v[i] = row + 32 * i < F && c4 < D4 ? x : z;
         }
+    }
+    // the first sample's slab 0.  G: its chain and the ids of the sample behind it, exposed once per workgroup
+    __device__ __forceinline__ void prime(int64_t b, int64_t B) {
+        if constexpr (G) {
+            fetch_ids(b);
+            offsets(idb);
+        }
+        load(b, 0);
+        if constexpr (G) {
+            if (b + gridDim.x < B) fetch_ids(b + gridDim.x);
+        }
+    }
+    // top of step (b, s): the loads of the step behind it, (bn, sn) if there is one (`more`)
+    __device__ __forceinline__ void ahead(int64_t b, int s, int64_t bn, int sn, bool more, int64_t B) {
+        if constexpr (G) {
+            if (s == 0) {
+#pragma unroll
+                for (int i = 0; i < NB; ++i) ida[i] = idb[i];
+                const int64_t b2 = b + 2 * (int64_t)gridDim.x;
+                if (b2 < B) fetch_ids(b2);      // (ids of samples past B are not loaded)
+            }
+            if (more && sn == 0) offsets(ida);
+        }
+        if (more) load(bn, sn);
     }
     __device__ __forceinline__ void stage(float* __restrict__ Ts) const {
 #pragma unroll
@@ -76,9 +162,11 @@ __device__ __forceinline__ bool ix_next(int64_t b, int s, int NS, int64_t B, int
     return bn < B;
 }
 
-template <int NB>
-__global__ void __launch_bounds__(256, 2) k_interact_xwide_fwd(const float* __restrict__ feat, int64_t B, int F, int D, int itself,
-                                                               float* __restrict__ R, int64_t ld_r, int vec) {
+// G = false: feat is the [B, F, D] block, ga is not read.  G (cdlrm_gather_interact_xwide_fwd): feat is x, the rows come through
+// ga.  One body; the loader alone knows the difference.
+template <int NB, bool G = false>
+__global__ void __launch_bounds__(256, 2) k_interact_xwide_fwd(const float* __restrict__ feat, IxGather ga, int64_t B, int F, int D,
+                                                               int itself, float* __restrict__ R, int64_t ld_r, int vec) {
     constexpr int FP = 32 * NB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Os = smem + 2 * ix_slice(FP);        // the pair row [pairs | pad words]
@@ -93,8 +181,9 @@ __global__ void __launch_bounds__(256, 2) k_interact_xwide_fwd(const float* __re
     int f[3];
 #pragma unroll
     for (int q = 0; q < 3; ++q) f[q] = (wave + q) % NB;
-    IxLoader<NB> ld;
-    ld.init(feat, F, D >> 2);
+    IxLoader<NB, G> ld;
+    if constexpr (G) ld.init(feat, ga, F, D >> 2);
+    else ld.init(feat, F, D >> 2);
     // the staging of step (b, s) into a slice; row 0 is the dense part of R[b]
     auto stage = [&](float* Ts, int64_t b, int s) __attribute__((always_inline)) {
         ld.stage(Ts);
@@ -106,7 +195,7 @@ __global__ void __launch_bounds__(256, 2) k_interact_xwide_fwd(const float* __re
         }
     };
     if ((int)threadIdx.x < 4 * P4 - npairs) Os[npairs + threadIdx.x] = 0.f;     // the pad words: written once, no pair lands there
-    ld.load(b, 0);
+    ld.prime(b, B);
     stage(smem, b, 0);
     __syncthreads();
     f32x16 a0, a1, a2;
@@ -115,7 +204,7 @@ __global__ void __launch_bounds__(256, 2) k_interact_xwide_fwd(const float* __re
         int64_t bn;
         int sn;
         const bool more = ix_next(b, s, NS, B, bn, sn);
-        if (more) ld.load(bn, sn);
+        ld.ahead(b, s, bn, sn, more, B);
         __builtin_amdgcn_sched_barrier(0);
         if (s == 0) {
 #pragma unroll
@@ -190,8 +279,10 @@ __global__ void __launch_bounds__(256, 2) k_interact_xwide_fwd(const float* __re
 
 // One wave per SIMD: bounded to two, the NB = 4 instance spills (172 to 232 bytes per lane in every arrangement tried); unbounded,
 // what does not fit 256 VGPRs is parked in AGPRs and there is no scratch.
-template <int NB>
-__global__ void __launch_bounds__(256) k_interact_xwide_bwd(const float* __restrict__ feat, const float* __restrict__ dR,
+// G (cdlrm_gather_interact_xwide_bwd): as in the forward kernel; the rows are read again from the cache, so the launch goes in
+// front of the batch's embedding update.
+template <int NB, bool G = false>
+__global__ void __launch_bounds__(256) k_interact_xwide_bwd(const float* __restrict__ feat, IxGather ga, const float* __restrict__ dR,
                                                                int64_t ld_r, int64_t B, int F, int D, int itself, int x_act,
                                                                float* __restrict__ dfeat, int vec_r, int vec_df) {
     constexpr int FP = 32 * NB;
@@ -207,8 +298,9 @@ __global__ void __launch_bounds__(256) k_interact_xwide_bwd(const float* __restr
     const bool active = wave < NB;                      // owns row block `wave` of S
     int64_t b = blockIdx.x;
     if (b >= B) return;                                 // (the whole workgroup)
-    IxLoader<NB> ld;
-    ld.init(feat, F, D >> 2);
+    IxLoader<NB, G> ld;
+    if constexpr (G) ld.init(feat, ga, F, D >> 2);
+    else ld.init(feat, F, D >> 2);
     v4f gn[NG];
     auto fetch_grad = [&](int64_t b) __attribute__((always_inline)) {
         if (!vec_r) return;
@@ -247,7 +339,7 @@ __global__ void __launch_bounds__(256) k_interact_xwide_bwd(const float* __restr
         }
     };
     fetch_grad(b);
-    ld.load(b, 0);
+    ld.prime(b, B);
     ld.stage(smem);
     head(b);                // (its barrier also publishes the first slice)
     int s = 0, cur = 0;
@@ -255,7 +347,7 @@ __global__ void __launch_bounds__(256) k_interact_xwide_bwd(const float* __restr
         int64_t bn;
         int sn;
         const bool more = ix_next(b, s, NS, B, bn, sn);
-        if (more) ld.load(bn, sn);
+        ld.ahead(b, s, bn, sn, more, B);
         __builtin_amdgcn_sched_barrier(0);
         if (active) {
             const float* Ts = smem + cur * ix_slice(FP);
@@ -352,8 +444,8 @@ extern "C" int cdlrm_interact_xwide_fwd(const float* feat, int64_t B, int32_t F,
     const IxPlan p = xwide_plan(CDLRM_IA_OP_FWD, B, F, D, itself, ld_r, aligned16(R), false);
     CDLRM_REQUIRE(p.lds <= 160 * 1024, "LDS budget");
     if (B == 0) return 0;
-    if (p.nb == 3) return ia_launch<k_interact_xwide_fwd<3>>(p, stream, false, feat, B, F, D, itself, R, ld_r, (int)p.vec_r);
-    return ia_launch<k_interact_xwide_fwd<4>>(p, stream, false, feat, B, F, D, itself, R, ld_r, (int)p.vec_r);
+    if (p.nb == 3) return ia_launch<k_interact_xwide_fwd<3>>(p, stream, false, feat, IxGather{}, B, F, D, itself, R, ld_r, (int)p.vec_r);
+    return ia_launch<k_interact_xwide_fwd<4>>(p, stream, false, feat, IxGather{}, B, F, D, itself, R, ld_r, (int)p.vec_r);
 }
 
 extern "C" int cdlrm_interact_xwide_bwd(const float* feat, const float* dR, int64_t ld_r, int64_t B, int32_t F, int32_t D,
@@ -365,8 +457,8 @@ extern "C" int cdlrm_interact_xwide_bwd(const float* feat, const float* dR, int6
     CDLRM_REQUIRE(p.lds <= 160 * 1024, "LDS budget");
     if (B == 0) return 0;
     if (p.nb == 3)
-        return ia_launch<k_interact_xwide_bwd<3>>(p, stream, true, feat, dR, ld_r, B, F, D, itself, x_act, dfeat, (int)p.vec_r, (int)p.vec_df);
-    return ia_launch<k_interact_xwide_bwd<4>>(p, stream, true, feat, dR, ld_r, B, F, D, itself, x_act, dfeat, (int)p.vec_r, (int)p.vec_df);
+        return ia_launch<k_interact_xwide_bwd<3>>(p, stream, true, feat, IxGather{}, dR, ld_r, B, F, D, itself, x_act, dfeat, (int)p.vec_r, (int)p.vec_df);
+    return ia_launch<k_interact_xwide_bwd<4>>(p, stream, true, feat, IxGather{}, dR, ld_r, B, F, D, itself, x_act, dfeat, (int)p.vec_r, (int)p.vec_df);
 }
 
 extern "C" int cdlrm_interact_xwide_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r,
@@ -379,4 +471,95 @@ extern "C" int cdlrm_interact_xwide_route(int32_t op, int64_t B, int32_t F, int3
     out->family = CDLRM_IA_XWIDE; out->d4 = D / 4; out->ns = p.ns; out->reserved = 0;
     out->grid = p.grid; out->lds_bytes = (int64_t)p.lds;
     return 0;
+}
+
+// ---- fused gather + interaction at 65 to 128 features (Criteo layout: one index per bag, so a bag's sum-pool is its cache row) ----
+// cached EmbeddingBag forward (model_no_ddp.py:200-203) + interact_features "dot" (:272-293) in one launch, and the interaction
+// backward reading the same rows again.  The float4 tiers only: whole-float4 R / dR rows, aligned dfeat.
+// The plan of both launches and of the query: xwide_plan's answer for an aligned call (the loader's chain lives in registers, so
+// there is no LDS beside it).  nb 0: no kernel -- F outside 65 .. 128, D not a multiple of 4 or above 512, a cache whose rows a
+// 32-bit float4-word offset cannot name, or more LDS than a workgroup gets.
+static IxPlan gather_xwide_plan(int op, int64_t B, const cdlrm_ctx* ctx) {
+    const int F = ctx->T + 1, D = ctx->D;
+    if (!(IX_SHAPE_OK(F, D) && ctx->total_rows * (D / 4) < INT32_MAX)) return IxPlan{};
+    const IxPlan p = xwide_plan(op, B, F, D, 1, (IX_WIDTH(F, D, 1) + 3) & ~3, true, true);
+    return p.lds <= 160 * 1024 ? p : IxPlan{};
+}
+
+#define IXG_SHAPE_MSG "unsupported shape (64 < T + 1 <= 128, D % 4 == 0, D <= 512, cache rows * D / 4 < 2^31)"
+
+extern "C" int cdlrm_gather_interact_xwide_supported(cdlrm_ctx* ctx) {
+    return ctx && gather_xwide_plan(CDLRM_IA_OP_FWD, 1, ctx).nb ? 1 : 0;
+}
+
+extern "C" int cdlrm_gather_interact_xwide_grid(cdlrm_ctx* ctx, int32_t op, int64_t B, int64_t* grid, int64_t* lds_bytes) {
+    CDLRM_REQUIRE(ctx && grid && lds_bytes && (op == CDLRM_IA_OP_FWD || op == CDLRM_IA_OP_BWD) && B >= 0, "bad argument");
+    const IxPlan p = gather_xwide_plan(op, B, ctx);
+    CDLRM_REQUIRE(p.nb, IXG_SHAPE_MSG);
+    *grid = p.grid;
+    *lds_bytes = (int64_t)p.lds;
+    return 0;
+}
+
+// what both entry points ask of the slots, the dense feature and the R / dR rows (the checks of cdlrm_gather_interact_fwd / _bwd)
+static int gather_xwide_check(const cdlrm_ctx* ctx, const IxPlan& p, int64_t n, const float* x, int64_t ld_x, const float* r,
+                              int64_t ld_r, int64_t B, int32_t itself) {
+    CDLRM_REQUIRE(p.nb, IXG_SHAPE_MSG ": gather + interaction as two calls");
+    CDLRM_REQUIRE(B >= 0 && n >= B && (int64_t)ctx->T * n < INT32_MAX && aligned16(x) && ld_x % 4 == 0 && ld_x >= ctx->D,
+                  "slot pitch / dense-feature rows");
+    const int width = IX_WIDTH(ctx->T + 1, ctx->D, itself);
+    CDLRM_REQUIRE(ld_r % 4 == 0 && aligned16(r) && ld_r >= ((width + 3) & ~3), "whole-float4 rows of R / dR (ld_r)");
+    return 0;
+}
+
+// one launch of the plan between a start and a stop event (either may be null)
+template <auto Kernel, typename... Args>
+static int ix_launch_between(const IxPlan& p, void* stream, hipEvent_t ev0, hipEvent_t ev1, Args... args) {
+    const int rc = cdlrm_grant_dynamic_lds<Kernel>(p.lds);
+    if (rc) return rc;
+    hipExtLaunchKernelGGL(Kernel, dim3((unsigned)p.grid), dim3(256), p.lds, (hipStream_t)stream, ev0, ev1, 0, args...);
+    return 0;
+}
+
+extern "C" int cdlrm_gather_interact_xwide_fwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
+                                               int64_t B, int32_t itself, float* R, int64_t ld_r, void* stream) {
+    CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
+    CDLRM_CLEAR_STALE();
+    CDLRM_REQUIRE(ctx && slots && x && R, "null argument");
+    CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
+    const IxPlan p = gather_xwide_plan(CDLRM_IA_OP_FWD, B, ctx);
+    const int rc = gather_xwide_check(ctx, p, n, x, ld_x, R, ld_r, B, itself);
+    if (rc) return rc;
+    if (B == 0) return 0;       // (an armed event pair stays armed for the next launch that can carry it)
+    // a timed pair (cdlrm_ctx_time_next_gather) and an attached completion event, as cdlrm_gather_interact_fwd carries them
+    hipEvent_t ev0 = (hipEvent_t)ctx->ev_start, ev1 = (hipEvent_t)ctx->ev_stop;
+    ctx->ev_start = ctx->ev_stop = nullptr;
+    hipEvent_t se = cdlrm_take_stop_event((hipStream_t)stream);
+    if (!ev1 && se) { ev1 = se; se = nullptr; }
+    const IxGather ga{ctx->d_tab, reinterpret_cast<const v4f*>(ctx->weight), slots, (int)n, ld_x / 4};
+    const int F = ctx->T + 1, D = ctx->D;
+    const int rl = p.nb == 3 ? ix_launch_between<k_interact_xwide_fwd<3, true>>(p, stream, ev0, ev1, x, ga, B, F, D, itself, R, ld_r, 1)
+                             : ix_launch_between<k_interact_xwide_fwd<4, true>>(p, stream, ev0, ev1, x, ga, B, F, D, itself, R, ld_r, 1);
+    if (rl) return rl;
+    if (se) CDLRM_HIP_CHECK(hipEventRecord(se, (hipStream_t)stream));
+    CDLRM_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cdlrm_gather_interact_xwide_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
+                                               const float* dR, int64_t ld_r, int64_t B, int32_t itself, int32_t x_act,
+                                               float* dfeat, void* stream) {
+    CdlrmStopScope stop_scope;          // (first: every exit below flushes an attached completion event)
+    CDLRM_REQUIRE(ctx && slots && x && dR && dfeat, "null argument");
+    CDLRM_REQUIRE(ctx->weight, "cdlrm_ctx_bind_cache first");
+    const IxPlan p = gather_xwide_plan(CDLRM_IA_OP_BWD, B, ctx);
+    const int rc = gather_xwide_check(ctx, p, n, x, ld_x, dR, ld_r, B, itself);
+    if (rc) return rc;
+    CDLRM_REQUIRE(aligned16(dfeat), "whole-float4 gradient rows (dfeat)");
+    if (B == 0) return 0;
+    const IxGather ga{ctx->d_tab, reinterpret_cast<const v4f*>(ctx->weight), slots, (int)n, ld_x / 4};
+    const int F = ctx->T + 1, D = ctx->D;
+    if (p.nb == 3)
+        return ia_launch<k_interact_xwide_bwd<3, true>>(p, stream, true, x, ga, dR, ld_r, B, F, D, itself, x_act, dfeat, 1, 1);
+    return ia_launch<k_interact_xwide_bwd<4, true>>(p, stream, true, x, ga, dR, ld_r, B, F, D, itself, x_act, dfeat, 1, 1);
 }

@@ -717,7 +717,7 @@ class StepPath(NamedTuple):
     lr: float
     lr_embeds: float
     lr_cells: bool = False          # the rate arguments are the engine's two rate cells, not literals
-    gather_wide: bool = False       # `fused` on the wide pair (cdlrm_gather_interact_wide_fwd / _bwd)
+    gather_wide: bool = False       # `fused` on the wide pair (cdlrm_gather_interact_wide_fwd / _bwd; F > 64: _xwide_, 4.13)
     embed_optimizer: str = "sgd"    # the cache rows' update: "sgd" or "rowwise_adagrad" 
     adagrad_eps: float = 0.0
     dense_optimizer: str = "sgd"    # the MLP parameters' update: "sgd" or "adagrad" 
@@ -1480,7 +1480,8 @@ class TrainEngine:
         # tests pin the default QR launch sequence
         self.fuse_qr = False
         # 32 to 63 tables: the same fusion on the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd) instead of
-        # cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd on a materialised block.  Opt-in (--fuse-gather-wide): bit-identical,
+        # cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd on a materialised block; 64 to 127 tables: on the extra-wide ones
+        # (cdlrm_gather_interact_xwide_fwd / _bwd).  Opt-in (--fuse-gather-wide): bit-identical,
         # measured stand-alone only (tools/gather_interact_wide_time.py), and existing tests pin the default
         # launch sequence at 32 and 63 tables.  No once-only fold there: the sorted embedding backward does every slot
         self.fuse_gather_wide = False
@@ -1756,10 +1757,20 @@ class TrainEngine:
                     and ops.gather_interact_supported(self.ctx)) or self._gather_wide(lS_o)
 
     def _gather_wide(self, lS_o) -> bool:
-        """One index per bag at 32 to 63 tables, opted in (fuse_gather_wide): the gather rides in the wide interaction kernels.
+        """One index per bag at 32 to 127 tables, opted in (fuse_gather_wide): the gather rides in the wide interaction kernels,
+        above 64 features in the extra-wide ones (self.F, a constant of the engine, decides: _gather_wide_calls).
         Multi-hot bags and quotient-remainder tables stay on two operators there."""
-        return bool(self.fuse_gather_wide and lS_o is None and self.qr is None and not self.cat and S.is_hip(self.dev)
-                    and self.F > ops.IA_NARROW_F and ops.gather_interact_wide_supported(self.ctx))
+        if not (self.fuse_gather_wide and lS_o is None and self.qr is None and not self.cat and S.is_hip(self.dev)):
+            return False
+        if self.F > ops.IA_WIDE_F:
+            return bool(ops.gather_interact_xwide_supported(self.ctx))
+        return bool(self.F > ops.IA_NARROW_F and ops.gather_interact_wide_supported(self.ctx))
+
+    def _gather_wide_calls(self):
+        """(forward, backward) of the pair `StepPath.gather_wide` means at this engine's feature count."""
+        if self.F > ops.IA_WIDE_F:
+            return ops.gather_interact_xwide_fwd, ops.gather_interact_xwide_bwd
+        return ops.gather_interact_wide_fwd, ops.gather_interact_wide_bwd
 
     def _side_gather(self, B: int) -> bool:
         """Short local batches run the gather on the side stream (see _fwd_bwd)."""
@@ -2285,7 +2296,7 @@ class TrainEngine:
             elif path.offsets:
                 ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R, n_bags=path.n_bags)
             elif path.gather_wide:
-                ops.gather_interact_wide_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
+                self._gather_wide_calls()[0](ctx, slots, feat[:, 0, :], self.itself, R)
             else:
                 ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         elif not self.cat:
@@ -2380,7 +2391,7 @@ class TrainEngine:
             elif fused and path.offsets:
                 ops.bag_interact_bwd(ctx, slots, lS_o, feat[:, 0, :], dR, self.itself, dfeat, n_bags=path.n_bags, x_act=self.bot[-1][1])
             elif path.gather_wide:
-                ops.gather_interact_wide_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
+                self._gather_wide_calls()[1](ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
             elif fused:
                 ops.gather_interact_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
             else:
@@ -2493,7 +2504,7 @@ class TrainEngine:
         elif self._fused_gather(lS_o) and lS_o is not None:
             ops.bag_interact_fwd(ctx, slots, lS_o, feat[:, 0, :], self.itself, R)
         elif self._gather_wide(lS_o):
-            ops.gather_interact_wide_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
+            self._gather_wide_calls()[0](ctx, slots, feat[:, 0, :], self.itself, R)
         elif self._fused_gather(lS_o):
             ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         else:

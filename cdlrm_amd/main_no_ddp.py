@@ -97,8 +97,8 @@ def ProcessArgs(argv=None):
     # --qr-flag: the compose with the remainder rows inside the interaction kernels (cdlrm_qr_interact_fwd / _bwd) instead of
     # cdlrm_qr_cached_fwd + interaction
     parser.add_argument("--qr-fuse-gather", action="store_true", default=False)
-    # 32 to 63 tables, one index per bag: the gather inside the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd)
-    # instead of cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd
+    # 32 to 127 tables, one index per bag: the gather inside the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd;
+    # from 64 tables cdlrm_gather_interact_xwide_fwd / _bwd) instead of cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd
     parser.add_argument("--fuse-gather-wide", action="store_true", default=False)
     # ---- debugging and profiling ----
     parser.add_argument("--print-freq", type=int, default=1)
@@ -570,8 +570,11 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
         eng.fuse_gather_wide = True
         if rank == 0:
             why = ("--qr-flag" if eng.qr is not None else "--arch-interaction-op=cat" if eng.cat else
-                   "dot interaction, D in 32 / 64 / 128 / 256, 32 < tables + 1 <= 64, a cache of fewer than 2^31 float4 words")
-            print("One-index steps: %s" % ("gather inside the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd)"
+                   "dot interaction, a cache of fewer than 2^31 float4 words; 32 < tables + 1 <= 64: D in 32 / 64 / 128 / 256; "
+                   "64 < tables + 1 <= 128: D % 4 == 0, D <= 512")
+            pair = "extra-wide interaction kernels (cdlrm_gather_interact_xwide_fwd" if eng.F > ops.IA_WIDE_F else \
+                "wide interaction kernels (cdlrm_gather_interact_wide_fwd"
+            print("One-index steps: %s" % ("gather inside the %s / _bwd)" % pair
                                            if eng._gather_wide(None) else
                                            "--fuse-gather-wide has no kernel for this model (%s): the route of a run without it" % why),
                   flush=True)

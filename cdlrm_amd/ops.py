@@ -737,6 +737,40 @@ def gather_interact_wide_grid(ctx: CacheCtx, op: str, B: int):
     return grid.value, lds.value
 
 
+# ---- the fused gather at 65 to 128 features (csrc/interact_xwide.hip) ----
+# Entry points of their own again: the _wide_ calls keep refusing T + 1 > 64.
+
+def gather_interact_xwide_supported(ctx: CacheCtx) -> bool:
+    """Shapes the extra-wide fused gather + interaction kernels take (64 < T + 1 <= 128, D % 4 == 0, D <= 512, a cache of fewer
+    than 2^31 float4 words)."""
+    return bool(_lib.raw().cdlrm_gather_interact_xwide_supported(ctx.handle))     # (a query: never on a step's tape)
+
+
+def gather_interact_xwide_fwd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor, itself: bool, R: torch.Tensor, stream=None):
+    """gather_interact_fwd at 64 to 127 tables.  Bit-identical to embbag_fwd + interact_fwd."""
+    B = x.shape[0]
+    assert slots.dtype == torch.int32 and slots.stride(1) == 1 and x.stride(1) == 1
+    check(_lib.lib().cdlrm_gather_interact_xwide_fwd(ctx.handle, slots.data_ptr(), slots.stride(0), x.data_ptr(), x.stride(0), B,
+                                                     int(bool(itself)), R.data_ptr(), R.stride(0), stream_ptr(stream)))
+
+
+def gather_interact_xwide_bwd(ctx: CacheCtx, slots: torch.Tensor, x: torch.Tensor, dR: torch.Tensor, itself: bool,
+                              dfeat: torch.Tensor, stream=None, x_act: int = 0):
+    """gather_interact_bwd at 64 to 127 tables (before the batch's embedding update rewrites the rows)."""
+    B = x.shape[0]
+    assert slots.dtype == torch.int32 and slots.stride(1) == 1 and x.stride(1) == 1 and dfeat.is_contiguous()
+    check(_lib.lib().cdlrm_gather_interact_xwide_bwd(ctx.handle, slots.data_ptr(), slots.stride(0), x.data_ptr(), x.stride(0),
+                                                     dR.data_ptr(), dR.stride(0), B, int(bool(itself)), int(x_act),
+                                                     dfeat.data_ptr(), stream_ptr(stream)))
+
+
+def gather_interact_xwide_grid(ctx: CacheCtx, op: str, B: int):
+    """(workgroups, dynamic LDS bytes) of a gather_interact_xwide_fwd (op "fwd") / _bwd ("bwd") launch.  No device is touched."""
+    grid, lds = C.c_int64(), C.c_int64()
+    check(_lib.raw().cdlrm_gather_interact_xwide_grid(ctx.handle, IA_OPS[op], int(B), C.byref(grid), C.byref(lds)))
+    return grid.value, lds.value
+
+
 # ---- multi-hot bags pooled inside the interaction kernels (csrc/bag_interact.hip, DESIGN.md 4.8) ----
 
 BAG_INTERACT_U = 4      # CDLRM_BAG_INTERACT_U: lookups of one bag whose rows a lane has in flight at a time (D = 256: half)

@@ -661,6 +661,23 @@ int cdlrm_gather_interact_wide_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t
 /* Grid (workgroups of 256 lanes: a wave per sample, striding) and dynamic LDS of such a launch on B samples: op CDLRM_IA_OP_FWD /
  * CDLRM_IA_OP_BWD.  From the plan the two calls launch from; refused where they refuse the context.  No device is touched. */
 int cdlrm_gather_interact_wide_grid(cdlrm_ctx* ctx, int32_t op, int64_t B, int64_t* grid, int64_t* lds_bytes);
+/* The same fusion for 64 to 127 tables: cdlrm_gather_interact_fwd / _bwd on the kernels of csrc/interact_xwide.hip, with the same
+ * arguments, checks and results -- bit-identical to cdlrm_embbag_fwd + cdlrm_interact_xwide_fwd / _bwd.  Shapes:
+ * cdlrm_gather_interact_xwide_supported() -- 64 < T + 1 <= 128, D % 4 == 0, D <= 512, a cache of fewer than 2^31 float4 words and
+ * a launch within 160 KB of LDS; anything else is refused ("unsupported shape") -- the caller issues the two operators.  R / dR
+ * rows must be whole aligned float4 words ("ld_r") and dfeat 16-byte aligned: the scalar tiers of cdlrm_interact_xwide_* are
+ * never taken.  Events as the _wide_ pair carries them; call the backward BEFORE the batch's embedding update.  There is no
+ * once-only SGD fold at these widths. */
+int cdlrm_gather_interact_xwide_supported(cdlrm_ctx* ctx);
+int cdlrm_gather_interact_xwide_fwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x, int64_t B,
+                                    int32_t itself, float* R, int64_t ld_r, void* stream);
+int cdlrm_gather_interact_xwide_bwd(cdlrm_ctx* ctx, const int32_t* slots, int64_t n, const float* x, int64_t ld_x,
+                                    const float* dR, int64_t ld_r, int64_t B, int32_t itself, int32_t x_act, float* dfeat,
+                                    void* stream);
+/* Grid (workgroups of 256 lanes: a sample per workgroup, striding; min(B, 512) forward, min(B, 256) backward) and dynamic LDS of
+ * such a launch on B samples: op CDLRM_IA_OP_FWD / CDLRM_IA_OP_BWD.  From the plan the two calls launch from; refused where they
+ * refuse the context.  No device is touched. */
+int cdlrm_gather_interact_xwide_grid(cdlrm_ctx* ctx, int32_t op, int64_t B, int64_t* grid, int64_t* lds_bytes);
 /* Linear + activation (create_mlp, model_no_ddp.py:244-270): Y = act(X W^T + b).
  * X [M, K] ld_x, W [N, K] row-major (nn.Linear.weight), Y [M, N] ld_y. act: 0 none, 1 ReLU, 2 sigmoid. */
 /* CDLRM_GEMM_ALONE, or-ed into `act` of cdlrm_linear_fwd / cdlrm_linear_bwd: the caller's promise that no other GEMM runs beside
