@@ -152,6 +152,9 @@ PROTOTYPES = {
     "cdlrm_interact_xwide_fwd": (C.c_int, [vp, c_i64, c_i32, c_i32, c_i32, vp, c_i64, vp]),
     "cdlrm_interact_xwide_bwd": (C.c_int, [vp, vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, vp, vp]),
     "cdlrm_interact_xwide_route": (C.c_int, [c_i32, c_i64, c_i32, c_i32, c_i32, c_i64, c_i32, C.POINTER(InteractRoute)]),
+    "cdlrm_interact_xwide_b16_fwd": (C.c_int, [vp, c_i64, c_i32, c_i32, c_i32, c_i32, vp, c_i64, vp]),
+    "cdlrm_interact_xwide_b16_bwd": (C.c_int, [vp, vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, vp, vp]),
+    "cdlrm_interact_xwide_b16_route": (C.c_int, [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_i64, c_i32, C.POINTER(InteractRoute)]),
     "cdlrm_gather_interact_wide_supported": (C.c_int, [vp]),
     "cdlrm_gather_interact_wide_fwd": (C.c_int, [vp, vp, c_i64, vp, c_i64, c_i64, c_i32, vp, c_i64, vp]),
     "cdlrm_gather_interact_wide_bwd": (C.c_int, [vp, vp, c_i64, vp, c_i64, vp, c_i64, c_i64, c_i32, c_i32, vp, vp]),

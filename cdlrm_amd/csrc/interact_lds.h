@@ -45,6 +45,20 @@ __host__ __device__ constexpr int ix_fwd_floats(int FP, int npairs) { return 2 *
 __host__ __device__ constexpr int ix_bwd_floats(int FP, int D, int npairs) {
     return 2 * ix_slice(FP) + D + ix_pair_row(npairs) + 4 * ix_out_tile();
 }
+// bf16 / bf16x3 extra-wide kernels (interact_xwide_b16.hip): the slices hold PL bf16 planes (1: hi, 2: hi and lo)
+// instead of fp32 words; footprints still in floats per workgroup.  Forward: a plane is [FP][32 + 8] bf16, contraction (column)
+// contiguous -- an 80-byte pitch, an odd multiple of 16 B.  Backward: a plane is the TRANSPOSE [32][FP + 8] bf16, contraction
+// (feature) contiguous -- 208 / 272 bytes, odd multiples of 16 B too -- and row 0 of the slab stays fp32 beside each slice (32
+// words: act' needs the bottom MLP's output unrounded).  Pair row, dR row and output tiles are those of the fp32 kernels.
+#define IXB_FWD_PITCH 40
+__host__ __device__ constexpr int ixb_bwd_pitch(int FP) { return FP + 8; }
+__host__ __device__ constexpr int ixb_fwd_slice(int FP, int PL) { return PL * FP * IXB_FWD_PITCH / 2; }
+__host__ __device__ constexpr int ixb_bwd_slice(int FP, int PL) { return PL * 32 * ixb_bwd_pitch(FP) / 2; }
+__host__ __device__ constexpr int ixb_row0() { return 32; }
+__host__ __device__ constexpr int ixb_fwd_floats(int FP, int PL, int npairs) { return 2 * ixb_fwd_slice(FP, PL) + ix_pair_row(npairs); }
+__host__ __device__ constexpr int ixb_bwd_floats(int FP, int PL, int D, int npairs) {
+    return 2 * ixb_bwd_slice(FP, PL) + 2 * ixb_row0() + D + ix_pair_row(npairs) + 4 * ix_out_tile();
+}
 
 // ---- host helpers of the entry points in dense.hip and interact_wide.hip --------------------------------------------------------
 // run-time D4 of the pipelined kernels -> compile-time: fn(std::integral_constant<int, D4>{})

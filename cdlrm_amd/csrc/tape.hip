@@ -109,6 +109,7 @@ static const std::vector<TapeEntry>& tape_registry() {
         TAPE_FN(cdlrm_qr_interact_fwd), TAPE_FN(cdlrm_qr_interact_bwd), TAPE_FN(cdlrm_interact_wide_fwd), TAPE_FN(cdlrm_interact_wide_bwd),
         TAPE_FN(cdlrm_gather_interact_wide_fwd), TAPE_FN(cdlrm_gather_interact_wide_bwd),
         TAPE_FN(cdlrm_interact_xwide_fwd), TAPE_FN(cdlrm_interact_xwide_bwd),
+        TAPE_FN(cdlrm_interact_xwide_b16_fwd), TAPE_FN(cdlrm_interact_xwide_b16_bwd),
         TAPE_FN(cdlrm_gather_interact_xwide_fwd), TAPE_FN(cdlrm_gather_interact_xwide_bwd),
         TAPE_FN(cdlrm_linear_bwd), TAPE_FN(cdlrm_mlp_wgrad), TAPE_FN(cdlrm_mlp_wgrad_sgd), TAPE_FN(cdlrm_mlp_wgrad_ex),
         TAPE_FN(cdlrm_mlp_wgrad_sgd_ex), TAPE_FN(cdlrm_bce_fwd_bwd),

@@ -718,6 +718,7 @@ class StepPath(NamedTuple):
     lr_embeds: float
     lr_cells: bool = False          # the rate arguments are the engine's two rate cells, not literals
     gather_wide: bool = False       # `fused` on the wide pair (cdlrm_gather_interact_wide_fwd / _bwd; F > 64: _xwide_, 4.13)
+    interact_precision: str = "fp32"    # "bf16" / "bf16x3": the dot interaction on cdlrm_interact_xwide_b16_fwd / _bwd (F > 64)
     embed_optimizer: str = "sgd"    # the cache rows' update: "sgd" or "rowwise_adagrad" 
     adagrad_eps: float = 0.0
     dense_optimizer: str = "sgd"    # the MLP parameters' update: "sgd" or "adagrad" 
@@ -725,6 +726,7 @@ class StepPath(NamedTuple):
 
 
 EMBED_OPTIMIZERS = ("sgd", "rowwise_adagrad")
+INTERACT_PRECISIONS = ("fp32", "bf16", "bf16x3")
 DENSE_OPTIMIZERS = ("sgd", "adagrad")
 
 
@@ -1277,6 +1279,12 @@ class MergePump:
 
 
 class TrainEngine:
+    # The dot interaction's own precision knob: "fp32", or "bf16" / "bf16x3" -- at 64 to 127 tables the interaction
+    # then runs on cdlrm_interact_xwide_b16_fwd / _bwd (one rounding per operand element / two bf16 planes and three products).
+    # A plain attribute, assigned between steps like matmul_precision and independent of it; below 64 tables, and with cat, it
+    # changes nothing.
+    interact_precision = "fp32"
+
     def __init__(self, cache_group: Embedding_Table_Cache_Group, dlrm: DLRM_Net, host_tables: Embedding_Table_Group,
                  *, lr: float, lr_embeds: float, world_size: int = 1, rank: int = 0, table_agg_freq: int = 1,
                  table_agg_op: str = "mean", process_group=None, loss: str = "bce", loss_weights=(1.0, 1.0),
@@ -1762,9 +1770,25 @@ class TrainEngine:
         Multi-hot bags and quotient-remainder tables stay on two operators there."""
         if not (self.fuse_gather_wide and lS_o is None and self.qr is None and not self.cat and S.is_hip(self.dev)):
             return False
+        if self._ia_precision() != "fp32":      # the precision kernels have no gather inside: two operators
+            return False
         if self.F > ops.IA_WIDE_F:
             return bool(ops.gather_interact_xwide_supported(self.ctx))
         return bool(self.F > ops.IA_NARROW_F and ops.gather_interact_wide_supported(self.ctx))
+
+    def _ia_precision(self) -> str:
+        """The precision the dot interaction runs at: interact_precision where the precision kernels exist (F > 64, dot), else
+        "fp32" -- such steps key and record exactly as without the knob.  An unknown name is a ValueError before any GPU call."""
+        if self.interact_precision == "fp32":
+            return "fp32"
+        if self.interact_precision not in INTERACT_PRECISIONS:
+            raise ValueError("interact_precision: 'fp32', 'bf16' or 'bf16x3', not %r" % (self.interact_precision,))
+        return self.interact_precision if self.F > ops.IA_WIDE_F and not self.cat else "fp32"
+
+    @staticmethod
+    def _ia(precision: str) -> dict:
+        """The keyword of ops.interact_fwd / interact_bwd for a precision; none for fp32: today's call."""
+        return {} if precision == "fp32" else {"precision": precision}
 
     def _gather_wide_calls(self):
         """(forward, backward) of the pair `StepPath.gather_wide` means at this engine's feature count."""
@@ -1840,7 +1864,7 @@ class TrainEngine:
             embed_optimizer=self.embed_optimizer, adagrad_eps=self.adagrad_eps if self.embed_optimizer != "sgd" else 0.0,
             dense_optimizer=self.dense_optimizer,
             dense_adagrad_eps=self.dense_adagrad_eps if self.dense_optimizer != "sgd" else 0.0, lr_cells=bool(self.lr_cells),
-            gather_wide=gather_wide)
+            gather_wide=gather_wide, interact_precision=self._ia_precision())
 
     def _take(self, idx, res, phase: int, which, st):
         """A batch's (slots, miss_pos, miss_count) into the probe buffers `which`, misses into aux region `phase`, on stream st:
@@ -2059,6 +2083,7 @@ class TrainEngine:
         [T, n] holds this batch's remainders (qr_split; columns of a window's r rectangle are fine).
         Returns the device loss buffer (element 0 = the loss, 1 = correct predictions, 2 = loss * batch)."""
         B, n = X.shape[0], lS_i.shape[1]
+        self._ia_precision()        # (an unknown interact_precision: a ValueError before any GPU call)
         if self.qr is not None:
             if lS_o is not None:
                 raise ValueError("quotient-remainder mode takes one lookup per bag (the operator pools before it combines)")
@@ -2300,7 +2325,7 @@ class TrainEngine:
             else:
                 ops.gather_interact_fwd(ctx, slots, feat[:, 0, :], self.itself, R)
         elif not self.cat:
-            ops.interact_fwd(feat, self.itself, R)
+            ops.interact_fwd(feat, self.itself, R, **self._ia(path.interact_precision))
         if path.resolve_cols is not None:
             self._issue_resolve(self._pending_resolve, rec, main, placed=path)
         cur = R
@@ -2395,7 +2420,7 @@ class TrainEngine:
             elif fused:
                 ops.gather_interact_bwd(ctx, slots, feat[:, 0, :], dR, self.itself, dfeat, x_act=self.bot[-1][1])
             else:
-                ops.interact_bwd(feat, dR, self.itself, dfeat, x_act=self.bot[-1][1])
+                ops.interact_bwd(feat, dR, self.itself, dfeat, x_act=self.bot[-1][1], **self._ia(path.interact_precision))
         # embedding backward + sparse SGD on a side stream, overlapped with the bottom-MLP backward and the
         # gradient all-reduce (the reference overlaps optimizer_embeds.step() with the all-reduce, :412-414)
         if not attach or self.cat:
@@ -2481,6 +2506,7 @@ class TrainEngine:
             # reduced into rows).  Every rank calls drain_merge() at the same step first -- Run does, in front of its rank-0
             # test block.
             raise RuntimeError("evaluate(): a row merge is still draining; every rank has to call drain_merge() first")
+        self._ia_precision()        # (an unknown interact_precision: a ValueError before any GPU call)
         self.finish()
         pend = self._pref
         if pend is not None and pend.phase == self._phase:
@@ -2516,7 +2542,7 @@ class TrainEngine:
             else:
                 ops.embbag_fwd(ctx, slots, lS_o, feat[:, 1:, :], feat.stride(0), D, n_bags=(B if lS_o is None else lS_o.shape[1]))
             if not self.cat:
-                ops.interact_fwd(feat, self.itself, R)
+                ops.interact_fwd(feat, self.itself, R, **self._ia(self._ia_precision()))
         cur = R
         for i, (l, act) in enumerate(self.top):
             y = buf["top_y"][i]

@@ -100,6 +100,10 @@ def ProcessArgs(argv=None):
     # 32 to 127 tables, one index per bag: the gather inside the wide interaction kernels (cdlrm_gather_interact_wide_fwd / _bwd;
     # from 64 tables cdlrm_gather_interact_xwide_fwd / _bwd) instead of cdlrm_embbag_fwd + cdlrm_interact_wide_fwd / _bwd
     parser.add_argument("--fuse-gather-wide", action="store_true", default=False)
+    # The dot interaction's own precision, independent of --matmul-precision: from 64 tables bf16 / bf16x3 run it
+    # on cdlrm_interact_xwide_b16_fwd / _bwd (one rounding per operand element / two bf16 planes, three products); below, no change.
+    # (checked below and not by argparse `choices`: the run ends with the one ERROR: line every other refusal prints)
+    parser.add_argument("--interaction-precision", type=str, default="fp32")
     # ---- debugging and profiling ----
     parser.add_argument("--print-freq", type=int, default=1)
     parser.add_argument("--test-freq", type=int, default=-1)
@@ -187,6 +191,8 @@ def ProcessArgs(argv=None):
     except ValueError as e:
         sys.exit("ERROR: --embed-optimizer=%s: %s" % (args.embed_optimizer, e))
     # (checked here and not by argparse `choices`: the run ends with the one ERROR: line every other refusal prints)
+    if args.interaction_precision not in ("fp32", "bf16", "bf16x3"):
+        sys.exit("ERROR: --interaction-precision=%s is not supported (fp32 | bf16 | bf16x3)" % args.interaction_precision)
     if args.insert_policy not in ("reference", "fill"):
         sys.exit("ERROR: --insert-policy=%s is not supported (reference | fill)" % args.insert_policy)
     if args.insert_policy == "fill" and args.data_generation in ("random", "synthetic"):
@@ -566,10 +572,12 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
             print("Quotient-remainder steps: %s" % ("compose inside the interaction kernels (cdlrm_qr_interact_fwd / _bwd)"
                                                      if eng._fused_gather(None) else
                                                      "cdlrm_qr_cached_fwd + interaction as two operators (%s)" % why), flush=True)
+    eng.interact_precision = getattr(args, "interaction_precision", "fp32")
     if getattr(args, "fuse_gather_wide", False):
         eng.fuse_gather_wide = True
         if rank == 0:
-            why = ("--qr-flag" if eng.qr is not None else "--arch-interaction-op=cat" if eng.cat else
+            why = ("--interaction-precision=%s" % eng.interact_precision if eng._ia_precision() != "fp32" else
+                   "--qr-flag" if eng.qr is not None else "--arch-interaction-op=cat" if eng.cat else
                    "dot interaction, a cache of fewer than 2^31 float4 words; 32 < tables + 1 <= 64: D in 32 / 64 / 128 / 256; "
                    "64 < tables + 1 <= 128: D % 4 == 0, D <= 512")
             pair = "extra-wide interaction kernels (cdlrm_gather_interact_xwide_fwd" if eng.F > ops.IA_WIDE_F else \
@@ -578,6 +586,18 @@ def Run(rank, m_spa, ln_emb, ln_bot, ln_top, train_ld, test_ld, batch_fifo, evic
                                            if eng._gather_wide(None) else
                                            "--fuse-gather-wide has no kernel for this model (%s): the route of a run without it" % why),
                   flush=True)
+    if eng.interact_precision != "fp32":
+        if rank == 0:
+            if eng._ia_precision() == "fp32":
+                how = "--interaction-precision=%s has no kernel for this model (%s): the run is the run without it" % (
+                    args.interaction_precision, "--arch-interaction-op=cat" if eng.cat else "64 to 127 tables")
+            else:
+                how = "%s operands on cdlrm_interact_xwide_b16_fwd / _bwd behind the gather (%s)" % (
+                    args.interaction_precision, "one rounding per operand element" if args.interaction_precision == "bf16" else
+                    "two bf16 planes, three products")
+                if eng.fuse_gather_wide:
+                    how += "; the precision kernels have no gather inside: --fuse-gather-wide is set aside"
+            print("Interaction: %s" % how, flush=True)
     pipe = WindowPipeline(cache_group, emb_tables, L * aux_rows * 2, parity_rng=not args.device_rng,
                           seed=args.numpy_rand_seed, average_on_writeback=args.average_on_writeback, rank=rank,
                           world_size=world, host_gather=lookahead_plan,

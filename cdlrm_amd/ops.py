@@ -646,22 +646,45 @@ IA_NARROW_F = 32          # features one 32x32 Gram tile holds; 33 .. 64 go to t
 IA_WIDE_F = 64            # features one wave's 64x64 Gram matrix holds; 65 .. 128 go to csrc/interact_xwide.hip
 
 
+IA_PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x3": 2}     # operand planes of csrc/interact_xwide_b16.hip (0: the fp32 kernels)
+
+
 def _interact_entry(F: int, op: str):
     """The C entry point interact_fwd (op "fwd") / interact_bwd ("bwd") calls at F features."""
     width = "xwide_" if F > IA_WIDE_F else "wide_" if F > IA_NARROW_F else ""
     return getattr(_lib.lib(), "cdlrm_interact_%s%s" % (width, op))
 
 
-def interact_fwd(feat: torch.Tensor, itself: bool, R: torch.Tensor, stream=None):
+def _interact_planes(F: int, precision) -> int:
+    """Operand planes of the precision kernels, 0 for the fp32 entry points: precision None / "fp32", or a
+    feature count the precision kernels do not serve -- an ineligible shape keeps its route."""
+    if precision is not None and precision not in IA_PRECISIONS:
+        raise ValueError("interaction precision: 'fp32', 'bf16' or 'bf16x3', not %r" % (precision,))
+    return IA_PRECISIONS[precision] if precision is not None and F > IA_WIDE_F else 0
+
+
+def interact_fwd(feat: torch.Tensor, itself: bool, R: torch.Tensor, stream=None, precision=None):
+    """precision "bf16" / "bf16x3" at F > 64: cdlrm_interact_xwide_b16_fwd with one / two bf16 operand planes."""
     B, F, D = feat.shape
+    planes = _interact_planes(F, precision)
+    if planes:
+        check(_lib.lib().cdlrm_interact_xwide_b16_fwd(feat.data_ptr(), B, F, D, int(bool(itself)), planes, R.data_ptr(), R.stride(0),
+                                                      stream_ptr(stream)))
+        return
     fn = _interact_entry(F, "fwd")
     check(fn(feat.data_ptr(), B, F, D, int(bool(itself)), R.data_ptr(), R.stride(0), stream_ptr(stream)))
 
 
-def interact_bwd(feat: torch.Tensor, dR: torch.Tensor, itself: bool, dfeat: torch.Tensor, stream=None, x_act: int = 0):
+def interact_bwd(feat: torch.Tensor, dR: torch.Tensor, itself: bool, dfeat: torch.Tensor, stream=None, x_act: int = 0,
+                 precision=None):
     """x_act: activation that produced feature 0 (the bottom MLP's output); its gradient row then leaves as the
-    pre-activation gradient."""
+    pre-activation gradient.  precision: as in interact_fwd (cdlrm_interact_xwide_b16_bwd)."""
     B, F, D = feat.shape
+    planes = _interact_planes(F, precision)
+    if planes:
+        check(_lib.lib().cdlrm_interact_xwide_b16_bwd(feat.data_ptr(), dR.data_ptr(), dR.stride(0), B, F, D, int(bool(itself)),
+                                                      int(x_act), planes, dfeat.data_ptr(), stream_ptr(stream)))
+        return
     fn = _interact_entry(F, "bwd")
     check(fn(feat.data_ptr(), dR.data_ptr(), dR.stride(0), B, F, D, int(bool(itself)), int(x_act), dfeat.data_ptr(),
              stream_ptr(stream)))
@@ -852,7 +875,7 @@ def qr_interact_grid(op: int, B: int, D: int):
 
 
 IA_OPS = {"fwd": 0, "bwd": 1, "gather_fwd": 2, "gather_bwd": 3, "gather_bwd_sgd": 4}
-IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db", 5: "wide_slab", 6: "wide_row", 7: "xwide"}
+IA_FAMILIES = {1: "generic", 2: "row", 3: "slab", 4: "slab_db", 5: "wide_slab", 6: "wide_row", 7: "xwide", 8: "xwide_b16"}
 
 
 def interact_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, aligned_r: bool = True,
@@ -885,6 +908,18 @@ def interact_xwide_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: in
     out = _lib.InteractRoute()
     check(_lib.raw().cdlrm_interact_xwide_route(IA_OPS[op], int(B), int(F), int(D), int(bool(itself)), int(ld_r),
                                                 int(bool(aligned_r)) | int(bool(aligned_dfeat)) << 1, C.byref(out)))
+    return {"family": IA_FAMILIES[out.family], "d4": out.d4, "ns": out.ns, "grid": out.grid, "lds_bytes": out.lds_bytes}
+
+
+def interact_xwide_b16_route(op: str, B: int, F: int, D: int, itself: bool, ld_r: int, precision: str, aligned_r: bool = True,
+                             aligned_dfeat: bool = True) -> dict:
+    """interact_xwide_route for the calls interact_fwd / interact_bwd make at 64 < F <= 128 with precision "bf16" / "bf16x3":
+    family "xwide_b16", lds_bytes that of the bf16 images.  A shape or precision those calls refuse raises their error.  No device
+    is touched."""
+    out = _lib.InteractRoute()
+    planes = precision if isinstance(precision, int) else IA_PRECISIONS.get(precision, -1)
+    check(_lib.raw().cdlrm_interact_xwide_b16_route(IA_OPS[op], int(B), int(F), int(D), int(bool(itself)), int(planes), int(ld_r),
+                                                    int(bool(aligned_r)) | int(bool(aligned_dfeat)) << 1, C.byref(out)))
     return {"family": IA_FAMILIES[out.family], "d4": out.d4, "ns": out.ns, "grid": out.grid, "lds_bytes": out.lds_bytes}
 
 

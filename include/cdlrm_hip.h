@@ -594,6 +594,7 @@ int cdlrm_qr_interact_grid(int32_t op, int64_t B, int32_t D, int64_t* grid, int6
 #define CDLRM_IA_WIDE_SLAB 5    /* k_interact_wide_fwd / _bwd<d4> (32 < F <= 64): 32-column slabs, a register ring of loads */
 #define CDLRM_IA_WIDE_ROW 6     /* k_interact_wide_fwd_row / _bwd_row (32 < F <= 64): any D, the sample's whole rows staged */
 #define CDLRM_IA_XWIDE 7        /* k_interact_xwide_fwd / _bwd<nb> (64 < F <= 128): a workgroup per sample, double-buffered slabs */
+#define CDLRM_IA_XWIDE_B16 8    /* k_interact_xwide_b16_fwd / _bwd<nb, planes> (64 < F <= 128): the xwide split on the bf16 matrix pipe */
 #define CDLRM_IA_OP_FWD 0               /* cdlrm_interact_fwd */
 #define CDLRM_IA_OP_BWD 1               /* cdlrm_interact_bwd */
 #define CDLRM_IA_OP_GATHER_FWD 2        /* cdlrm_gather_interact_fwd */
@@ -642,6 +643,21 @@ int cdlrm_interact_xwide_bwd(const float* feat, const float* dR, int64_t ld_r, i
  * slabs of a sample.  A shape the entry point refuses is refused here with its error.  No device is touched. */
 int cdlrm_interact_xwide_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int64_t ld_r, int32_t aligned,
                                struct cdlrm_interact_route* out);
+/* cdlrm_interact_xwide_fwd / _bwd on the bf16 matrix pipe (csrc/interact_xwide_b16.hip), opt-in: the same operands, layouts,
+ * shapes, tiers and refusals.  planes 1 ("bf16"): every operand element of the two contractions -- feat in the forward, S = G + G^T
+ * and feat in the backward -- is rounded once to bf16 (round-to-nearest-even) on its way into LDS.  planes 2 ("bf16x3"): every
+ * element is split into two bf16 planes (x ~ h + l, h = bf16(x), l = bf16(x - h), l = 0 where h is not finite) and a product is
+ * al*bh + ah*bl + ah*bh, near-fp32 error.  Any other `planes` is refused.  Accumulation is fp32; R[:, :D] and the dR[:, :D] term
+ * of dfeat row 0 are exact.  No atomics: two launches give the same bits.  cdlrm_interact_xwide_b16_bwd carries an attached
+ * completion event like cdlrm_interact_xwide_bwd. */
+int cdlrm_interact_xwide_b16_fwd(const float* feat, int64_t B, int32_t F, int32_t D, int32_t itself, int32_t planes,
+                                 float* R, int64_t ld_r, void* stream);
+int cdlrm_interact_xwide_b16_bwd(const float* feat, const float* dR, int64_t ld_r, int64_t B, int32_t F, int32_t D,
+                                 int32_t itself, int32_t x_act, int32_t planes, float* dfeat, void* stream);
+/* cdlrm_interact_route for the two calls above: family CDLRM_IA_XWIDE_B16; lds_bytes depends on `planes`.  A shape or a plane
+ * count the entry points refuse is refused here with their error.  No device is touched. */
+int cdlrm_interact_xwide_b16_route(int32_t op, int64_t B, int32_t F, int32_t D, int32_t itself, int32_t planes, int64_t ld_r,
+                                   int32_t aligned, struct cdlrm_interact_route* out);
 /* Cached EmbeddingBag forward + interact_features "dot" in ONE launch (model_no_ddp.py:200-203 + :272-293) for 32 to 63 tables:
  * cdlrm_gather_interact_fwd / _bwd on the pipelined kernels of csrc/interact_wide.hip, with the same arguments, the same checks
  * (n >= B, T * n < 2^31, 16-byte aligned x with ld_x % 4 == 0, whole-float4 R / dR rows, 16-byte aligned dfeat) and the same
